@@ -7,17 +7,23 @@ State, mesh, Hessians and factors are resident in HBM before the timed region st
 host hands over only the scripted handle positions (~24 KB) and reads back a few hundred bytes of
 reduction partials per line-search trial.
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the
+steps and prints the line; besides the contract's keys it carries what the timed steps themselves report:
   roofline      the dominant hand-written kernel pair (subdomain back-solve), algorithmic bytes /
                 measured HIP-event time on the library's stream, against 8 TB/s
+`--dump-outputs DIR` writes the state the last timed step left (positions, velocities) and its energy / gradient
+norm / iterations as DIR/<name>.npy (float64).
+`--full` adds everything that takes runs of its own and writes bench_detail.json:
+  workloads     short runs of the other configurations (--extra-workloads)
+  roofline_by_kernel  every kernel class launched back to back on the resident state (dotmi_bench_kernel)
   cpu_baseline  the CPU oracle (a port of the reference algorithm, oracle/dot_oracle.c) timed on the
                 host cores of this box on a bounded sample of the same workload -- headline leg: with the
                 reference's own CHOLMODSolver (oracle/_ref) doing the subdomain factorisations and solves;
-                variant: the port's own envelope Cholesky
+                variant: the port's own envelope Cholesky (--no-cpu-baseline leaves it out)
 
 `python bench.py --gpus N` with N > 1 and no launcher starts its N ranks itself (torch.distributed.run on
 127.0.0.1); it refuses to run when the box has fewer GPUs, and n_gpus is checked against ncclCommCount.
@@ -155,15 +161,37 @@ def compact_line(full):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: each array as dirname/<name>.npy in float64.  An array above its even share of `limit` keeps a
+    fixed sample of its rows (seed 0, sorted), so that two runs of the same arguments write the same rows."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = limit // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.nbytes > share:
+            row = a.nbytes // a.shape[0]
+            keep = np.sort(np.random.default_rng(0).choice(a.shape[0], max(share // row, 1), replace=False))
+            a = a[keep]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default=DEFAULT_WORKLOAD)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the extra workloads, the per-kernel rooflines, the CPU baseline and bench_detail.json")
     ap.add_argument("--extra-workloads", default=EXTRA_WORKLOADS,
-                    help="comma list of further workloads reported in the `workloads` array, or `none`")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="(--full) comma list of further workloads reported in the `workloads` array, or `none`")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) leave out the CPU baseline")
     ap.add_argument("--cpu-steps", type=int, default=12)
     ap.add_argument("--cpu-threads", type=int, default=0)
     args = ap.parse_args()
@@ -327,9 +355,10 @@ def main():
                         "one thread: best of 3 numeric factorisations / best of 10 solves per subdomain, summed over the subdomains (own-element matrices, "
                         "the pattern of H_s); the reference runs them concurrently under TBB"}
 
-    def run_workload(name, steps, warmup):
+    def run_workload(name, steps, warmup, full=True, dump_dir=None):
         """-> (record, per-step stats, scene, timestepper is closed).  A trailing "+owner" (N > 1) runs the workload with
-        DOTMI_FLAG_OWNER_EXCHANGE: interface-only vector collectives, the dot products in their tails"""
+        DOTMI_FLAG_OWNER_EXCHANGE: interface-only vector collectives, the dot products in their tails.  full: also the
+        per-kernel rooflines; dump_dir: write the outputs of the last timed step there (write_outputs)"""
         owner = name.endswith("+owner")
         label = name
         if owner:
@@ -376,6 +405,12 @@ def main():
             t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
+        if dump_dir:
+            # before the per-kernel rooflines below: their launches run on the live state
+            x, v, _ = ts.getState()
+            last = stats[-1]
+            write_outputs(dump_dir, {"positions": x, "velocities": v,
+                                     "last_step": [last.E, last.g2, last.iters, last.ls_halvings]})
         iters = [s.iters for s in stats]
         # ---- roofline of the dominant hand-written kernel, measured inside the timed region -----------------
         pre_ms = sum(s.ms_precond for s in stats)
@@ -476,7 +511,7 @@ def main():
             "factor_storage_bytes": rec.get("factor_storage_bytes"),
         }
         target = ts.targetGRes
-        rec["roofline_by_kernel"] = kernel_rooflines(ts, rec) if rank == 0 or world == 1 else None
+        rec["roofline_by_kernel"] = kernel_rooflines(ts, rec) if full and (rank == 0 or world == 1) else None
         # ---- the loop as a whole: device time of the L-BFGS loop per iteration (comparable across rounds where
         # a chaotic workload's iteration count moves) and the algorithmic bytes one iteration's launches read and write -- the
         # back-solve's structural non-zeros + the four vector kernels' section 8(d) bytes in the forms the loop launches -- over it
@@ -500,7 +535,8 @@ def main():
         ts.close()
         return rec, stats, sc, nparts, target, elapsed
 
-    rec, stats, sc, nparts, target_gres, elapsed = run_workload(args.workload, args.steps, args.warmup)
+    rec, stats, sc, nparts, target_gres, elapsed = run_workload(args.workload, args.steps, args.warmup, full=args.full,
+                                                                dump_dir=args.dump_outputs if rank == 0 else None)
     cfg = sc.cfg
     ms_per_step = rec["ms_per_step"]
     iters = rec["iters"]
@@ -512,7 +548,7 @@ def main():
 
     # ---- the other configurations BASELINE.json / north_star name, short runs (every rank takes part) --------------
     extra = []
-    if args.extra_workloads and args.extra_workloads != "none":
+    if args.full and args.extra_workloads and args.extra_workloads != "none":
         names = args.extra_workloads.split(",")
         if world > 1:
             # N > 1: the two configurations meant to scale also under the owner exchange (interface-only collectives), next to
@@ -563,7 +599,7 @@ def main():
         if extra:
             out["workloads"] = [rec] + extra
         # ---- CPU baseline on this box's host cores: bounded sample of the same workload ---------------
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             from tests import oracle_py as O
             threads = args.cpu_threads or min(os.cpu_count() or 1, 16)
             O.lib().dor_set_threads(threads)
@@ -635,18 +671,18 @@ def main():
                 out["cpu_baseline"]["reference_cholmod"] = reference_cholmod_leg(sc2, ep2, nparts, orc)
             except Exception as e:   # noqa: BLE001 - the leg is optional (needs oracle/_ref + the image's MKL)
                 out["cpu_baseline"]["reference_cholmod"] = {"error": f"{type(e).__name__}: {e}"}
-        # the full record (per-kernel rooflines, PMC sources, per-workload detail, the long explanatory strings) goes to a
-        # side file; the ONE stdout line stays below 4 KB so that the driver's parser gets all of it
-        detail_paths = [os.path.join(ROOT, "bench_detail.json")]
-        if os.path.isdir(os.path.join(ROOT, "gpurun_out")):
-            detail_paths.append(os.path.join(ROOT, "gpurun_out", f"bench_detail_n{world}.json"))
-        for dp_ in detail_paths:
+        line = compact_line(out)
+        if args.full:
+            # the full record (per-kernel rooflines, PMC sources, per-workload detail, the long explanatory strings) goes to a
+            # side file; the ONE stdout line stays below 4 KB so that the driver's parser gets all of it
             try:
-                with open(dp_, "w") as fh:
+                with open(os.path.join(ROOT, "bench_detail.json"), "w") as fh:
                     json.dump(out, fh, indent=1)
             except OSError:
                 pass
-        print(json.dumps(compact_line(out)), flush=True)
+        else:
+            del line["detail"]
+        print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

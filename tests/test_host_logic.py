@@ -564,6 +564,24 @@ def test_bench_source_id_is_stable_and_pmc_files_carry_it():
     assert a == b and len(a) == 12 and int(a, 16) >= 0
 
 
+def test_bench_dump_outputs_are_float64_bounded_and_the_same_rows_every_run(tmp_path):
+    """--dump-outputs: every array as <name>.npy in float64; above its share of the limit an array keeps a fixed row sample"""
+    import bench
+    x = np.arange(3000.0).reshape(1000, 3)
+    arrays = {"positions": x, "last_step": [1.5, 2e-7, 26, 0]}
+    bench.write_outputs(str(tmp_path / "a"), arrays)
+    assert np.array_equal(np.load(tmp_path / "a" / "positions.npy"), x)
+    s = np.load(tmp_path / "a" / "last_step.npy")
+    assert s.dtype == np.float64 and s.tolist() == [1.5, 2e-7, 26.0, 0.0]
+    for d in ("b", "c"):
+        bench.write_outputs(str(tmp_path / d), arrays, limit=2 * 24 * 100)
+    p = np.load(tmp_path / "b" / "positions.npy")
+    assert p.shape == (100, 3) and np.array_equal(p, np.load(tmp_path / "c" / "positions.npy"))
+    rows = (p[:, 0] / 3).astype(int)
+    assert np.array_equal(p, x[rows]) and np.all(np.diff(rows) > 0)
+    assert sum(f.stat().st_size for f in (tmp_path / "b").iterdir()) < 2 * 24 * 100 + 2 * 128 + 32
+
+
 # ---- the job table of the back-solve launches (dot_amd/csrc/bs_tiles.hpp; round 5) ---------------------------------------
 def _plan_bs_tiles(name, env=None):
     import ctypes as C

@@ -8,7 +8,7 @@ while [ $# -gt 0 ] && [ "$1" != "--" ]; do envs+=("$1"); shift; done
 for r in $(seq 1 $R); do
   for e in "${envs[@]}"; do
     ee="$e"; [ "$e" = "-" ] && ee=""
-    env $ee python bench.py --no-cpu-baseline --extra-workloads "${AB_EXTRA:-}" "$@" 2>/dev/null | tail -1 | E="$e" python -c "
+    env $ee python bench.py ${AB_EXTRA:+--full} --no-cpu-baseline --extra-workloads "${AB_EXTRA:-}" "$@" 2>/dev/null | tail -1 | E="$e" python -c "
 import json,sys,os
 d=json.loads(sys.stdin.read())
 w=d.get('workloads',[])

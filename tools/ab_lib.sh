@@ -4,7 +4,7 @@
 A=$1; B=$2; R=${3:-3}; shift; shift; shift
 for r in $(seq 1 $R); do
   for L in "$A" "$B"; do
-    DOTMI_LIBRARY=$(realpath $L) python bench.py --no-cpu-baseline --extra-workloads "${AB_EXTRA:-}" "$@" 2>/dev/null | tail -1 | python -c "
+    DOTMI_LIBRARY=$(realpath $L) python bench.py ${AB_EXTRA:+--full} --no-cpu-baseline --extra-workloads "${AB_EXTRA:-}" "$@" 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 w=d.get('workloads',[])
