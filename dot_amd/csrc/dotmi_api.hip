@@ -79,6 +79,7 @@ int dotmi_refix(dotmi_handle *h, const uint8_t *fixed)
     if (resolve_refresh(h) == DOTMI_E_DEVICE) return DOTMI_E_DEVICE;   // (asynchronous refresh of the last step)
     h->fixed.assign(fixed, fixed + h->nV);
     HIPCHECK(h, hipMemcpy(h->M.fixed, fixed, h->nV, hipMemcpyHostToDevice));
+    if (h->pd) return pd_factor(h);   // L for the new fixed set (LBFGSTimeStepper::updatePrecondMtrAndFactorize, :266-270)
     return refactor(h, h->x, nullptr, nullptr);
 }
 
@@ -182,6 +183,10 @@ int dotmi_eval_elem_hessians(dotmi_handle *h, const double *x, double *H)
 int dotmi_refactor(dotmi_handle *h, const double *x)
 {
     if (!h) return DOTMI_E_INVALID;
+    if (h->pd) {
+        h->err = "dotmi_refactor: an LBFGS-PD handle has no Hessian block solve";
+        return DOTMI_E_INVALID;
+    }
     HIPCHECK(h, hipSetDevice(h->device));
     if (resolve_refresh(h) == DOTMI_E_DEVICE) return DOTMI_E_DEVICE;   // (asynchronous refresh of the last step)
     const double *xd = h->x;
@@ -200,7 +205,9 @@ int dotmi_apply_precond(dotmi_handle *h, const double *r, double *p)
     if (int rc = upload_tmp(h, r, h->q)) return rc;
     LbfgsArgs L;
     memset(&L, 0, sizeof(L));
-    if (int rc = apply_precond(h, h->q, h->z, L)) return rc;
+    if (h->pd) {
+        if (int rc = pd_apply(h, h->q, h->z, L)) return rc;
+    } else if (int rc = apply_precond(h, h->q, h->z, L)) return rc;
     HIPCHECK(h, hipMemcpyAsync(p, h->z, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->st));
     HIPCHECK(h, hipStreamSynchronize(h->st));
     return 0;
@@ -214,6 +221,10 @@ int dotmi_probe_direction(dotmi_handle *h, const double *x, int32_t m, const dou
                           double *q_out, double *z_out, double *p_out, double *alpha0, double *E_trial)
 {
     if (!h || !x || m < 0 || m > h->hist || (m > 0 && (!S || !Y))) return DOTMI_E_INVALID;
+    if (h->pd) {
+        h->err = "dotmi_probe_direction: an LBFGS-PD handle has no Hessian block solve";
+        return DOTMI_E_INVALID;
+    }
     if (h->dist) {
         h->err = "dotmi_probe_direction: single-GPU handles only";
         return DOTMI_E_INVALID;
@@ -290,6 +301,10 @@ int dotmi_probe_direction(dotmi_handle *h, const double *x, int32_t m, const dou
 int dotmi_spmv(dotmi_handle *h, const double *p, double *Hp)
 {
     if (!h || !p || !Hp) return DOTMI_E_INVALID;
+    if (h->pd) {
+        h->err = "dotmi_spmv: an LBFGS-PD handle has no Hessian block solve";
+        return DOTMI_E_INVALID;
+    }
     if (h->shardHess) {
         h->err = "dotmi_spmv: the rows of the global Hessian are sharded over the ranks on this handle (DOTMI_SHARD_HESS=0 keeps them replicated)";
         return DOTMI_E_INVALID;
@@ -314,17 +329,21 @@ int dotmi_get_features(dotmi_handle *h, double *A, double *vol, double *mass)
 
 int32_t dotmi_part_size(const dotmi_handle *h, int32_t part)
 {
-    if (!h || part < 0 || part >= h->nPartsAll) return DOTMI_E_INVALID;
+    if (!h || h->pd || part < 0 || part >= h->nPartsAll) return DOTMI_E_INVALID;
     return 3 * (int32_t)h->partVerts[part].size();
 }
 
-int32_t dotmi_padded_size(const dotmi_handle *h) { return h ? h->P.nmax : DOTMI_E_INVALID; }
+int32_t dotmi_padded_size(const dotmi_handle *h) { return h ? (h->pd ? h->PD.nmax : h->P.nmax) : DOTMI_E_INVALID; }
 
 int64_t dotmi_factor_storage_bytes(const dotmi_handle *h) { return h ? (int64_t)(8 * h->wTotal) : DOTMI_E_INVALID; }
 
 int dotmi_part_matrix(dotmi_handle *h, int32_t part, int inverse, double *Mout, int32_t *l2g)
 {
     if (!h || part < h->p0 || part >= h->p1 || !Mout) return DOTMI_E_INVALID;
+    if (h->pd) {
+        h->err = "dotmi_part_matrix: an LBFGS-PD handle has no Hessian block solve";
+        return DOTMI_E_INVALID;
+    }
     HIPCHECK(h, hipSetDevice(h->device));
     if (inverse && h->twoLevel) {
         h->err = "the factors are in the two-level form (DOTMI_TWO_LEVEL): there is no explicit inverse of a whole subdomain to return";
@@ -401,9 +420,11 @@ int dotmi_bench_precond(dotmi_handle *h, int32_t reps, double *ms_per_launch, in
     if (!h || reps < 1) return DOTMI_E_INVALID;
     HIPCHECK(h, hipSetDevice(h->device));
     if (int rc = enter_with_factors(h)) return rc;
-    launch_gemv(h->P, h->q, h->st);  // warm
+    // (LBFGS-PD: the apply of L^-1 on the three columns of q, merge included)
+    auto one = [&]() { h->pd ? launch_pd_apply(h->PD, h->nV, h->q, h->z, h->st) : launch_gemv(h->P, h->q, h->st); };
+    one();  // warm
     HIPCHECK(h, hipEventRecord(h->ev0, h->st));
-    for (int i = 0; i < reps; ++i) launch_gemv(h->P, h->q, h->st);
+    for (int i = 0; i < reps; ++i) one();
     HIPCHECK(h, hipEventRecord(h->ev1, h->st));
     HIPCHECK(h, hipEventSynchronize(h->ev1));
     float ms = 0;
@@ -421,6 +442,10 @@ int dotmi_bench_precond(dotmi_handle *h, int32_t reps, double *ms_per_launch, in
 int dotmi_bench_kernel(dotmi_handle *h, int32_t kind, int32_t reps, double *ms_per_launch, int64_t *bytes_per_launch)
 {
     if (!h || reps < 1) return DOTMI_E_INVALID;
+    if (h->pd) {
+        h->err = "dotmi_bench_kernel: an LBFGS-PD handle has no Hessian block solve";
+        return DOTMI_E_INVALID;
+    }
     HIPCHECK(h, hipSetDevice(h->device));
     if (int rc = enter_with_factors(h)) return rc;
     const int n = h->n, nV = h->nV;

@@ -212,6 +212,162 @@ static long long one_pass_nnz(const std::vector<NdNode> &nd, const std::vector<s
 }
 constexpr long long TWO_LEVEL_FROM_BYTES = 240000000ll;   // one-pass bytes per application from which the two-level form is the default
 
+// what the element pass, the refresh's sharding and the owner exchange need beside the subdomains (the tail of build_device_mesh;
+// an LBFGS-PD handle, which has no subdomains, builds this part only)
+static int build_element_side(dotmi_handle *h, const std::vector<int> &adj_ptr, const std::vector<int> &blk_ptr,
+                              const std::vector<int> &blk_ent)
+{
+    const int nV = h->nV, nT = h->nT;
+    // element ownership + inertia vertex slice
+    if (h->shardElems) {
+        std::vector<int> el;
+        for (int e = 0; e < nT; ++e)
+            if (h->epart[e] >= h->p0 && h->epart[e] < h->p1) el.push_back(e);
+        h->nOwnElem = (int)el.size();
+        if (int rc = upload(h, &h->elist, el)) return rc;
+        h->v0 = (int)((long long)nV * h->rank / h->world);
+        h->v1 = (int)((long long)nV * (h->rank + 1) / h->world);
+    } else {
+        h->elist = nullptr;
+        h->nOwnElem = nT;
+        h->v0 = 0;
+        h->v1 = nV;
+    }
+    // ---- sharded refresh lists ------------------------------------------------------------------------------------
+    // The block rows this rank reads: the rows of its subdomains' vertices (dense fill of H_s = R_s H R_s^T) and its
+    // slice [v0, v1) of the SpMV.  Their blocks are sums over the elements incident to the row vertex, so the elements
+    // needed are the rank's own plus the halo that touches its interface vertices -- recomputed locally instead of
+    // exchanging 1152 bytes per element (DOTTimeStepper.cpp:349-380, :574-616 run on every rank's share).
+    h->shardHess = h->shardElems && (h->owner || (h->tune.shardHess >= 0 ? h->tune.shardHess != 0 : true));
+    h->nHessElems = nT;
+    if (h->shardHess) {
+        std::vector<uint8_t> needV(nV, 0);
+        for (int pI = h->p0; pI < h->p1; ++pI)
+            for (int v : h->partVerts[pI]) needV[v] = 1;
+        if (!h->owner)
+            for (int v = h->v0; v < h->v1; ++v) needV[v] = 1;
+        std::vector<int> el, e2c(nT, -1);
+        for (int e = 0; e < nT; ++e)
+            if (needV[h->T[4 * e]] || needV[h->T[4 * e + 1]] || needV[h->T[4 * e + 2]] || needV[h->T[4 * e + 3]]) {
+                e2c[e] = (int)el.size();
+                el.push_back(e);
+            }
+        std::vector<int> bl, bptr(1, 0), bent, optr(1, 0), oent;
+        for (int v = 0; v < nV; ++v) {
+            if (!needV[v]) continue;
+            for (int k = adj_ptr[v]; k < adj_ptr[v + 1]; ++k) {
+                bl.push_back(k);
+                for (int i = blk_ptr[k]; i < blk_ptr[k + 1]; ++i) {
+                    const int e = blk_ent[i] >> 4;
+                    bent.push_back((e2c[e] << 4) | (blk_ent[i] & 15));   // every contributor touches v: listed
+                    if (h->owner && h->epart[e] >= h->p0 && h->epart[e] < h->p1) oent.push_back(bent.back());
+                }
+                bptr.push_back((int)bent.size());
+                optr.push_back((int)oent.size());
+            }
+        }
+        if (h->owner) {
+            if (oent.empty()) oent.push_back(-1);
+            if (int rc = upload(h, &h->ownBlkPtr, optr)) return rc;
+            if (int rc = upload(h, &h->ownBlkEnt, oent)) return rc;
+        }
+        h->nHessElems = (int)el.size();
+        h->nHessBlk = (int)bl.size();
+        if (int rc = upload(h, &h->hessElems, el)) return rc;
+        if (int rc = upload(h, &h->hessBlk, bl)) return rc;
+        if (int rc = upload(h, &h->hessBlkPtr, bptr)) return rc;
+        if (int rc = upload(h, &h->hessBlkEnt, bent)) return rc;
+    }
+    // element patches (patches.hpp): PTall covers every element (the kernel-level entry points evaluate the whole mesh on
+    // every rank), PT this rank's own elements -- the same object unless the element pass is sharded
+    {
+        int PE = h->tune.patchElems > 0 ? (h->tune.patchElems <= 256 ? 256 : 512) : 256;
+        std::vector<int> all(nT);
+        for (int e = 0; e < nT; ++e) all[e] = e;
+        if (int rc = upload_patches(h, build_patches(nV, h->T.data(), h->Xrest.data(), all, PE), h->PTall)) return rc;
+        if (h->shardElems) {
+            std::vector<int> own;
+            for (int e = 0; e < nT; ++e)
+                if (h->epart[e] >= h->p0 && h->epart[e] < h->p1) own.push_back(e);
+            if (int rc = upload_patches(h, build_patches(nV, h->T.data(), h->Xrest.data(), own, PE), h->PT)) return rc;
+        } else {
+            h->PT = h->PTall;
+        }
+        // the patches of a speculating step (one rank): the set that keeps direction rows + patches + trial-point workgroups
+        // resident at once -- the default set where it does, 512-element patches where only those do, none otherwise
+        h->specFits = false;
+        if (!h->dist && h->world == 1 && h->tune.specStep != 0) {
+            const int nbv = (nV + 255) / 256, room = 512 - NB_RED - nbv;
+            if (std::max(h->PT.nPatches, nbv) <= room) {
+                h->PTspec = h->PT;
+                h->specFits = true;
+            } else if (h->tune.patchElems == 0 && PE == 256) {
+                const HostPatches H2 = build_patches(nV, h->T.data(), h->Xrest.data(), all, 512);
+                if (std::max(H2.nPatches, nbv) <= room) {
+                    if (int rc = upload_patches(h, H2, h->PTspec)) return rc;
+                    h->specFits = true;
+                }
+            }
+        }
+    }
+    if (h->owner) {
+        // who holds / owns a vertex: a rank HOLDS the vertices of its subdomains (= of its elements); the lowest rank that
+        // holds a vertex OWNS it (its inertia term, its share of every dot product).  Vertices held by two or more ranks
+        // are the only ones whose entries travel inside the loop.
+        std::vector<int> holders(nV, 0), last(nV, -1), ownerR(nV, -1);
+        for (int r = 0; r < h->world; ++r)
+            for (int pI = h->firstPart[r]; pI < h->firstPart[r + 1]; ++pI)
+                for (int v : h->partVerts[pI])
+                    if (last[v] != r) {
+                        last[v] = r;
+                        holders[v]++;
+                        if (ownerR[v] < 0) ownerR[v] = r;
+                    }
+        std::vector<uint8_t> own(nV, 0), held(nV, 0);
+        std::vector<int> iface;
+        std::vector<double> mo(nV, 0.0);
+        for (int pI = h->p0; pI < h->p1; ++pI)
+            for (int v : h->partVerts[pI]) held[v] = 1;
+        for (int v = 0; v < nV; ++v) {
+            own[v] = ownerR[v] == h->rank || (ownerR[v] < 0 && h->rank == 0);
+            if (own[v]) mo[v] = h->mass[v];
+            if (holders[v] >= 2) iface.push_back(v);
+        }
+        h->nIface = (int)iface.size();
+        if (iface.empty()) iface.push_back(0);
+        std::vector<int> hl;
+        for (int v = 0; v < nV; ++v)
+            if (held[v]) hl.push_back(v);
+        h->nHeld = (int)hl.size();
+        if (hl.empty()) hl.push_back(0);
+        if (int rc = upload(h, &h->heldList, hl)) return rc;
+        if (int rc = upload(h, &h->ownMask, own)) return rc;
+        if (int rc = upload(h, &h->heldMask, held)) return rc;
+        {
+            std::vector<uint8_t> kind(nV);
+            for (int v = 0; v < nV; ++v) kind[v] = (uint8_t)((own[v] ? 1 : 0) | (holders[v] >= 2 ? 2 : 0));
+            if (int rc = upload(h, &h->vkind, kind)) return rc;
+            std::vector<int> sh;
+            for (int v = 0; v < nV; ++v)
+                if (held[v] && holders[v] >= 2) sh.push_back(v);
+            h->nShared = (int)sh.size();
+            if (sh.empty()) sh.push_back(0);
+            if (int rc = upload(h, &h->sharedList, sh)) return rc;
+        }
+        if (int rc = upload(h, &h->ifaceIdx, iface)) return rc;
+        if (int rc = upload(h, &h->massOwn, mo)) return rc;
+        if (int rc = dalloc(h, &h->xpack, (size_t)3 * h->nIface + 8 + RED_K)) return rc;
+        // the element pass' inertia term 1/2 m |x - x~|^2 by ownership too: the same kernel over every vertex with the
+        // owner's share of the mass (positions outside the held vertices stay where the warm start put them)
+        h->Mown = h->M;
+        h->Mown.mass = h->massOwn;
+        if (h->tune.fuseLog)
+            fprintf(stderr, "dotmi: owner exchange: rank %d holds %d of %d vertices, %d are held by more than one rank\n", h->rank,
+                    (int)std::count(held.begin(), held.end(), 1), nV, h->nIface);
+    }
+    return 0;
+}
+
 int build_device_mesh(dotmi_handle *h)
 {
     const int nV = h->nV, nT = h->nT;
@@ -265,6 +421,10 @@ int build_device_mesh(dotmi_handle *h)
     if (int rc = upload(h, &M.blk_ptr, blk_ptr)) return rc;
     if (int rc = upload(h, &M.blk_ent, blk_ent)) return rc;
     if (int rc = upload(h, &M.blk_row, blk_row)) return rc;
+    if (h->pd) {   // LBFGS-PD: the scalar factor of the constant Laplacian instead of the subdomain block solve (dotmi_pd.hip)
+        if (int rc = build_pd(h, adj_ptr, adj_idx)) return rc;
+        return build_element_side(h, adj_ptr, blk_ptr, blk_ent);
+    }
 
     // ---- subdomains (ADMMDDTimeStepper.cpp:88-262) ------------------------------------------------
     const int nP = h->nPartsAll;
@@ -895,154 +1055,7 @@ int build_device_mesh(dotmi_handle *h)
     HIPCHECK(h, hipHostMalloc((void **)&h->h_info, sizeof(int) * std::max(P.nParts, 1)));
     memset(h->h_info, 0, sizeof(int) * std::max(P.nParts, 1));
 
-    // element ownership + inertia vertex slice
-    if (h->shardElems) {
-        std::vector<int> el;
-        for (int e = 0; e < nT; ++e)
-            if (h->epart[e] >= h->p0 && h->epart[e] < h->p1) el.push_back(e);
-        h->nOwnElem = (int)el.size();
-        if (int rc = upload(h, &h->elist, el)) return rc;
-        h->v0 = (int)((long long)nV * h->rank / h->world);
-        h->v1 = (int)((long long)nV * (h->rank + 1) / h->world);
-    } else {
-        h->elist = nullptr;
-        h->nOwnElem = nT;
-        h->v0 = 0;
-        h->v1 = nV;
-    }
-    // ---- sharded refresh lists ------------------------------------------------------------------------------------
-    // The block rows this rank reads: the rows of its subdomains' vertices (dense fill of H_s = R_s H R_s^T) and its
-    // slice [v0, v1) of the SpMV.  Their blocks are sums over the elements incident to the row vertex, so the elements
-    // needed are the rank's own plus the halo that touches its interface vertices -- recomputed locally instead of
-    // exchanging 1152 bytes per element (DOTTimeStepper.cpp:349-380, :574-616 run on every rank's share).
-    h->shardHess = h->shardElems && (h->owner || (h->tune.shardHess >= 0 ? h->tune.shardHess != 0 : true));
-    h->nHessElems = nT;
-    if (h->shardHess) {
-        std::vector<uint8_t> needV(nV, 0);
-        for (int pI = h->p0; pI < h->p1; ++pI)
-            for (int v : h->partVerts[pI]) needV[v] = 1;
-        if (!h->owner)
-            for (int v = h->v0; v < h->v1; ++v) needV[v] = 1;
-        std::vector<int> el, e2c(nT, -1);
-        for (int e = 0; e < nT; ++e)
-            if (needV[h->T[4 * e]] || needV[h->T[4 * e + 1]] || needV[h->T[4 * e + 2]] || needV[h->T[4 * e + 3]]) {
-                e2c[e] = (int)el.size();
-                el.push_back(e);
-            }
-        std::vector<int> bl, bptr(1, 0), bent, optr(1, 0), oent;
-        for (int v = 0; v < nV; ++v) {
-            if (!needV[v]) continue;
-            for (int k = adj_ptr[v]; k < adj_ptr[v + 1]; ++k) {
-                bl.push_back(k);
-                for (int i = blk_ptr[k]; i < blk_ptr[k + 1]; ++i) {
-                    const int e = blk_ent[i] >> 4;
-                    bent.push_back((e2c[e] << 4) | (blk_ent[i] & 15));   // every contributor touches v: listed
-                    if (h->owner && h->epart[e] >= h->p0 && h->epart[e] < h->p1) oent.push_back(bent.back());
-                }
-                bptr.push_back((int)bent.size());
-                optr.push_back((int)oent.size());
-            }
-        }
-        if (h->owner) {
-            if (oent.empty()) oent.push_back(-1);
-            if (int rc = upload(h, &h->ownBlkPtr, optr)) return rc;
-            if (int rc = upload(h, &h->ownBlkEnt, oent)) return rc;
-        }
-        h->nHessElems = (int)el.size();
-        h->nHessBlk = (int)bl.size();
-        if (int rc = upload(h, &h->hessElems, el)) return rc;
-        if (int rc = upload(h, &h->hessBlk, bl)) return rc;
-        if (int rc = upload(h, &h->hessBlkPtr, bptr)) return rc;
-        if (int rc = upload(h, &h->hessBlkEnt, bent)) return rc;
-    }
-    // element patches (patches.hpp): PTall covers every element (the kernel-level entry points evaluate the whole mesh on
-    // every rank), PT this rank's own elements -- the same object unless the element pass is sharded
-    {
-        int PE = h->tune.patchElems > 0 ? (h->tune.patchElems <= 256 ? 256 : 512) : 256;
-        std::vector<int> all(nT);
-        for (int e = 0; e < nT; ++e) all[e] = e;
-        if (int rc = upload_patches(h, build_patches(nV, h->T.data(), h->Xrest.data(), all, PE), h->PTall)) return rc;
-        if (h->shardElems) {
-            std::vector<int> own;
-            for (int e = 0; e < nT; ++e)
-                if (h->epart[e] >= h->p0 && h->epart[e] < h->p1) own.push_back(e);
-            if (int rc = upload_patches(h, build_patches(nV, h->T.data(), h->Xrest.data(), own, PE), h->PT)) return rc;
-        } else {
-            h->PT = h->PTall;
-        }
-        // the patches of a speculating step (one rank): the set that keeps direction rows + patches + trial-point workgroups
-        // resident at once -- the default set where it does, 512-element patches where only those do, none otherwise
-        h->specFits = false;
-        if (!h->dist && h->world == 1 && h->tune.specStep != 0) {
-            const int nbv = (nV + 255) / 256, room = 512 - NB_RED - nbv;
-            if (std::max(h->PT.nPatches, nbv) <= room) {
-                h->PTspec = h->PT;
-                h->specFits = true;
-            } else if (h->tune.patchElems == 0 && PE == 256) {
-                const HostPatches H2 = build_patches(nV, h->T.data(), h->Xrest.data(), all, 512);
-                if (std::max(H2.nPatches, nbv) <= room) {
-                    if (int rc = upload_patches(h, H2, h->PTspec)) return rc;
-                    h->specFits = true;
-                }
-            }
-        }
-    }
-    if (h->owner) {
-        // who holds / owns a vertex: a rank HOLDS the vertices of its subdomains (= of its elements); the lowest rank that
-        // holds a vertex OWNS it (its inertia term, its share of every dot product).  Vertices held by two or more ranks
-        // are the only ones whose entries travel inside the loop.
-        std::vector<int> holders(nV, 0), last(nV, -1), ownerR(nV, -1);
-        for (int r = 0; r < h->world; ++r)
-            for (int pI = h->firstPart[r]; pI < h->firstPart[r + 1]; ++pI)
-                for (int v : h->partVerts[pI])
-                    if (last[v] != r) {
-                        last[v] = r;
-                        holders[v]++;
-                        if (ownerR[v] < 0) ownerR[v] = r;
-                    }
-        std::vector<uint8_t> own(nV, 0), held(nV, 0);
-        std::vector<int> iface;
-        std::vector<double> mo(nV, 0.0);
-        for (int pI = h->p0; pI < h->p1; ++pI)
-            for (int v : h->partVerts[pI]) held[v] = 1;
-        for (int v = 0; v < nV; ++v) {
-            own[v] = ownerR[v] == h->rank || (ownerR[v] < 0 && h->rank == 0);
-            if (own[v]) mo[v] = h->mass[v];
-            if (holders[v] >= 2) iface.push_back(v);
-        }
-        h->nIface = (int)iface.size();
-        if (iface.empty()) iface.push_back(0);
-        std::vector<int> hl;
-        for (int v = 0; v < nV; ++v)
-            if (held[v]) hl.push_back(v);
-        h->nHeld = (int)hl.size();
-        if (hl.empty()) hl.push_back(0);
-        if (int rc = upload(h, &h->heldList, hl)) return rc;
-        if (int rc = upload(h, &h->ownMask, own)) return rc;
-        if (int rc = upload(h, &h->heldMask, held)) return rc;
-        {
-            std::vector<uint8_t> kind(nV);
-            for (int v = 0; v < nV; ++v) kind[v] = (uint8_t)((own[v] ? 1 : 0) | (holders[v] >= 2 ? 2 : 0));
-            if (int rc = upload(h, &h->vkind, kind)) return rc;
-            std::vector<int> sh;
-            for (int v = 0; v < nV; ++v)
-                if (held[v] && holders[v] >= 2) sh.push_back(v);
-            h->nShared = (int)sh.size();
-            if (sh.empty()) sh.push_back(0);
-            if (int rc = upload(h, &h->sharedList, sh)) return rc;
-        }
-        if (int rc = upload(h, &h->ifaceIdx, iface)) return rc;
-        if (int rc = upload(h, &h->massOwn, mo)) return rc;
-        if (int rc = dalloc(h, &h->xpack, (size_t)3 * h->nIface + 8 + RED_K)) return rc;
-        // the element pass' inertia term 1/2 m |x - x~|^2 by ownership too: the same kernel over every vertex with the
-        // owner's share of the mass (positions outside the held vertices stay where the warm start put them)
-        h->Mown = h->M;
-        h->Mown.mass = h->massOwn;
-        if (h->tune.fuseLog)
-            fprintf(stderr, "dotmi: owner exchange: rank %d holds %d of %d vertices, %d are held by more than one rank\n", h->rank,
-                    (int)std::count(held.begin(), held.end(), 1), nV, h->nIface);
-    }
-    return 0;
+    return build_element_side(h, adj_ptr, blk_ptr, blk_ent);
 }
 
 LbfgsArgs lbfgs_args(const dotmi_handle *h)
@@ -1623,7 +1636,17 @@ static int create_impl(dotmi_handle *h, const dotmi_mesh *mesh, const dotmi_para
     h->density = mesh->density;
     h->nPartsAll = mesh->nParts;
     h->T.assign(mesh->T, mesh->T + 4 * (size_t)h->nT);
-    if (mesh->vpart) {
+    h->pd = (h->flags & DOTMI_FLAG_LBFGS_PD) != 0;
+    if (h->pd) {
+        const int bad = DOTMI_FLAG_FORCE_DIST | DOTMI_FLAG_OWNER_EXCHANGE | DOTMI_FLAG_GSDD | DOTMI_FLAG_NEWTON | DOTMI_FLAG_ASYNC_REFRESH;
+        if (prm->world > 1 || (h->flags & bad) || mesh->vpart) {
+            h->err = "DOTMI_FLAG_LBFGS_PD: single GPU, host loop, not with DOTMI_FLAG_FORCE_DIST / OWNER_EXCHANGE / GSDD / NEWTON / "
+                     "ASYNC_REFRESH or a vertex partition";
+            return DOTMI_E_INVALID;
+        }
+        h->nPartsAll = 1;
+        h->epart.assign(h->nT, 0);   // (unused: no subdomains)
+    } else if (mesh->vpart) {
         if (prm->world > 1 || (prm->flags & DOTMI_FLAG_FORCE_DIST)) {
             h->err = "a vertex partition (vpart) is single-GPU only";
             return DOTMI_E_INVALID;
@@ -1734,7 +1757,7 @@ static int create_impl(dotmi_handle *h, const dotmi_mesh *mesh, const dotmi_para
             h->err = "DOTMI_FLAG_GSDD: single GPU only";
             return DOTMI_E_INVALID;
         }
-        h->devLoop = !h->gsdd && !h->newton && !(h->flags & (DOTMI_FLAG_HOST_LOOP | DOTMI_FLAG_TIME_PHASES));
+        h->devLoop = !h->gsdd && !h->newton && !h->pd && !(h->flags & (DOTMI_FLAG_HOST_LOOP | DOTMI_FLAG_TIME_PHASES));
         // replicated element pass, merged tile partials: the back-solve of the next direction is issued on the trial
         // gradient, beside the controller (enqueue_loop_slot); sharded subdomains keep their one collective per iteration
         // (round 4: also with the sharded element pass -- the scatter of -g and H s_new then happen in pair_stats, behind the
@@ -1794,6 +1817,8 @@ static int create_impl(dotmi_handle *h, const dotmi_mesh *mesh, const dotmi_para
     HIPCHECK(h, hipMemcpyAsync(h->xn, h->x, sizeof(double) * n, hipMemcpyDeviceToDevice, h->st));
     launch_be_update(h->nV, h->M.fixed, h->x, h->xn, h->v, h->xt, h->dt, h->gdtsq, h->st);
     HIPCHECK(h, hipStreamSynchronize(h->st));
+    // LBFGS-PD: the Laplacian's factor (LBFGSTimeStepper::precompute, :113-194); the Hessian is never assembled
+    if (h->pd) return pd_factor(h);
     // DOTTimeStepper::precompute (DOTTimeStepper.cpp:150-178)
     return refactor(h, h->x, nullptr, nullptr);
 }

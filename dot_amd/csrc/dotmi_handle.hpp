@@ -290,6 +290,8 @@ struct dotmi_handle {
     // device-resident loop control (single-GPU path)
     bool gsdd = false;   // DOTMI_FLAG_GSDD
     bool newton = false; // DOTMI_FLAG_NEWTON
+    bool pd = false;     // DOTMI_FLAG_LBFGS_PD: no subdomain block solve; the scalar factor of L below instead (dotmi_pd.hip)
+    DevPD PD;
     bool devLoop = false;
     DevLoop *ctl = nullptr, *h_ctl = nullptr;  // device / pinned staging
     int *h_flags = nullptr;                    // pinned: {status, slots done}, written by the controller
@@ -389,6 +391,11 @@ int refactor_finish(dotmi_handle *h, double *ms_hess, double *ms_fact);
 int refactor(dotmi_handle *h, const double *x, double *ms_hess, double *ms_fact);
 int resolve_refresh(dotmi_handle *h, double *ms_hess = nullptr, double *ms_fact = nullptr);
 int enter_with_factors(dotmi_handle *h);
+int run_factor(dotmi_handle *h);
+// dotmi_pd.hip (LBFGS-PD)
+int build_pd(dotmi_handle *h, const std::vector<int> &adj_ptr, const std::vector<int> &adj_idx);
+int pd_factor(dotmi_handle *h);
+int pd_apply(dotmi_handle *h, const double *q, double *z, const LbfgsArgs &L);
 // dotmi_collectives.hip
 int allreduce_sum(dotmi_handle *h, double *dev, size_t n);
 int adopt_rank0(dotmi_handle *h, double *vals, int n);

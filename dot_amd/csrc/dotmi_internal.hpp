@@ -171,6 +171,31 @@ struct DevParts {
     long long *pad_dst;
 };
 
+// ---- LBFGS-PD (DOTMI_FLAG_LBFGS_PD, dotmi_pd.hip / k_pd.hip): the scalar factor of the constant Laplacian -------------------------
+constexpr int PD_KC = 8;   // columns per thread of an apply work item: an item covers up to 256 x PD_KC columns of a 64-row block
+struct PdItem {
+    int blk;          // 64-row block of X
+    int cs, ce;       // its columns [cs, ce) this item reads
+    int nch, first;   // two-pass blocks: chunks of the block and the (long-item) index of its first one
+    long long pbase;  // offset of the item's partial z (3 per column) in DevPD::ppart
+};
+struct DevPD {
+    int nmax = 0;                  // padded scalar size (multiple of 64)
+    int *cvert = nullptr;          // nmax: padded position -> vertex, -1 = padding
+    double *W = nullptr;           // X = chol(L)^-1 (RowTile blocks; the work buffer is dotmi_handle::W2)
+    RowTile *rt = nullptr;         // nmax / 64 row blocks
+    double *Lval = nullptr;        // L on the vertex adjacency (DevMesh::adj_ptr / adj_idx)
+    int *inc_ptr = nullptr, *inc = nullptr;   // per vertex: incident (element << 2 | corner), ascending element
+    long long *fill_dst = nullptr;  // per CSR entry of L: its place in the work buffer, or -1
+    long long *pad_dst = nullptr;   // identity padding
+    int npad = 0;
+    PdItem *items = nullptr;        // nOne one-pass items, then nLong chunks of two-pass blocks
+    int nOne = 0, nLong = 0;
+    double *ppart = nullptr, *tdots = nullptr;
+    int *mptr = nullptr;            // per vertex: the partials of its column (CSR over ment, fixed order)
+    long long *ment = nullptr;
+};
+
 constexpr int MT_PAD = -2147483647 - 1;   // end of a dof's interleaved list (no offset, plain or complemented, has this value)
 
 struct LbfgsArgs {
@@ -472,6 +497,10 @@ void launch_tile_gemm(const TileTask *tasks, int ntasks, const TileProd *prods, 
 void launch_tile_flow(const TileTask *tasks, int ntasks, const TileProd *prods, const int *depPtr, const int *depIdx, int *done,
                       int *next, int epoch, int *info, int nwg, hipStream_t st, double waitMs, bool fastDiag = true);
 void launch_clear_tiles(double *const *tiles, const int *lds_, int ntiles, hipStream_t st);
+// k_pd.hip (LBFGS-PD): L on the device, its fill into the work buffer, z = L^-1 q per coordinate
+void launch_pd_assemble(const DevMesh &M, const DevPD &D, double dtSq, hipStream_t st);
+void launch_pd_fill(const DevPD &D, int nnz, double *W2, hipStream_t st);
+void launch_pd_apply(const DevPD &D, int nV, const double *q, double *z, hipStream_t st);
 // small helpers
 void launch_init_x(int nV, const uint8_t *fixed, const double *v, double dt, const double *gdtsq,
                    double *x, hipStream_t st);

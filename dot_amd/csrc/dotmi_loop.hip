@@ -799,23 +799,35 @@ int dotmi_step(dotmi_handle *h, dotmi_step_stats *st)
         }
         L = lbfgs_args(h);
         phase_mark(h, -1);
-        launch_build_qpad(h->P, h->g, L, xi, h->st);   // q, straight into the padded right-hand sides
-        phase_mark(h, DOTMI_T_MODIFY_GRAD);
-        // ---- subdomain back-solve, merge, second half ------------------------------------------------
-        if (int rc = apply_precond(h, nullptr, h->z, L)) return rc;
+        if (h->pd) {
+            // LBFGS-PD (LBFGSTimeStepper::solve_oneStep, :338-449): q interleaved, z = L^-1 q per coordinate (dotmi_pd.hip)
+            launch_build_q(n, h->g, L, xi, h->q, h->st);
+            phase_mark(h, DOTMI_T_MODIFY_GRAD);
+            if (int rc = pd_apply(h, h->q, h->z, L)) return rc;
+        } else {
+            launch_build_qpad(h->P, h->g, L, xi, h->st);   // q, straight into the padded right-hand sides
+            phase_mark(h, DOTMI_T_MODIFY_GRAD);
+            // ---- subdomain back-solve, merge, second half ------------------------------------------------
+            if (int rc = apply_precond(h, nullptr, h->z, L)) return rc;
+        }
         phase_mark(h, DOTMI_T_BACKSOLVE);
         launch_build_p(n, h->z, L, h->partC, xi, h->p, h->st);
         phase_mark(h, DOTMI_T_MODIFY_SEARCHDIR);
         // ---- alpha_0 and the first trial ---------------------------------------------------------------
-        launch_spmv_dots(h->M, h->Hval, h->p, h->g, nullptr, h->v0, h->v1, h->partS, h->st);
-        const double *spart = h->partS;
-        if (h->shardElems) {
-            hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(64), 0, h->st, h->partS, NB_RED, RED_K, 2, 0.0,
-                               0.0, 0, h->partG);
-            if (int rc = allreduce_sum(h, h->partG, 2)) return rc;
-            spart = h->partG;  // rows >= 1 stay zero
+        if (h->pd) {
+            // only TST_DOT estimates alpha_0 (Optimizer::initStepSize, Optimizer.cpp:1076-1093): the unit step, no H p
+            launch_step_forward(n, h->x, h->p, h->x_trial, nullptr, 1.0, 0, h->alphaMin, h->alpha_dev, h->h_alpha, h->st);
+        } else {
+            launch_spmv_dots(h->M, h->Hval, h->p, h->g, nullptr, h->v0, h->v1, h->partS, h->st);
+            const double *spart = h->partS;
+            if (h->shardElems) {
+                hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(64), 0, h->st, h->partS, NB_RED, RED_K, 2, 0.0,
+                                   0.0, 0, h->partG);
+                if (int rc = allreduce_sum(h, h->partG, 2)) return rc;
+                spart = h->partG;  // rows >= 1 stay zero
+            }
+            launch_step_forward(n, h->x, h->p, h->x_trial, spart, 0.0, 1, h->alphaMin, h->alpha_dev, h->h_alpha, h->st);
         }
-        launch_step_forward(n, h->x, h->p, h->x_trial, spart, 0.0, 1, h->alphaMin, h->alpha_dev, h->h_alpha, h->st);
         phase_mark(h, DOTMI_T_LINESEARCH_OTHER);
         const int slot = free_slot(h);
         double E = 0;
@@ -891,7 +903,9 @@ int dotmi_step(dotmi_handle *h, dotmi_step_stats *st)
     ms_fact += h->carryFact;
     h->carryHess = h->carryFact = 0.0;
 
-    const bool refreshAtEnd = !failed && !h->newton;   // Newton refreshes at the START of every iteration instead
+    // (Newton refreshes at the START of every iteration instead; LBFGS-PD's preconditioner is constant: LBFGSTimeStepper::fullyImplicit
+    // refactors only for H, HI and JH, :296-335)
+    const bool refreshAtEnd = !failed && !h->newton && !h->pd;
     if (failed) status = 2;
     else {
         if (it >= h->iterCap) status = 2;

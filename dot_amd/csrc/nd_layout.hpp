@@ -60,18 +60,19 @@ struct NdBuilder {
     std::vector<int> mark;  // nV, -1
     int maxDepth, minSplit;
     std::vector<std::vector<int>> rootS;  // per part: the root separator (set once the root is split)
+    int upv = 3;   // unknowns per vertex: 3 for the Hessian blocks, 1 for the scalar Laplacian of LBFGS-PD (dotmi_pd.hip)
 
     // flop model of the node's factorisation; every part is padded to the largest A, C of the batch, so an
     // unbalanced split costs as much as its bigger half twice
-    static long long cost(long long a, long long c, long long s)
+    static long long cost(long long a, long long c, long long s, int upv = 3)
     {
         // in padded scalar sizes (blocks of 64), raw sizes as the tie-break
         auto model = [](long long a_, long long c_, long long s_) {
             const long long m = std::max(a_, c_);
             return 2 * m * m * m + 8 * s_ * m * m + 8 * s_ * s_ * m + s_ * s_ * s_;
         };
-        auto r64 = [](long long v) { return (3 * v + 63) / 64 * 64; };
-        return model(r64(a), r64(c), r64(s)) + model(3 * a, 3 * c, 3 * s) / 64;
+        auto r64 = [upv](long long v) { return (upv * v + 63) / 64 * 64; };
+        return model(r64(a), r64(c), r64(s)) + model(upv * a, upv * c, upv * s) / 64;
     }
 
     // Smallest vertex separator that an ordered bisection (first t of `ord` | rest) admits: a minimum vertex
@@ -180,7 +181,7 @@ struct NdBuilder {
                 for (int i = 0; i < n; ++i) mark[ord[i]] = i < t ? 0 : 1;
                 int nl = 0, nr = 0;
                 min_cover(ord, t, cov, nl, nr);
-                const long long c = cost(t - nl, n - t - nr, nl + nr);
+                const long long c = cost(t - nl, n - t - nr, nl + nr, upv);
                 if (best < 0 || c < best) { best = c; bestAxis = axis; bestT = t; }
             }
         }
@@ -203,7 +204,7 @@ struct NdBuilder {
         region.emplace_back();
         const int np = (int)sets.size();
         int mx = 0;
-        for (auto &v : sets) mx = std::max(mx, 3 * (int)v.size());
+        for (auto &v : sets) mx = std::max(mx, upv * (int)v.size());
         auto make_leaf = [&]() {
             tree[id].size = std::max(64, (mx + 63) / 64 * 64);
             tree[id].tail = tree[id].tail1 = tree[id].size;
@@ -229,8 +230,8 @@ struct NdBuilder {
                     if (parentS)
                         for (int v : (*parentS)[p]) mark[v] = -1;
                     for (int v : rootS[p]) mark[v] = -1;
-                    mt = std::max(mt, 3 * (int)br.size());
-                    mt1 = std::max(mt1, 3 * (int)(br.size() + bp.size()));
+                    mt = std::max(mt, upv * (int)br.size());
+                    mt1 = std::max(mt1, upv * (int)(br.size() + bp.size()));
                     in.insert(in.end(), bp.begin(), bp.end());
                     in.insert(in.end(), br.begin(), br.end());
                     region[id][p] = in;
@@ -246,7 +247,7 @@ struct NdBuilder {
         for (int p = 0; p < np; ++p) {
             split(sets[p], As[p], Cs[p], Ss[p]);
             mc = std::max(mc, (int)Cs[p].size());
-            ms = std::max(ms, 3 * (int)Ss[p].size());
+            ms = std::max(ms, upv * (int)Ss[p].size());
         }
         if (mc == 0) return make_leaf();
         if (depth == 0) rootS = Ss;
@@ -350,14 +351,16 @@ constexpr int ND_MIN_SPLIT = 512;   // smallest region (scalars) that is still s
                                     // of the stiff monkey get their second level -- X 165 -> 124 MB, factor 0.78 -> 0.55 ms)
 
 // layout of the given vertex sets (one per owned subdomain): tree[0] is the root, region[node][part] the
-// vertices of the node's leaf block / separator in layout order; returns the padded size (lda, multiple of 64)
+// vertices of the node's leaf block / separator in layout order; returns the padded size (lda, multiple of 64).
+// upv: unknowns per vertex (region sizes in scalars = upv x vertices); 3 everywhere but the scalar layout of LBFGS-PD
 inline int nd_plan(const std::vector<std::vector<int>> &partVerts, int nV, const std::vector<int> &adj_ptr,
                    const std::vector<int> &adj_idx, const double *Xrest, int levels, int minSplit,
-                   std::vector<NdNode> &tree, std::vector<std::vector<std::vector<int>>> &region)
+                   std::vector<NdNode> &tree, std::vector<std::vector<std::vector<int>>> &region, int upv = 3)
 {
     tree.clear();
     region.clear();
     NdBuilder nb{tree, region, adj_ptr, adj_idx, Xrest, std::vector<int>(nV, -1), levels, minSplit};
+    nb.upv = upv;
     std::vector<std::vector<int>> sets(partVerts);
     const int root = nb.build(sets, 0);
     if (tree[root].size < 128) tree[root].size = 128;  // only a leaf root can be that small

@@ -46,6 +46,9 @@ struct Options {  // the Config fields the DOT stepper reads (src/Config.hpp)
     const void *commId = nullptr;
     double alphaMin = 0.1;  // lower clamp of alpha_0 (Optimizer.cpp:1085); 1.0 = unit first step (LBFGS-H, :1088)
     int flags = 0;  // DOTMI_FLAG_* (e.g. DOTMI_FLAG_TIME_PHASES to fill the reference's timer_step slots)
+    // `timeStepper LBFGS` (LBFGSTimeStepper with D0T_PD, main.cpp:918-919): L-BFGS on the constant projective-dynamics Laplacian
+    // (DOTMI_FLAG_LBFGS_PD).  No subdomains: partitionAmt / epart / vpart are not passed on; the first trial is the unit step
+    bool lbfgsPD = false;
 };
 
 class DotHipTimeStepper {
@@ -90,9 +93,9 @@ public:
         m.lambda = mesh_.lambda;
         m.density = mesh_.density;
         m.fixed = fixed_.data();
-        m.epart = opt_.epart;
-        m.nParts = opt_.partitionAmt;
-        m.vpart = opt_.vpart;
+        m.epart = opt_.lbfgsPD ? nullptr : opt_.epart;
+        m.nParts = opt_.lbfgsPD ? 1 : opt_.partitionAmt;
+        m.vpart = opt_.lbfgsPD ? nullptr : opt_.vpart;
         dotmi_params p{};
         p.energy = opt_.energyType;
         p.dt = dt_;
@@ -100,12 +103,12 @@ public:
         p.relTol = relTol_;
         p.history = 5;        // DOTTimeStepper.cpp:45
         p.iterCap = 10000;    // DOTTimeStepper.cpp:302
-        p.alphaMin = opt_.alphaMin;
+        p.alphaMin = opt_.lbfgsPD ? 1.0 : opt_.alphaMin;
         p.device = opt_.device;
         p.rank = opt_.rank;
         p.world = opt_.world;
         p.comm_id = opt_.commId;
-        p.flags = opt_.flags;
+        p.flags = opt_.flags | (opt_.lbfgsPD ? DOTMI_FLAG_LBFGS_PD : 0);
         if (int rc = dotmi_create(&m, &p, x0_.data(), &h_))
             throw std::runtime_error(std::string("dotmi_create: ") + dotmi_last_error(nullptr) + " (" +
                                      std::to_string(rc) + ")");

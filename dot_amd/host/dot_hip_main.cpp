@@ -10,7 +10,7 @@
 //   output/<name>/config.txt      echo of the effective script (Config::saveToFile, Config.cpp:209-302; main.cpp:786)
 //   output/<name>/info.txt        nV nT / steps innerIters / wall-clock summary (main.cpp:338-358)
 //   output/<name>/label.obj, wire.poly   partition labels of the surface triangles, surface wire frame
-//                                 (ADMMDDTimeStepper.cpp:375-442)
+//                                 (ADMMDDTimeStepper.cpp:375-442; not for `timeStepper LBFGS`, which has no partition)
 // Script token `restart <status file>` resumes from a saved status (Optimizer.cpp:126-177).
 //
 // usage: dot_hip 100 <script.txt> [--mesh-root DIR] [--parts N] [--energy FCR|SNH] [--epart raw.i32]
@@ -112,12 +112,16 @@ int main(int argc, char **argv)
         // path with the whole mesh as ONE subdomain (no averaging: dup = 1) and the alpha_0 clamp at 1
         const bool newton = cfg.timeStepper == "Newton";   // projected Newton: one subdomain, DOTMI_FLAG_NEWTON
         const bool lbfgsH = cfg.timeStepper == "LBFGSH" || newton;
+        // `timeStepper LBFGS` (LBFGSTimeStepper with D0T_PD): LBFGS-PD on the whole mesh -- no partition, and none of the partition
+        // files (label.obj / wire.poly are written by the ADMMDD constructor only)
+        const bool lbfgsPD = cfg.timeStepper == "LBFGS";
         int nParts = partsOverride > 0 ? partsOverride : cfg.partitionAmt;
-        if (lbfgsH) nParts = 1;
+        if (lbfgsH || lbfgsPD) nParts = 1;
         if (cfg.blockSize > 0 && partsOverride <= 0) nParts = mesh.nV() / cfg.blockSize + 1;  // main.cpp:792-798
-        if (nParts < 2 && !lbfgsH) nParts = 4;
+        if (lbfgsPD) nParts = 1;   // (block-size scripts included: the stepper has no subdomains)
+        if (nParts < 2 && !lbfgsH && !lbfgsPD) nParts = 4;
         std::vector<int32_t> epart;
-        if (lbfgsH) {
+        if (lbfgsH || lbfgsPD) {
             epart.assign(mesh.nT(), 0);
         } else if (!epartFile.empty()) {
             std::ifstream f(epartFile, std::ios::binary);
@@ -163,7 +167,7 @@ int main(int argc, char **argv)
             }
             if (outGiven) {
                 mkdir(outDir.c_str(), 0755);
-                write_partition_files(outDir, mesh, x0, epart);
+                if (!lbfgsPD) write_partition_files(outDir, mesh, x0, epart);
             }
             if (cfg.restart) {
                 int t = 0;
@@ -192,6 +196,7 @@ int main(int argc, char **argv)
         if (cfg.timeStepper == "GSDD") opt.flags |= DOTMI_FLAG_GSDD;
         if (lbfgsH) opt.alphaMin = 1.0;
         if (newton) opt.flags |= DOTMI_FLAG_NEWTON;
+        opt.lbfgsPD = lbfgsPD;
         // `timeStepper LBFGSJH <n>`: block-Jacobi on a vertex partition (the reference takes METIS::partMesh_nodes;
         // without METIS a vertex goes to the lowest-numbered subdomain among its elements) and a unit first step
         std::vector<int32_t> vpart;
@@ -210,7 +215,7 @@ int main(int argc, char **argv)
             fIter = std::fopen((outDir + "/iterStats.txt").c_str(), "w");
             fLog = std::fopen((outDir + "/log.txt").c_str(), "w");
             if (!fIter || !fLog) throw std::runtime_error("cannot write into " + outDir);
-            write_partition_files(outDir, mesh, x0, epart);
+            if (!lbfgsPD) write_partition_files(outDir, mesh, x0, epart);
             write_config_txt(outDir + "/config.txt", cfg);   // main.cpp:786
         }
         const SurfaceMesh surf = files ? build_surface_mesh(mesh) : SurfaceMesh();

@@ -40,11 +40,12 @@ class DOTTimeStepper:
         self._mu = np.full(self.nT, mu, dtype=np.float64)
         self._lam = np.full(self.nT, lam, dtype=np.float64)
         self._fixed = np.ascontiguousarray(scene.fixed, dtype=np.uint8)
-        self._epart = np.ascontiguousarray(epart, dtype=np.int32)
+        # (epart None: no element partition -- an LBFGS-PD handle, _lib.FLAG_LBFGS_PD, builds no subdomains)
+        self._epart = np.ascontiguousarray(epart, dtype=np.int32) if epart is not None else None
         self.nparts = int(nparts)
         self._vpart = np.ascontiguousarray(vpart, dtype=np.int32) if vpart is not None else None
         m = Mesh(self.nV, self.nT, dp(self._X), ip(self._T), dp(self._mu), dp(self._lam), cfg.rho,
-                 up(self._fixed), ip(self._epart), self.nparts, ip(self._vpart) if vpart is not None else None)
+                 up(self._fixed), ip(self._epart) if epart is not None else None, self.nparts, ip(self._vpart) if vpart is not None else None)
         p = Params()
         p.energy = cfg.energy_id if energy is None else energy
         p.dt = cfg.dt

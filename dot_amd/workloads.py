@@ -38,6 +38,11 @@ WORKLOADS = {
     "monkey18K_TSS_1K": ("monkey18K", dict(energy="FCR", size=1.0, duration=10.0, dt=0.025, rho=1000.0, YM=1e5,
                                            PR=0.4, script="twistnsns_old", rot_deg=40.0, rot_axis=(0.0, 1.0, 0.0),
                                            handle_ratio=0.02, block_size=1024), -1),
+    # input/otherMethods/monkey18K_TSS_LBFGSPD_E2.5e4.txt: `timeStepper LBFGS` (LBFGS-PD, DOTMI_FLAG_LBFGS_PD), the whole mesh, no
+    # partition (the nParts of 1 is what a caller passes with the flag)
+    "monkey18K_TSS_LBFGSPD": ("monkey18K", dict(energy="FCR", size=1.0, duration=10.0, dt=0.025, rho=1000.0, YM=2.5e4,
+                                                PR=0.4, script="twistnsns_old", rot_deg=40.0, rot_axis=(0.0, 1.0, 0.0),
+                                                handle_ratio=0.02), 1),
 }
 
 

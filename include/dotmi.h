@@ -143,6 +143,17 @@ enum {
                                       * packets (each vertex counted once over the ranks), alpha_0's p.Hp uses each rank's own
                                       * elements' part of H, and the positions are made whole again once per step.  Implies the
                                       * sharded element pass and refresh.  Same iterations as one GPU; tests/test_gpu_two_ranks.py */
+#define DOTMI_FLAG_LBFGS_PD 512     /* dotmi_step runs the reference's LBFGS-PD (`timeStepper LBFGS`, LBFGSTimeStepper with D0T_PD,
+                                     * LBFGSTimeStepper.cpp:113-194, :338-449): L-BFGS whose initial inverse Hessian is the constant
+                                     * projective-dynamics Laplacian L = M + sum_e dt^2 vol_e (2 mu_e + lambda_e) D_e^T D_e (fixed rows and
+                                     * columns replaced by the identity), applied to the x, y, z columns separately; the first trial of
+                                     * every line search is the unit step.  The handle builds NO subdomain block solve (epart, vpart and
+                                     * nParts are ignored: pass NULL / 1) but the scalar nV x nV factor of L, once per create and per
+                                     * dotmi_refix; a step refreshes nothing (ms_hessian = ms_factor = 0).  dotmi_apply_precond returns
+                                     * L^-1 r per coordinate.  Host-driven loop, single GPU: not with world > 1, FORCE_DIST,
+                                     * OWNER_EXCHANGE, GSDD, NEWTON, ASYNC_REFRESH or a vpart.  Entries of the Hessian block solve
+                                     * (dotmi_refactor, dotmi_part_matrix, dotmi_spmv, dotmi_probe_direction, the bench entries) return
+                                     * DOTMI_E_INVALID on such a handle. */
 
 typedef struct {
     int32_t iters;        /* L-BFGS iterations (innerIterAmt delta, DOTTimeStepper.cpp:338) */
@@ -341,6 +352,11 @@ int32_t dotmi_backsolve_form(const dotmi_handle *h);
 int dotmi_plan_backsolve_form(int32_t nV, int32_t nT, const int32_t *T, const double *Xrest, const int32_t *epart, int32_t nParts,
                               int32_t *form, int64_t *one_pass_bytes);
 int dotmi_part_matrix(dotmi_handle *h, int32_t part, int inverse, double *M, int32_t *l2g);
+/* (host only) the scalar layout a DOTMI_FLAG_LBFGS_PD handle factors L in (the nested dissection of the whole vertex graph, one unknown
+ * per vertex): its padded size and the bytes one application of L^-1 streams from the factor for all three coordinates -- 8 x the
+ * structural non-zeros of X, as dotmi_step_stats.precond_bytes counts them (64-row blocks whose rows are longer than 2048 columns take
+ * two passes, dots then scatter, and read their rows a second time, like the 3-dof back-solve beyond 5120 columns) */
+int dotmi_plan_pd(int32_t nV, int32_t nT, const int32_t *T, const double *Xrest, int32_t *padded, int64_t *apply_bytes);
 
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* Launch the subdomain back-solve kernel `reps` times on the handle's stream between two HIP events
