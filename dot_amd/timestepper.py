@@ -21,10 +21,13 @@ class DOTTimeStepper:
     def __init__(self, scene: Scene, epart: np.ndarray, nparts: int, energy: Optional[int] = None,
                  device: int = 0, rank: int = 0, world: int = 1, comm_id: Optional[bytes] = None,
                  history: int = 5, rel_tol: float = 1e-5, iter_cap: int = 10000, flags: int = 0, allreduce=None,
-                 alpha_min: float = 0.1, vpart: Optional[np.ndarray] = None):
+                 alpha_min: float = 0.1, vpart: Optional[np.ndarray] = None, mu: Optional[np.ndarray] = None,
+                 lam: Optional[np.ndarray] = None):
         """allreduce: optional callable(np.ndarray) that sums the array over the ranks IN PLACE (world > 1): the
         library then stages its collectives through host memory and calls it instead of RCCL
-        (dotmi_params::allreduce) -- e.g. a torch.distributed gloo all_reduce."""
+        (dotmi_params::allreduce) -- e.g. a torch.distributed gloo all_reduce.
+        mu, lam: optional per-element Lame parameters, shape (nT,) (dotmi_mesh::mu / ::lambda); either one left out is
+        the constant that the scene's YM and PR give."""
         L = _lib.load()
         cfg = scene.cfg
         self.scene = scene
@@ -33,12 +36,12 @@ class DOTTimeStepper:
         self.frameAmt = int(cfg.duration / cfg.dt)  # Optimizer::setTime, Optimizer.cpp:249-257
         self.globalIterNum = 0
         self.innerIterAmt = 0
-        mu, lam = lame(cfg.YM, cfg.PR)
+        mu0, lam0 = lame(cfg.YM, cfg.PR)
         # keep every array alive for the lifetime of the handle
         self._X = np.ascontiguousarray(scene.V_rest, dtype=np.float64)
         self._T = np.ascontiguousarray(scene.T, dtype=np.int32)
-        self._mu = np.full(self.nT, mu, dtype=np.float64)
-        self._lam = np.full(self.nT, lam, dtype=np.float64)
+        self._mu = self._per_element(mu, mu0, "mu")
+        self._lam = self._per_element(lam, lam0, "lam")
         self._fixed = np.ascontiguousarray(scene.fixed, dtype=np.uint8)
         # (epart None: no element partition -- an LBFGS-PD handle, _lib.FLAG_LBFGS_PD, builds no subdomains)
         self._epart = np.ascontiguousarray(epart, dtype=np.int32) if epart is not None else None
@@ -85,6 +88,14 @@ class DOTTimeStepper:
         self._h = h
         self._L = L
         self.last_stats: Optional[StepStats] = None
+
+    def _per_element(self, a, const, name):
+        if a is None:
+            return np.full(self.nT, const, dtype=np.float64)
+        a = np.array(a, dtype=np.float64)   # a private copy, kept alive with the handle
+        if a.shape != (self.nT,):
+            raise ValueError(f"{name} must have shape ({self.nT},), got {a.shape}")
+        return a
 
     # ---- lifetime -------------------------------------------------------------------------------
     def close(self):

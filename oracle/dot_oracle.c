@@ -1630,6 +1630,17 @@ void dor_set_fixed(dor_sim *s, const unsigned char *fixed)
     dor_refactor(s, s->x);
 }
 
+/* per-element Lame parameters (Mesh::u / Mesh::lambda, read per element by every energy term, Energy.cpp:411,730,764,990,
+ * 1014,1042): the tolerance takes element 0's, as Optimizer::computeCharNormSq does (Optimizer.cpp:622-623), and the
+ * factors are refreshed at the current x as dor_set_fixed does (an external solver, if bound, refactors through it) */
+void dor_set_lame(dor_sim *s, const double *mu, const double *lam)
+{
+    memcpy(s->mu, mu, sizeof(double) * s->nT);
+    memcpy(s->lam, lam, sizeof(double) * s->nT);
+    s->targetGRes = char_norm_sq(s, s->relTol * s->relTol);
+    dor_refactor(s, s->x);
+}
+
 int dor_use_ext_solver(dor_sim *s, const dor_ext_solver *api)
 {
     ext_release(s);

@@ -123,6 +123,9 @@ double dor_target_gres(const dor_sim *s);
 /* lower clamp of the initial step length: 0.1 = DOT (Optimizer.cpp:1085), 1.0 = unit step of the other steppers (:1088) */
 void dor_set_alpha_min(dor_sim *s, double a);
 void dor_set_fixed(dor_sim *s, const unsigned char *fixed);
+/* per-element Lame parameters mu[nT], lam[nT] in place of the constants of dor_create: targetGRes from element 0's,
+ * factors refreshed at the current x */
+void dor_set_lame(dor_sim *s, const double *mu, const double *lam);
 
 /* features / structure getters */
 void dor_get_features(const dor_sim *s, double *A /*nT*9*/, double *vol /*nT*/, double *mass /*nV*/,

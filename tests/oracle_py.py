@@ -77,6 +77,7 @@ def lib():
         L.dor_target_gres.restype = C.c_double
         L.dor_set_alpha_min.argtypes = [C.c_void_p, C.c_double]
         L.dor_set_fixed.argtypes = [C.c_void_p, c_up]
+        L.dor_set_lame.argtypes = [C.c_void_p, c_dp, c_dp]
         L.dor_get_features.argtypes = [C.c_void_p, c_dp, c_dp, c_dp, c_dp, c_dp]
         L.dor_get_dup.argtypes = [C.c_void_p, c_ip]
         L.dor_part_size.argtypes = [C.c_void_p, C.c_int]
@@ -111,7 +112,8 @@ class OracleSim:
     """Thin object wrapper over dor_sim."""
 
     def __init__(self, V_rest, T, YM, PR, rho, material, dt, fixed, x_init, epart, nparts,
-                 with_gravity=True, rel_tol=1e-5, vpart=None):
+                 with_gravity=True, rel_tol=1e-5, vpart=None, mu=None, lam=None):
+        """mu, lam: optional per-element Lame parameters (nT,) in place of the constants from YM, PR (dor_set_lame)"""
         L = lib()
         self.nV, self.nT = V_rest.shape[0], T.shape[0]
         self.nparts = int(nparts)
@@ -129,6 +131,9 @@ class OracleSim:
             self.h = L.dor_create(self.nV, self.nT, _dp(V_rest), _ip(T), YM, PR, rho, material, dt,
                                   int(with_gravity), fixed.ctypes.data_as(c_up), _dp(x_init),
                                   _ip(epart), self.nparts, rel_tol)
+        if mu is not None or lam is not None:
+            _, _, _, mu_c, lam_c = self.features()      # (either one left out keeps the constant from YM, PR)
+            self.set_lame(mu_c if mu is None else mu, lam_c if lam is None else lam)
 
     def close(self):
         if self.h:
@@ -226,6 +231,13 @@ class OracleSim:
     def set_fixed(self, fixed):
         fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
         lib().dor_set_fixed(self.h, fixed.ctypes.data_as(c_up))
+
+    def set_lame(self, mu, lam):
+        mu = np.ascontiguousarray(mu, dtype=np.float64)
+        lam = np.ascontiguousarray(lam, dtype=np.float64)
+        if mu.shape != (self.nT,) or lam.shape != (self.nT,):
+            raise ValueError(f"mu, lam must have shape ({self.nT},), got {mu.shape}, {lam.shape}")
+        lib().dor_set_lame(self.h, _dp(mu), _dp(lam))
 
     @property
     def target_gres(self):

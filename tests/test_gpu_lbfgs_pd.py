@@ -15,11 +15,15 @@ from tests import oracle_py as O
 pytestmark = pytest.mark.gpu
 
 
-def dense_L(ts, sc, fixed):
-    """L from the handle's own features (restTriInv A, volumes, lumped mass) and the formula above, in numpy"""
+def dense_L(ts, sc, fixed, mu=None, lam=None):
+    """L from the handle's own features (restTriInv A, volumes, lumped mass) and the formula above, in numpy; mu / lam: optional
+    per-element Lame parameters (nT,), else the scene's one material"""
     A, vol, mass = ts.features()
     A = A.reshape(-1, 3, 3)
-    mu, lam = lame(sc.cfg.YM, sc.cfg.PR)
+    mu0, lam0 = lame(sc.cfg.YM, sc.cfg.PR)
+    nT = sc.T.shape[0]
+    mu = np.full(nT, mu0) if mu is None else np.asarray(mu, dtype=np.float64)
+    lam = np.full(nT, lam0) if lam is None else np.asarray(lam, dtype=np.float64)
     nV = sc.V_rest.shape[0]
     L = np.diag(mass.astype(np.float64))
     Le = np.zeros((nV, nV))
@@ -27,7 +31,7 @@ def dense_L(ts, sc, fixed):
         D = np.zeros((3, 4))
         D[:, 1:] = A[e].T
         D[:, 0] = -A[e].sum(axis=0)
-        Le[np.ix_(t, t)] += sc.cfg.dt ** 2 * vol[e] * (2 * mu + lam) * (D.T @ D)
+        Le[np.ix_(t, t)] += sc.cfg.dt ** 2 * vol[e] * (2 * mu[e] + lam[e]) * (D.T @ D)
     L = L + Le
     f = np.asarray(fixed, dtype=bool)
     L[f, :] = 0.0
@@ -36,8 +40,8 @@ def dense_L(ts, sc, fixed):
     return L
 
 
-def make_pd(sc, energy=None, flags=0):
-    return DOTTimeStepper(sc, None, 1, energy=energy, alpha_min=1.0, flags=dl.FLAG_LBFGS_PD | flags)
+def make_pd(sc, energy=None, flags=0, mu=None, lam=None):
+    return DOTTimeStepper(sc, None, 1, energy=energy, alpha_min=1.0, flags=dl.FLAG_LBFGS_PD | flags, mu=mu, lam=lam)
 
 
 def check_apply(ts, L, seed=0):
@@ -87,10 +91,11 @@ class DenseSolver:
         assert L.dor_use_ext_solver(orc.h, C.byref(self.api)) == 0
 
 
-def oracle_for(sc, energy_id):
+def oracle_for(sc, energy_id, mu=None, lam=None):
     ep = np.zeros(sc.T.shape[0], dtype=np.int32)
     cfg = sc.cfg
-    orc = O.OracleSim(sc.V_rest, sc.T, cfg.YM, cfg.PR, cfg.rho, energy_id, cfg.dt, sc.fixed, sc.x0, ep, 1, cfg.with_gravity)
+    orc = O.OracleSim(sc.V_rest, sc.T, cfg.YM, cfg.PR, cfg.rho, energy_id, cfg.dt, sc.fixed, sc.x0, ep, 1, cfg.with_gravity,
+                      mu=mu, lam=lam)
     orc.set_alpha_min(1.0)
     return orc
 
@@ -113,6 +118,29 @@ def test_steps_match_the_oracle_with_the_laplacian(name, energy, nsteps):
         assert st.status == 0 and st.g2 <= ts.targetGRes
         # no refresh inside or at the end of a PD step
         assert st.ms_hessian == 0.0 and st.ms_factor == 0.0, k
+        assert np.abs(ts.getResult() - orc.state()[0]).max() < 1e-9, k
+    ts.close()
+    orc.close()
+
+
+def test_per_element_materials_weight_the_laplacian():
+    """L's element weights dt^2 vol_e (2 mu_e + lambda_e) with a random Lame field per element (tests/materials.py): the apply
+    is the dense solve of that L, and 2 steps take the oracle's iterations with a dense L^-1 of the same field"""
+    from tests.materials import field
+    sc, _, _ = load_workload("bunny5K_LTSS")
+    mu, lam = field(sc, "random")
+    ts = make_pd(sc, mu=mu, lam=lam)
+    L = dense_L(ts, sc, sc.fixed, mu, lam)
+    check_apply(ts, L)
+    # (and the field matters: the one-material L is another matrix)
+    assert np.abs(L - dense_L(ts, sc, sc.fixed)).max() > 1e-3 * np.abs(L).max()
+    sol = DenseSolver(L)
+    orc = oracle_for(sc, sc.cfg.energy_id, mu, lam)
+    sol.bind(orc)
+    for k in range(2):
+        st, so = _scripted_step(sc, ts, orc)
+        assert (st.status, st.iters, st.ls_halvings) == (so.status, so.iters, so.ls_halvings), k
+        assert st.status == 0 and st.g2 <= ts.targetGRes
         assert np.abs(ts.getResult() - orc.state()[0]).max() < 1e-9, k
     ts.close()
     orc.close()

@@ -38,15 +38,20 @@ def bunny(request):
     ts.close(); orc.close()
 
 
-def snh_gradient_extended(sc, ts, x):
-    """Gradient of the incremental potential for Stable Neo-Hookean in numpy longdouble (64-bit mantissa), closed form:
-    per tet F = Ds A, P = dt^2 vol (mu F + lam (det F - 1 - mu/lam) cof F), nodal forces P A^T; plus m_v (x_v - x~_v)."""
+def _snh_extended_terms(sc, ts, x, mu, lam):
+    """per tet F, cof F, det F, A, dt^2 vol, mu, lam in longdouble; mu / lam: per-element arrays (nT,), or None for the scene's
+    one material"""
     LD = np.longdouble
     cfg = sc.cfg
     A, vol, mass = ts.features()
-    mu = LD(cfg.YM) / (2 * (1 + LD(cfg.PR)))
-    lam = LD(cfg.YM) * LD(cfg.PR) / ((1 + LD(cfg.PR)) * (1 - 2 * LD(cfg.PR)))
-    xt = ts.getState()[2].astype(LD)
+    if mu is None:
+        mu = LD(cfg.YM) / (2 * (1 + LD(cfg.PR)))
+    else:
+        mu = np.asarray(mu, dtype=np.float64).astype(LD)
+    if lam is None:
+        lam = LD(cfg.YM) * LD(cfg.PR) / ((1 + LD(cfg.PR)) * (1 - 2 * LD(cfg.PR)))
+    else:
+        lam = np.asarray(lam, dtype=np.float64).astype(LD)
     X = x.astype(LD)
     T = sc.T
     Ds = np.stack([X[T[:, 1]] - X[T[:, 0]], X[T[:, 2]] - X[T[:, 0]], X[T[:, 3]] - X[T[:, 0]]], axis=2)   # [e, r, k]
@@ -59,13 +64,33 @@ def snh_gradient_extended(sc, ts, x):
             cof[:, r, c] = F[:, r1, c1] * F[:, r2, c2] - F[:, r1, c2] * F[:, r2, c1]
     J = (F[:, 0, :] * cof[:, 0, :]).sum(axis=1)
     w = LD(cfg.dt) ** 2 * vol.astype(LD)
-    P = w[:, None, None] * (mu * F + (lam * (J - (1 + mu / lam)))[:, None, None] * cof)
+    return X, F, cof, J, Ai, w, mu, lam, mass.astype(LD), ts.getState()[2].astype(LD)
+
+
+def snh_energy_extended(sc, ts, x, mu=None, lam=None):
+    """Incremental potential for Stable Neo-Hookean in longdouble, closed form: per tet
+    dt^2 vol (mu (|F|^2 - 3) + lam (det F - 1 - mu/lam)^2) / 2, plus m_v |x_v - x~_v|^2 / 2 over every vertex."""
+    X, F, cof, J, Ai, w, mu, lam, mass, xt = _snh_extended_terms(sc, ts, x, mu, lam)
+    JmA = J - (1 + mu / lam)
+    psi = (mu * ((F * F).sum(axis=(1, 2)) - 3) + lam * JmA * JmA) / 2
+    return float((w * psi).sum() + (mass[:, None] * (X - xt) ** 2).sum() / 2)
+
+
+def snh_gradient_extended(sc, ts, x, mu=None, lam=None):
+    """Gradient of the incremental potential for Stable Neo-Hookean in numpy longdouble (64-bit mantissa), closed form:
+    per tet F = Ds A, P = dt^2 vol (mu F + lam (det F - 1 - mu/lam) cof F), nodal forces P A^T; plus m_v (x_v - x~_v).
+    mu / lam: optional per-element Lame parameters (nT,), else the scene's one material."""
+    X, F, cof, J, Ai, w, mu, lam, mass, xt = _snh_extended_terms(sc, ts, x, mu, lam)
+    T = sc.T
+    coef = lam * (J - (1 + mu / lam))
+    mu_b = mu[:, None, None] if np.ndim(mu) else mu
+    P = w[:, None, None] * (mu_b * F + coef[:, None, None] * cof)
     gk = np.einsum("ecj,eaj->eac", P, Ai)            # node a+1, component c
     g = np.zeros_like(X)
     for a in range(3):
         np.add.at(g, T[:, a + 1], gk[:, a, :])
     np.add.at(g, T[:, 0], -gk.sum(axis=1))
-    g += mass.astype(LD)[:, None] * (X - xt)
+    g += mass[:, None] * (X - xt)
     g[sc.fixed.astype(bool)] = 0
     return g.astype(np.float64)
 

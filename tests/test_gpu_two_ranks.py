@@ -15,7 +15,8 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _worker(rank, world, initfile, outdir, workload, shard_elems, steps):
+def _worker(rank, world, initfile, outdir, workload, shard_elems, steps, material=None):
+    """material: optional (kind, seed) of a per-element Lame field of tests/materials.py, rebuilt here from its name"""
     sys.path.insert(0, ROOT)
     owner = shard_elems.startswith("owner")   # DOTMI_FLAG_OWNER_EXCHANGE: interface-only exchange, owner-summed dot products
     if owner:
@@ -38,8 +39,12 @@ def _worker(rank, world, initfile, outdir, workload, shard_elems, steps):
 
     from dot_amd import lib as dl
     sc, ep, n = load_workload(workload)
+    mu = lam = None
+    if material is not None:
+        from tests.materials import field
+        mu, lam = field(sc, *material)
     ts = DOTTimeStepper(sc, ep, n, device=0, rank=rank, world=world, allreduce=allreduce,
-                        flags=dl.FLAG_OWNER_EXCHANGE if owner else 0)
+                        flags=dl.FLAG_OWNER_EXCHANGE if owner else 0, mu=mu, lam=lam)
     calls[0] = nbytes[0] = 0          # (the collectives of dotmi_create are not the loop's)
     its, halv, Es = [], [], []
     for _ in range(steps):
@@ -76,6 +81,17 @@ CASES = [("bunny5K_LTSS", 4, "0", 2), ("bunny5K_LTSS", 4, "1", 2), ("horse7K_str
 
 @pytest.mark.parametrize("workload,steps,shard_elems,world", CASES)
 def test_ranks_on_one_gpu_reproduce_the_single_gpu_run(workload, steps, shard_elems, world):
+    _ranks_reproduce_the_single_gpu_run(workload, steps, shard_elems, world)
+
+
+def test_ranks_with_per_element_materials_reproduce_the_single_gpu_run():
+    """A random Lame field per element (tests/materials.py) with the sharded element pass and refresh: each rank's refresh
+    evaluates only the elements its vertices need (hessElems, a strict subset of the mesh on two ranks), so the element Hessian
+    kernel must read the material of element elist[i], not of element i."""
+    _ranks_reproduce_the_single_gpu_run("bunny5K_LTSS", 4, "1", 2, material=("random", 0))
+
+
+def _ranks_reproduce_the_single_gpu_run(workload, steps, shard_elems, world, material=None):
     import torch.multiprocessing as mp
     from tests.workloads import load_workload
     from dot_amd.timestepper import DOTTimeStepper
@@ -83,7 +99,7 @@ def test_ranks_on_one_gpu_reproduce_the_single_gpu_run(workload, steps, shard_el
     ctx = mp.get_context("spawn")
     with tempfile.TemporaryDirectory() as d:
         initfile = os.path.join(d, "init")
-        procs = [ctx.Process(target=_worker, args=(r, world, initfile, d, workload, shard_elems, steps))
+        procs = [ctx.Process(target=_worker, args=(r, world, initfile, d, workload, shard_elems, steps, material))
                  for r in range(world)]
         for p in procs:
             p.start()
@@ -113,7 +129,11 @@ def test_ranks_on_one_gpu_reproduce_the_single_gpu_run(workload, steps, shard_el
         assert per_it < 0.75 * 2 * 8 * n3, (per_it, 2 * 8 * n3)
     # and it is the single-GPU run up to the summation order of the exchanged vectors
     sc, ep, n = load_workload(workload)
-    ts = DOTTimeStepper(sc, ep, n)
+    mu = lam = None
+    if material is not None:
+        from tests.materials import field
+        mu, lam = field(sc, *material)
+    ts = DOTTimeStepper(sc, ep, n, mu=mu, lam=lam)
     its, halv = [], []
     for _ in range(steps):
         x = ts.getResult()
