@@ -98,7 +98,63 @@ DM_HD void sym_eig3(const Mat3 &Ain, double (&w)[3], Mat3 &Q)
     }
 }
 
+// One Hestenes (one-sided Jacobi) rotation: makes the columns bp, bq of B = F V orthogonal and applies the same rotation to
+// the columns P, Q of V, so that B = F V keeps holding.  Skipped (false) when they are orthogonal to 1e-15 |bp| |bq| already.
+template <int P, int Q>
+DM_HD bool column_rot(double (&bp)[3], double (&bq)[3], Mat3 &V)
+{
+    const double a = bp[0] * bp[0] + bp[1] * bp[1] + bp[2] * bp[2];
+    const double b = bq[0] * bq[0] + bq[1] * bq[1] + bq[2] * bq[2];
+    const double g = bp[0] * bq[0] + bp[1] * bq[1] + bp[2] * bq[2];
+    if (g * g <= 1e-30 * (a * b)) return false;
+    const double zeta = (b - a) / (2.0 * g);
+    const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(zeta * zeta + 1.0));
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double x = bp[i], y = bq[i];
+        bp[i] = c * x - s * y;
+        bq[i] = s * x + c * y;
+        const double vx = V.m[i][P], vy = V.m[i][Q];
+        V.m[i][P] = c * vx - s * vy;
+        V.m[i][Q] = s * vx + c * vy;
+    }
+    return true;
+}
+
+// (bp, bq) -> (bq, -bp) when |bp| < |bq|, the same on the columns P, Q of V: a quarter turn, det V stays +1
+template <int P, int Q>
+DM_HD void column_order(double (&bp)[3], double (&bq)[3], Mat3 &V)
+{
+    const double a = bp[0] * bp[0] + bp[1] * bp[1] + bp[2] * bp[2];
+    const double b = bq[0] * bq[0] + bq[1] * bq[1] + bq[2] * bq[2];
+    if (a >= b) return;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double x = bp[i], vx = V.m[i][P];
+        bp[i] = bq[i]; bq[i] = -x;
+        V.m[i][P] = V.m[i][Q]; V.m[i][Q] = -vx;
+    }
+}
+
+DM_HD bool columns_skew(const double (&bp)[3], const double (&bq)[3])
+{
+    const double a = bp[0] * bp[0] + bp[1] * bp[1] + bp[2] * bp[2];
+    const double b = bq[0] * bq[0] + bq[1] * bq[1] + bq[2] * bq[2];
+    const double g = bp[0] * bq[0] + bp[1] * bq[1] + bp[2] * bq[2];
+    return g * g > 1e-26 * (a * b);
+}
+
 // F = U diag(S) V^T, U,V in SO(3), S0 >= S1 >= |S2|, sign(S2) = sign(det F)
+//
+// V comes from the eigenvectors of F^T F, U from Gram-Schmidt on the columns of B = F V (the structure of the reference's
+// SVD).  The squared matrix resolves a singular value only down to sqrt(eps) sigma_0: with TWO of them small against the
+// largest (an element squashed towards a line) the eigenvectors of the small pair, and with them R = U V^T, come out with
+// an error of eps (sigma_0 / sigma_1)^2 where the polar factor is conditioned like eps sigma_0 / (sigma_1 + sigma_2).  The
+// columns of B show it: they are orthogonal exactly when V holds right singular vectors.  Where a pair is off by more
+// than 1e-13 |b_i| |b_j| -- never on a well-conditioned element, whose columns are orthogonal to a few eps, so those take
+// the path they always took, bit for bit -- one-sided Jacobi sweeps on B and V (which work on F itself, not on its square)
+// finish the job, and the columns are put back in descending order.
 DM_HD void svd3(const Mat3 &F, Mat3 &U, double (&S)[3], Mat3 &V)
 {
     Mat3 C;
@@ -127,6 +183,18 @@ DM_HD void svd3(const Mat3 &F, Mat3 &U, double (&S)[3], Mat3 &V)
         b1[i] = F.m[i][0] * V.m[0][1] + F.m[i][1] * V.m[1][1] + F.m[i][2] * V.m[2][1];
         b2[i] = F.m[i][0] * V.m[0][2] + F.m[i][1] * V.m[1][2] + F.m[i][2] * V.m[2][2];
     }
+    if (columns_skew(b0, b1) || columns_skew(b0, b2) || columns_skew(b1, b2)) {
+#pragma unroll 1
+        for (int sweep = 0; sweep < 6; ++sweep) {
+            bool turned = column_rot<0, 1>(b0, b1, V);
+            turned |= column_rot<0, 2>(b0, b2, V);
+            turned |= column_rot<1, 2>(b1, b2, V);
+            if (!turned) break;
+        }
+        column_order<0, 1>(b0, b1, V);
+        column_order<1, 2>(b1, b2, V);
+        column_order<0, 1>(b0, b1, V);
+    }
     double u0[3], u1[3], u2[3];
     double n0 = sqrt(b0[0] * b0[0] + b0[1] * b0[1] + b0[2] * b0[2]);
     if (n0 > 0) {
@@ -137,10 +205,14 @@ DM_HD void svd3(const Mat3 &F, Mat3 &U, double (&S)[3], Mat3 &V)
     double d01 = u0[0] * b1[0] + u0[1] * b1[1] + u0[2] * b1[2];
     double r1[3] = {b1[0] - d01 * u0[0], b1[1] - d01 * u0[1], b1[2] - d01 * u0[2]};
     double n1 = sqrt(r1[0] * r1[0] + r1[1] * r1[1] + r1[2] * r1[2]);
-    if (n1 > 1e-14 * n0 && n1 > 0) {
+    // b1 is orthogonal to b0 to 1e-13 |b0| |b1| here, so r1 keeps (nearly) all of b1 and normalising it is stable however
+    // small sigma_1 is; the second test admits it below the old threshold (S[1] = |r1| then, not a projection on an
+    // arbitrary vector)
+    const double nb1sq = b1[0] * b1[0] + b1[1] * b1[1] + b1[2] * b1[2];
+    if ((n1 > 1e-14 * n0 || 4.0 * (n1 * n1) > nb1sq) && n1 > 0) {
         u1[0] = r1[0] / n1; u1[1] = r1[1] / n1; u1[2] = r1[2] / n1;
     } else {
-        // rank <= 1: unit vector orthogonal to u0 built from the smallest-|component| axis
+        // b1 = 0: unit vector orthogonal to u0 built from the smallest-|component| axis
         double ax = fabs(u0[0]), ay = fabs(u0[1]), az = fabs(u0[2]);
         double e0 = 0, e1 = 0, e2 = 0, d;
         if (ax <= ay && ax <= az) { e0 = 1; d = u0[0]; }

@@ -95,6 +95,26 @@ def snh_gradient_extended(sc, ts, x, mu=None, lam=None):
     return g.astype(np.float64)
 
 
+def fcr_gradient_60_digits(sc, ts, x, mu=None, lam=None):
+    """Gradient of the incremental potential for Fixed-Corotational at 60 digits (tests/elem_reference.py), rounded to double, and
+    the mask of the tets with two singular values small against the largest (sigma_1 <= 1e-2 sigma_0).
+
+    Why the Fixed-Corotational comparison at amp = 0.05 goes through it: device and oracle used to share one SVD structure
+    (eigen-analysis of F^T F), whose polar factor is off by eps (sigma_0 / sigma_1)^2 on such tets, and agreed with each other
+    to 1e-12 in that error.  The bunny at amp = 0.05 has one (tet 13734, sigma = (1974, 2.46, -0.196), a sliver stretched
+    2000-fold): the oracle's gradient is off by 2.9e-12 of max|g| there against the 60-digit value.  svd3 now refines such tets
+    (elem_math.hpp), the oracle keeps its rounding (its fixtures depend on it), so each side is held to the exact value, with the
+    bounds of the Stable Neo-Hookean branch above: device 1e-12, oracle 1e-11, the device the more accurate."""
+    from tests import elem_reference as R
+    cfg = sc.cfg
+    m0, l0 = scene.lame(cfg.YM, cfg.PR)
+    nT = len(sc.T)
+    mu = np.full(nT, m0) if mu is None else np.asarray(mu, dtype=np.float64)
+    lam = np.full(nT, l0) if lam is None else np.asarray(lam, dtype=np.float64)
+    gx, sigma = R.fcr_mesh_gradient(sc.V_rest, sc.T, x, ts.getState()[2], mu, lam, cfg.rho, cfg.dt, sc.fixed)
+    return gx, sigma[:, 1] <= 1e-2 * sigma[:, 0]
+
+
 def test_native_library_is_loaded():
     L = dl.load()
     with open("/proc/self/maps") as f:
@@ -120,6 +140,7 @@ def test_energy_gradient_hessian_match_oracle(bunny, amp):
     E, Eo = ts.computeEnergyVal(x), orc.energy(x)
     assert abs(E - Eo) <= 1e-12 * abs(Eo)
     g, go = ts.computeGradient(x), orc.gradient(x)
+    thin = None
     if sc.cfg.energy == "SNH":
         # The device evaluates Stable Neo-Hookean energy and stress in closed form (Psi depends on |F|^2 and det F only:
         # P = mu F + lam (J - a) cof F), the oracle -- like the reference -- through the SVD of F.  Same function; on
@@ -129,11 +150,18 @@ def test_energy_gradient_hessian_match_oracle(bunny, amp):
         gx = snh_gradient_extended(sc, ts, x)
         assert rel(g, gx) < 1e-12 and rel(go, gx) < 1e-11 and rel(g, gx) < rel(go, gx) + 1e-15
         assert rel(g, go) < 1e-11
+    elif amp == 0.05:
+        gx, thin = fcr_gradient_60_digits(sc, ts, x)
+        print(f"FCR amp 0.05 against 60 digits: device {rel(g, gx):.3g} oracle {rel(go, gx):.3g}; {thin.sum()} tets with sigma_1 <= 1e-2 sigma_0")
+        assert rel(g, gx) < 1e-12 and rel(go, gx) < 1e-11 and rel(g, gx) < rel(go, gx) + 1e-15
+        assert rel(g, go) < 1e-11
     else:
         assert rel(g, go) < 1e-12
     assert np.abs(g[sc.fixed.astype(bool)]).max() == 0.0
     H, Ho = ts.computeElemHessians(x), orc.elem_hessians(x)
     per_elem = np.abs(H - Ho).reshape(len(H), -1).max(axis=1) / np.abs(Ho).reshape(len(H), -1).max(axis=1)
+    if thin is not None:
+        print(f"per-tet Hessian against the oracle on those tets: {per_elem[thin]}, elsewhere {per_elem[~thin].max():.3g}")
     assert per_elem.max() < 1e-10, per_elem.max()
     assert np.abs(H - H.transpose(0, 2, 1)).max() <= 1e-12 * np.abs(H).max()
 
