@@ -1,6 +1,6 @@
-// dotmi_create.hip -- dotmi_create and what it builds: mesh features, tolerance, partition maps, dissection layout, back-solve tiles, factor storage, tile schedule, patches; the host-only planning entry points; dotmi_destroy
+// dotmi_create.hip -- dotmi_create and what it builds: mesh features, tolerance, the device side of every planning stage of block_plan.hpp (uploads and buffers), patches, loop state; the host-only planning entry points; dotmi_destroy
 #include "dotmi_handle.hpp"
-#include "bs_tiles.hpp"
+#include "block_plan.hpp"
 
 namespace dotmi {
 std::string g_create_error;
@@ -186,32 +186,6 @@ int upload_patches(dotmi_handle *h, const HostPatches &H, DevPatches &D)
     return 0;
 }
 
-// structural non-zeros of the one-pass form (explicit inverse) on a planned layout: every row of a region from the region's first
-// column to its diagonal, live columns only -- x 8 = the bytes one application streams (dotmi_step_stats.precond_bytes)
-static long long one_pass_nnz(const std::vector<NdNode> &nd, const std::vector<std::vector<std::vector<int>>> &reg, int nParts)
-{
-    long long nnz = 0;
-    const int nmax0 = nd[0].size;
-    std::vector<int> usedBefore(nmax0 + 1);
-    for (int ls = 0; ls < nParts; ++ls) {
-        std::vector<uint8_t> live(nmax0, 0);
-        for (size_t k = 0; k < nd.size(); ++k) {
-            const int used = 3 * (int)reg[k][ls].size(), ro = nd_region_first_row(nd[k], used);
-            std::fill(live.begin() + ro, live.begin() + ro + used, 1);
-        }
-        usedBefore[0] = 0;
-        for (int c = 0; c < nmax0; ++c) usedBefore[c + 1] = usedBefore[c] + live[c];
-        for (size_t k = 0; k < nd.size(); ++k) {
-            const NdNode &N = nd[k];
-            const int used = 3 * (int)reg[k][ls].size(), ro = nd_region_first_row(N, used);
-            const int cb = N.a < 0 ? (ro & ~15) : N.off;
-            for (int r = ro; r < ro + used; ++r) nnz += usedBefore[r + 1] - usedBefore[cb];
-        }
-    }
-    return nnz;
-}
-constexpr long long TWO_LEVEL_FROM_BYTES = 240000000ll;   // one-pass bytes per application from which the two-level form is the default
-
 // what the element pass, the refresh's sharding and the owner exchange need beside the subdomains (the tail of build_device_mesh;
 // an LBFGS-PD handle, which has no subdomains, builds this part only)
 static int build_element_side(dotmi_handle *h, const std::vector<int> &adj_ptr, const std::vector<int> &blk_ptr,
@@ -368,7 +342,8 @@ static int build_element_side(dotmi_handle *h, const std::vector<int> &adj_ptr, 
     return 0;
 }
 
-int build_device_mesh(dotmi_handle *h)
+// element arrays, block-CSR adjacency incl. self and the per-block contribution lists -> device
+static int build_mesh_graph(dotmi_handle *h, MeshGraph &G, std::vector<int> &blk_ptr, std::vector<int> &blk_ent)
 {
     const int nV = h->nV, nT = h->nT;
     DevMesh &M = h->M;
@@ -391,8 +366,8 @@ int build_device_mesh(dotmi_handle *h)
         if (int rc = upload(h, &M.fixed, h->fixed)) return rc;
     }
     // adjacency incl. self
-    std::vector<int> adj_ptr, adj_idx;
-    build_adjacency(nV, nT, h->T.data(), adj_ptr, adj_idx);
+    G = mesh_graph(nV, nT, h->T.data(), h->Xrest.data());
+    const std::vector<int> &adj_ptr = G.adj_ptr, &adj_idx = G.adj_idx;
     M.nnzb = adj_ptr[nV];
     std::vector<int> blk_row(M.nnzb);
     for (int v = 0; v < nV; ++v)
@@ -402,7 +377,9 @@ int build_device_mesh(dotmi_handle *h)
         return (int)(std::lower_bound(b, e, u) - adj_idx.data());
     };
     // per-block contributions, ascending element
-    std::vector<int> blk_ptr(M.nnzb + 1, 0), blk_ent((size_t)16 * nT), eblk((size_t)16 * nT);
+    std::vector<int> eblk((size_t)16 * nT);
+    blk_ptr.assign(M.nnzb + 1, 0);
+    blk_ent.resize((size_t)16 * nT);
     for (int e = 0; e < nT; ++e)
         for (int a = 0; a < 4; ++a)
             for (int b = 0; b < 4; ++b) {
@@ -421,161 +398,59 @@ int build_device_mesh(dotmi_handle *h)
     if (int rc = upload(h, &M.blk_ptr, blk_ptr)) return rc;
     if (int rc = upload(h, &M.blk_ent, blk_ent)) return rc;
     if (int rc = upload(h, &M.blk_row, blk_row)) return rc;
-    if (h->pd) {   // LBFGS-PD: the scalar factor of the constant Laplacian instead of the subdomain block solve (dotmi_pd.hip)
-        if (int rc = build_pd(h, adj_ptr, adj_idx)) return rc;
-        return build_element_side(h, adj_ptr, blk_ptr, blk_ent);
-    }
+    return 0;
+}
 
-    // ---- subdomains (ADMMDDTimeStepper.cpp:88-262) ------------------------------------------------
+// subdomains (ADMMDDTimeStepper.cpp:88-262): the vertex sets of all parts, how many hold a vertex, the parts this rank owns
+static void choose_subdomains(dotmi_handle *h)
+{
     const int nP = h->nPartsAll;
-    h->partVerts.assign(nP, {});
-    {
-        std::vector<int> mark(nV, -1);
-        if (!h->vpart.empty()) {   // vertex partition given: disjoint vertex sets (block-Jacobi, LBFGS-JH)
-            for (int v = 0; v < nV; ++v) h->partVerts[h->vpart[v]].push_back(v);
-        } else
-        for (int pI = 0; pI < nP; ++pI) {
-            for (int e = 0; e < nT; ++e)
-                if (h->epart[e] == pI)
-                    for (int k = 0; k < 4; ++k) {
-                        const int v = h->T[4 * e + k];
-                        if (mark[v] != pI) {
-                            mark[v] = pI;
-                            h->partVerts[pI].push_back(v);
-                        }
-                    }
-            std::sort(h->partVerts[pI].begin(), h->partVerts[pI].end());
-        }
+    if (!h->vpart.empty()) {   // vertex partition given: disjoint vertex sets (block-Jacobi, LBFGS-JH)
+        h->partVerts.assign(nP, {});
+        for (int v = 0; v < h->nV; ++v) h->partVerts[h->vpart[v]].push_back(v);
+    } else {
+        h->partVerts = part_vertex_sets(h->nT, h->T.data(), h->epart.data(), nP);
     }
-    h->dup.assign(nV, 0);
-    int nsmax = 0;
+    h->dup.assign(h->nV, 0);
+    // ownership: contiguous groups of parts balanced by sum n_s^2 (the back-solve cost)
+    std::vector<int32_t> ps(nP);
     for (int pI = 0; pI < nP; ++pI) {
         for (int v : h->partVerts[pI]) h->dup[v]++;
-        nsmax = std::max(nsmax, 3 * (int)h->partVerts[pI].size());
+        ps[pI] = 3 * (int32_t)h->partVerts[pI].size();
     }
-    // ownership: contiguous groups of parts balanced by sum n_s^2 (the back-solve cost)
-    {
-        std::vector<int32_t> ps(nP), first(h->world + 1);
-        for (int pI = 0; pI < nP; ++pI) ps[pI] = 3 * (int32_t)h->partVerts[pI].size();
-        dotmi_plan_shards(nP, ps.data(), h->world, first.data());
-        h->p0 = first[h->rank];
-        h->p1 = first[h->rank + 1];
-        h->firstPart = first;
+    h->firstPart.assign(h->world + 1, 0);
+    dotmi_plan_shards(nP, ps.data(), h->world, h->firstPart.data());
+    h->p0 = h->firstPart[h->rank];
+    h->p1 = h->firstPart[h->rank + 1];
+}
+
+// the factors are the one allocation that grows with the square of the subdomain size: refuse what cannot fit
+// instead of failing somewhere inside hipMalloc
+static int check_factors_fit(dotmi_handle *h, const FactorStorage &F)
+{
+    size_t freeB = 0, totalB = 0;
+    HIPCHECK(h, hipMemGetInfo(&freeB, &totalB));
+    const double need = 8.0 * (double)F.wOnePass * 2.1;   // + the work buffer of the factorisation
+    if (need > 0.9 * (double)freeB) {
+        h->err = "the subdomain factors need " + std::to_string((long long)(need / 1e9)) + " GB (" + std::to_string(h->P.nParts) +
+                 " subdomains, padded size " + std::to_string(h->P.nmax) + "), more than the free HBM: use more subdomains";
+        return DOTMI_E_INVALID;
     }
+    if (8.0 * (double)F.wTotal * 2.1 > 0.9 * (double)freeB) {
+        h->err = "the two-level factors do not fit the free HBM";
+        return DOTMI_E_INVALID;
+    }
+    return 0;
+}
+
+// the padded layout and the job table of the back-solve launches (bs_tiles.hpp) -> device
+static int upload_backsolve_tables(dotmi_handle *h, const std::vector<int> &dofmap, const BsTilePlan &TP)
+{
     DevParts &P = h->P;
-    P.nParts = h->p1 - h->p0;
-    // ---- nested-dissection layout of the owned subdomains ---------------------------------------
-    int ndLevels = h->tune.ndLevels;
-    int ndMin = h->tune.ndMin;
-    std::vector<std::vector<std::vector<int>>> region;  // [node][owned part] -> vertices of the leaf / separator
-    {
-        std::vector<std::vector<int>> sets(P.nParts);
-        for (int ls = 0; ls < P.nParts; ++ls) sets[ls] = h->partVerts[h->p0 + ls];
-        // two-level form of the back-solve (DevTwoLevel): the block solve as a whole (not GSDD's subdomain at
-        // a time); per subdomain, so sharded subdomains take it as well.  By default where the one-pass form would stream at least 240 MB per application on its own
-        // layout: the three launches around the tile kernels and the split merge cost 25-40 us per iteration, the form saves bytes
-        // and a third of the factorisation -- measured (profiles/r06_two_level.txt H): bar17K (197 MB) +21 % per step, monkey
-        // (124 MB) +42 %, horse7K / 8 (107 MB) +8 %; kingkong18K / 18 (245 MB) -10 %, horse7K@r1:64 (681 MB) -12 %, 1 M tets
-        // (3.8 GB) -16 %.  The form wants a tree of at least four levels with regions split down to ~200 scalars (the horse at
-        // three levels / 384: +4 % instead of -12 %).
-        const bool eligible = !(h->flags & DOTMI_FLAG_GSDD);
-        const bool userDepth = ndLevels >= 0 || getenv("DOTMI_ND_MIN") != nullptr;
-        bool wantTwoLevel = eligible && h->tune.twoLevel > 0;
-        int lvUsed = 0, mnUsed = 0;
-        auto plan = [&](bool twoLevelDepth) {
-            int lv = ndLevels, mn = ndMin;
-            if (twoLevelDepth && !userDepth) {
-                // sixteen leaves per subdomain where its size allows: four levels, regions split down to a fifteenth of the biggest
-                // subdomain (between 128 and 256 scalars) -- 1 M tets / 256 (3.2 k dofs): 213, the same tree as with 256; 4.2 M tets /
-                // 1024 (2.9 k dofs): 192, 16 leaves instead of 8: 13.8 -> 9.8 GB per application, the step -7 %; 192 k tets / 64:
-                // 433 -> 325 MB, -7.5 % (profiles/r06_two_level.txt J)
-                lv = std::max(4, nd_default_levels(h->partVerts));
-                int nsmax = 0;
-                for (auto &v : h->partVerts) nsmax = std::max(nsmax, 3 * (int)v.size());
-                mn = std::min(256, std::max(128, nsmax / 15));
-            } else if (lv < 0 && !getenv("DOTMI_ND_MIN")) {
-                // depth and split threshold from ALL subdomains of the mesh: the same tree on every rank (nd_layout.hpp)
-                nd_choose_depth(h->partVerts, nV, adj_ptr, adj_idx, h->Xrest.data(), BS_NARROW, mn, lv, mn);
-            } else if (lv < 0) {
-                lv = nd_default_levels(h->partVerts);
-            }
-            if (h->tune.fuseLog) fprintf(stderr, "dotmi: dissection: %d levels, regions split down to %d scalars\n", lv, mn);
-            lvUsed = lv;
-            mnUsed = mn;
-            nd_plan(sets, nV, adj_ptr, adj_idx, h->Xrest.data(), lv, mn, h->nd, region);
-        };
-        plan(wantTwoLevel);
-        if (!wantTwoLevel && eligible && h->tune.twoLevel < 0 && !h->nd.empty() && h->nd[0].a >= 0) {
-            // counted over ALL subdomains of the mesh, so that every rank of a sharded run -- and the single-GPU run it is
-            // compared with -- takes the same form (a rank's own factors are private, but the forms differ in rounding)
-            long long nnz = 0;
-            if (P.nParts == (int)h->partVerts.size()) {
-                nnz = one_pass_nnz(h->nd, region, P.nParts);
-            } else {
-                std::vector<NdNode> treeAll;
-                std::vector<std::vector<std::vector<int>>> regionAll;
-                nd_plan(h->partVerts, nV, adj_ptr, adj_idx, h->Xrest.data(), lvUsed, mnUsed, treeAll, regionAll);
-                if (!treeAll.empty()) nnz = one_pass_nnz(treeAll, regionAll, (int)h->partVerts.size());
-            }
-            if (8 * nnz >= TWO_LEVEL_FROM_BYTES) {
-                wantTwoLevel = true;
-                if (!userDepth) plan(true);
-            }
-        }
-        h->twoLevel = wantTwoLevel && !h->nd.empty() && h->nd[0].a >= 0;   // (a tree that has separators at all)
-        if (h->twoLevel) nd_relayout_leaves_first(h->nd);
-    }
-    P.nmax = h->nd[0].size;
-    h->tileMode = P.nParts > 0;   // (a rank without subdomains plans nothing)
-    // per part: padded position of every local vertex, tiles of the back-solve, structural non-zeros
-    h->partPos.assign(P.nParts, {});
-    std::vector<int> dofmap((size_t)P.nParts * P.nmax, -1);
-    // the job table of the back-solve launches (bs_tiles.hpp): tiles per region, wide / narrow / packs, heavy first
-    BsTilePlan TP;
-    plan_backsolve_tiles(h->nd, [&](int k, int ls) { return 3 * (int)region[k][ls].size(); }, P.nParts, P.nmax,
-                         BsTileRules{h->tune.tileRows, h->tune.tileRowsLong, h->tune.tilePasses, h->tune.wavePacks}, TP);
-    std::vector<int4> &tiles = TP.tiles;
-    std::vector<std::vector<int2>> &ranges = TP.ranges;
-    h->precond_bytes = 0;
-    int64_t nnzX = 0;
-    for (int ls = 0; ls < P.nParts; ++ls) {
-        const auto &pv = h->partVerts[h->p0 + ls];
-        std::unordered_map<int, int> posOf;
-        posOf.reserve(pv.size() * 2);
-        std::vector<int> usedBefore(P.nmax + 1, 0);  // number of live columns before a padded position
-        std::vector<uint8_t> live(P.nmax, 0);
-        for (size_t nd = 0; nd < h->nd.size(); ++nd) {
-            const NdNode &N = h->nd[nd];
-            const auto &rv = region[nd][ls];
-            const int ro = nd_region_first_row(N, 3 * (int)rv.size());
-            for (size_t k = 0; k < rv.size(); ++k) {
-                posOf[rv[k]] = ro + 3 * (int)k;
-                for (int d = 0; d < 3; ++d) {
-                    dofmap[(size_t)ls * P.nmax + ro + 3 * k + d] = 3 * rv[k] + d;
-                    live[ro + 3 * k + d] = 1;
-                }
-            }
-        }
-        for (int c = 0; c < P.nmax; ++c) usedBefore[c + 1] = usedBefore[c] + live[c];
-        h->partPos[ls].resize(pv.size());
-        for (size_t i = 0; i < pv.size(); ++i) h->partPos[ls][i] = posOf.at(pv[i]);
-        // structural non-zeros: every row of a region from the region's first column to the diagonal, live columns only
-        for (size_t nd = 0; nd < h->nd.size(); ++nd) {
-            const NdNode &N = h->nd[nd];
-            const int used = 3 * (int)region[nd][ls].size();
-            const int ro = nd_region_first_row(N, used);
-            const int cb = N.a < 0 ? (ro & ~15) : N.off;
-            for (int r = ro; r < ro + used; ++r) nnzX += usedBefore[r + 1] - usedBefore[cb];
-        }
-    }
-    // every structural non-zero of the inverse factors is streamed once per back-solve
-    h->precond_bytes = nnzX * 8;
     P.nbmax = 1;
-    for (auto &r : ranges) P.nbmax = std::max(P.nbmax, (int)r.size());
+    for (auto &r : TP.ranges) P.nbmax = std::max(P.nbmax, (int)r.size());
     std::vector<int2> trange((size_t)std::max(P.nParts, 1) * P.nbmax, make_int2(0, 0));
-    for (int ls = 0; ls < P.nParts; ++ls) std::copy(ranges[ls].begin(), ranges[ls].end(), trange.begin() + (size_t)ls * P.nbmax);
-    std::vector<int4> &tilesByPart = TP.tilesByPart, &ltilesByPart = TP.ltilesByPart, &ltiles = TP.ltiles;
-    std::vector<int2> &lworkByPart = TP.lworkByPart, &lwork = TP.lwork;
+    for (int ls = 0; ls < P.nParts; ++ls) std::copy(TP.ranges[ls].begin(), TP.ranges[ls].end(), trange.begin() + (size_t)ls * P.nbmax);
     h->partTilePtr = TP.partTilePtr;
     h->partLworkPtr = TP.partLworkPtr;
     P.maxTileLen = TP.maxTileLen;
@@ -583,480 +458,228 @@ int build_device_mesh(dotmi_handle *h)
     P.ntiles = TP.ntiles;
     P.ntilesWide = TP.ntilesWide;
     P.nquad = TP.nquad;
-    if (h->tune.fuseLog)
-        fprintf(stderr, "dotmi: back-solve: %d one-tile jobs (%d wide), %d packs of four small tiles%s\n", P.ntiles, P.ntilesWide,
-                P.nquad, TP.shallow ? ", shallow launch: long rows in 4-pass tiles" : "");
-    P.nltiles = (int)ltiles.size();
-    P.nlwork = (int)lwork.size();
-    // merge lists (owned parts only)
-    std::vector<int> vp_ptr(nV + 1, 0), vp_off;
-    {
-        for (int ls = 0; ls < P.nParts; ++ls)
-            for (int v : h->partVerts[h->p0 + ls]) vp_ptr[v + 1]++;
-        for (int v = 0; v < nV; ++v) vp_ptr[v + 1] += vp_ptr[v];
-        vp_off.resize(vp_ptr[nV]);
-        std::vector<int> cur(vp_ptr.begin(), vp_ptr.end() - 1);
-        for (int ls = 0; ls < P.nParts; ++ls) {
-            const auto &pv = h->partVerts[h->p0 + ls];
-            for (int i = 0; i < (int)pv.size(); ++i) vp_off[cur[pv[i]]++] = ls * P.nmax + h->partPos[ls][i];
-        }
-    }
-    // ---- factor storage: 64-row blocks (RowTile) ---------------------------------------------------------------
-    const int ntl = P.nmax / 64;
-    std::vector<RowTile> rtab((size_t)std::max(P.nParts, 1) * ntl, RowTile{-1, 0, 0});
-    std::vector<long long> rtOff(rtab.size(), -1);
-    std::vector<int> rtLd(rtab.size(), 0), rtC0(rtab.size(), 0);
-    size_t wTotal = 0;
-    {
-        // first column a row of the layout can have non-zero: that of its tree node
-        std::vector<int> nodeC0(P.nmax, 0);
-        for (const NdNode &N : h->nd) {
-            if (N.a < 0)
-                for (int r = N.off; r < N.off + N.size; ++r) nodeC0[r] = N.off;
-            else
-                for (int r = N.offS; r < N.offS + N.sizeS; ++r) nodeC0[r] = N.off;
-        }
-        for (int ls = 0; ls < P.nParts; ++ls)
-            for (int J = 0; J < ntl; ++J) {
-                RowTile &R = rtab[(size_t)ls * ntl + J];
-                {
-                    bool live = false;
-                    for (int r = 64 * J; r < 64 * J + 64 && !live; ++r) live = dofmap[(size_t)ls * P.nmax + r] >= 0;
-                    if (!live) continue;   // identity padding only: nothing stored, nothing read
-                    const int c0 = nodeC0[64 * J];
-                    R = RowTile{(long long)wTotal, 64 * (J + 1) - c0, c0};
-                    wTotal += (size_t)64 * R.ld;
-                }
-                rtOff[(size_t)ls * ntl + J] = R.off;
-                rtLd[(size_t)ls * ntl + J] = R.ld;
-                rtC0[(size_t)ls * ntl + J] = R.c0;
-            }
-        // the factors are the one allocation that grows with the square of the subdomain size: refuse what cannot fit
-        // instead of failing somewhere inside hipMalloc
-        size_t freeB = 0, totalB = 0;
-        HIPCHECK(h, hipMemGetInfo(&freeB, &totalB));
-        const double need = 8.0 * (double)wTotal * 2.1;   // + the work buffer of the factorisation
-        if (need > 0.9 * (double)freeB) {
-            h->err = "the subdomain factors need " + std::to_string((long long)(need / 1e9)) + " GB (" + std::to_string(P.nParts) +
-                     " subdomains, padded size " + std::to_string(P.nmax) + "), more than the free HBM: use more subdomains";
-            return DOTMI_E_INVALID;
-        }
-    }
-    // two-level form: a separator's row blocks store the LEAF columns of their sub-tree in a second range (their main range starts
-    // at the sub-tree's first separator column)
-    std::vector<long long> rtOffM(rtab.size(), -1);
-    std::vector<int> rtLdM(rtab.size(), 0), rtC0M(rtab.size(), 0);
-    std::vector<uint8_t> leafTile(ntl, 0);
-    if (h->twoLevel) {
-        std::vector<int> nodeOfRow(P.nmax, -1);
-        for (size_t k = 0; k < h->nd.size(); ++k) {
-            const NdNode &N = h->nd[k];
-            if (N.a < 0)
-                for (int r = N.off; r < N.off + N.size; ++r) leafTile[r / 64] = 1;
-            else
-                for (int r = N.offS; r < N.offS + N.sizeS; ++r) nodeOfRow[r] = (int)k;
-        }
-        for (int ls = 0; ls < P.nParts; ++ls)
-            for (int J = 0; J < ntl; ++J) {
-                const size_t at = (size_t)ls * ntl + J;
-                if (rtab[at].off < 0 || nodeOfRow[64 * J] < 0) continue;
-                const NdNode &N = h->nd[nodeOfRow[64 * J]];
-                rtOffM[at] = (long long)wTotal;
-                // (+ 16: a leaf range is a multiple of 64 columns, often a power of two -- consecutive rows of a panel would then
-                // start on the same HBM channels)
-                rtLdM[at] = N.endL - N.offL + 16;
-                rtC0M[at] = N.offL;
-                wTotal += (size_t)64 * rtLdM[at];
-            }
-        size_t freeB = 0, totalB = 0;
-        HIPCHECK(h, hipMemGetInfo(&freeB, &totalB));
-        if (8.0 * (double)wTotal * 2.1 > 0.9 * (double)freeB) {
-            h->err = "the two-level factors do not fit the free HBM";
-            return DOTMI_E_INVALID;
-        }
-    }
-    h->rtOff = rtOff;
-    h->rtLd = rtLd;
-    h->rtC0 = rtC0;
-    h->rtOffM = rtOffM;
-    h->rtLdM = rtLdM;
-    h->rtC0M = rtC0M;
-    h->wTotal = wTotal;
-    // offset in W of (memory row r, column c) of owned subdomain ls, or -1 when that place is not stored
-    auto waddr = [&](int ls, int r, int c) -> long long {
-        const size_t at = (size_t)ls * ntl + (r >> 6);
-        const RowTile &R = rtab[at];
-        if (R.off < 0) return -1;
-        if (c < R.c0) {
-            if (rtOffM[at] < 0 || c < rtC0M[at] || c >= rtC0M[at] + rtLdM[at]) return -1;
-            return rtOffM[at] + (long long)(r & 63) * rtLdM[at] + (c - rtC0M[at]);
-        }
-        if (c >= R.c0 + R.ld) return -1;
-        return R.off + (long long)(r & 63) * R.ld + (c - R.c0);
-    };
-    // dense fill list: per scalar of every 3x3 block of the principal sub-matrix
-    std::vector<long long> fill_dst, pad_dst;
-    std::vector<int> fill_src;
-    std::vector<int4> fillBlk;   // (owned subdomain, memory row, memory column) of the blocks' corners, for the tile pattern
-    {
-        std::vector<int> g2p(nV, -1);
-        for (int ls = 0; ls < P.nParts; ++ls) {
-            const auto &pv = h->partVerts[h->p0 + ls];
-            for (int i = 0; i < (int)pv.size(); ++i) g2p[pv[i]] = h->partPos[ls][i];
-            for (int i = 0; i < (int)pv.size(); ++i) {
-                const int v = pv[i];
-                for (int k = adj_ptr[v]; k < adj_ptr[v + 1]; ++k) {
-                    const int j = g2p[adj_idx[k]];
-                    if (j < 0) continue;
-                    const int r0 = h->partPos[ls][i];
-                    for (int rc = 0; rc < 9; ++rc) fill_dst.push_back(waddr(ls, r0 + rc / 3, j + rc % 3));
-                    fill_src.push_back(k);
-                    fillBlk.push_back(make_int4(ls, r0, j, 0));
-                }
-            }
-            for (int r = 0; r < P.nmax; ++r)
-                if (dofmap[(size_t)ls * P.nmax + r] < 0) {
-                    const long long a = waddr(ls, r, r);
-                    if (a >= 0) pad_dst.push_back(a);
-                }
-            for (int v : pv) g2p[v] = -1;
-        }
-    }
-    P.nfill = (int)fill_src.size();
-    P.npad = (int)pad_dst.size();
+    P.nltiles = (int)TP.ltiles.size();
+    P.nlwork = (int)TP.lwork.size();
     if (int rc = upload(h, &P.dofmap, dofmap)) return rc;
-    if (int rc = upload(h, &P.tile, tiles)) return rc;
-    if (int rc = upload(h, &P.tileByPart, tilesByPart)) return rc;
-    if (int rc = upload(h, &P.ltileByPart, ltilesByPart)) return rc;
-    if (int rc = upload(h, &P.lworkByPart, lworkByPart)) return rc;
-    if (int rc = upload(h, &P.ltile, ltiles)) return rc;
-    if (int rc = upload(h, &P.lwork, lwork)) return rc;
+    if (int rc = upload(h, &P.tile, TP.tiles)) return rc;
+    if (int rc = upload(h, &P.tileByPart, TP.tilesByPart)) return rc;
+    if (int rc = upload(h, &P.ltileByPart, TP.ltilesByPart)) return rc;
+    if (int rc = upload(h, &P.lworkByPart, TP.lworkByPart)) return rc;
+    if (int rc = upload(h, &P.ltile, TP.ltiles)) return rc;
+    if (int rc = upload(h, &P.lwork, TP.lwork)) return rc;
     if (int rc = dalloc(h, &P.tdots, (size_t)std::max(P.nltiles, 1) * P.maxChunks * 64)) return rc;
     HIPCHECK(h, hipMemset(P.tdots, 0, sizeof(double) * (size_t)std::max(P.nltiles, 1) * P.maxChunks * 64));
-    if (int rc = upload(h, &P.trange, trange)) return rc;
-    {
-        // reduce_partial_p: the tiles of a part that hold a group of 16 columns, ascending (a tile's range starts on a multiple of 16)
-        const int ng = P.nmax / 16;
-        std::vector<int> rptr((size_t)std::max(P.nParts, 1) * (ng + 1) , 0), ridx;
-        for (int ls = 0; ls < P.nParts; ++ls) {
-            std::vector<std::vector<int>> lists(ng);
-            for (size_t b = 0; b < ranges[ls].size(); ++b)
-                for (int g = ranges[ls][b].x / 16; g <= (ranges[ls][b].y - 1) / 16 && g < ng; ++g)
-                    lists[g].push_back((int)b | (std::min(16, ranges[ls][b].y - 16 * g) << 24));   // tile | columns of the group it holds
-            for (int g = 0; g < ng; ++g) {
-                rptr[(size_t)ls * (ng + 1) + g] = (int)ridx.size();
-                ridx.insert(ridx.end(), lists[g].begin(), lists[g].end());
-            }
-            rptr[(size_t)ls * (ng + 1) + ng] = (int)ridx.size();
-        }
-        if (ridx.empty()) ridx.push_back(0);
-        if (int rc = upload(h, &P.rp_ptr, rptr)) return rc;
-        if (int rc = upload(h, &P.rp_idx, ridx)) return rc;
-    }
-    if (int rc = upload(h, &P.vp_ptr, vp_ptr)) return rc;
-    if (int rc = upload(h, &P.vp_off, vp_off)) return rc;
-    {
-        // merge straight from the tile partials (merge_tiles_kernel): per global scalar dof the ppart entries that make
-        // up its value -- subdomain after subdomain (vp order), inside a subdomain the tiles that hold the column in
-        // tile order; the first entry of a subdomain is stored complemented.  Same sums, same order as
-        // reduce_partial_p + merge.
-        P.mt_ptr = nullptr;
-        P.mt_ent = nullptr;
-        P.mt_wave = nullptr;
-        P.mt_il = nullptr;
-        const long long ppartN = (long long)P.nParts * P.nbmax * P.nmax;
-        // Big meshes: the walk over a dof's ~20 tile partials is a walk over scattered 8-byte words and 4-byte list entries
-        // (1 M tets: 75 us per iteration at 0.26 of the HBM peak); the two-launch form reads the partials coalesced in the
-        // subdomains' own order and gathers one 24-byte triple per (vertex, subdomain).  Small meshes keep the one launch.
-        P.splitMerge = h->tune.splitMerge >= 0 ? (h->tune.splitMerge != 0) : (3ll * nV >= 400000 || ppartN >= (1ll << 31));
-        if (h->twoLevel) P.splitMerge = 1;   // (the leaves' results are finished on the per-subdomain sums psub)
-        const bool lists = !P.splitMerge && ppartN < (1ll << 31) && !(h->flags & DOTMI_FLAG_GSDD);
-        if (!(h->flags & DOTMI_FLAG_GSDD)) {
-            std::vector<int> mp(lists ? (size_t)3 * nV + 1 : 0, 0), ment;
-            long long count = 0;
-            for (int v = 0; v < nV; ++v)
-                for (int d = 0; d < 3; ++d) {
-                    for (int k = vp_ptr[v]; k < vp_ptr[v + 1]; ++k) {
-                        const int ls = vp_off[k] / P.nmax, col = vp_off[k] % P.nmax + d;
-                        bool first = true;
-                        for (size_t b = 0; b < ranges[ls].size(); ++b)
-                            if (col >= ranges[ls][b].x && col < ranges[ls][b].y) {
-                                ++count;
-                                if (lists) {
-                                    const int off = (int)(((long long)ls * P.nbmax + (long long)b) * P.nmax + col);
-                                    ment.push_back(first ? ~off : off);
-                                }
-                                first = false;
-                            }
-                    }
-                    if (lists) mp[(size_t)3 * v + d + 1] = (int)ment.size();
-                }
-            // Few subdomains with long rows in short tiles (bunny5K: 8-16 rows per tile): a column is covered by dozens of tiles,
-            // ~30 scattered partials per dof against ~10 on bar17K -- there too the coalesced within-subdomain sum first is the
-            // shorter way (bunny5K 1.395 -> 1.367 ms per step; the stiff monkey, 8 per dof, loses 3 % with it)
-            const bool longLists = h->tune.splitMerge < 0 && count >= 24ll * 3 * nV;
-            if (lists && longLists) {
-                P.splitMerge = 1;
-            } else if (lists) {
-                if (int rc = upload(h, &P.mt_ptr, mp)) return rc;
-                if (int rc = upload(h, &P.mt_ent, ment)) return rc;
-                // the lists once more, interleaved by wavefront (DevParts::mt_il): what the merge kernels walk when they visit
-                // every dof (the owner exchange's vertex lists keep the CSR walk)
-                const int n3 = 3 * nV, nw = (n3 + 63) / 64;
-                std::vector<int2> mw(nw);
-                std::vector<int> il;
-                for (int w = 0; w < nw; ++w) {
-                    int L = 0;
-                    for (int l = 0; l < 64 && 64 * w + l < n3; ++l) L = std::max(L, mp[64 * w + l + 1] - mp[64 * w + l]);
-                    mw[w] = make_int2((int)il.size(), L);
-                    il.resize(il.size() + (size_t)64 * L, MT_PAD);
-                    for (int l = 0; l < 64 && 64 * w + l < n3; ++l)
-                        for (int q = 0, e = mp[64 * w + l]; e < mp[64 * w + l + 1]; ++q, ++e) il[(size_t)mw[w].x + 64 * q + l] = ment[e];
-                }
-                if (il.empty()) il.push_back(MT_PAD);
-                if (il.size() < (size_t)1 << 31) {
-                    if (int rc = upload(h, &P.mt_wave, mw)) return rc;
-                    if (int rc = upload(h, &P.mt_il, il)) return rc;
-                }
-            }
-            if (h->tune.fuseLog) {
-                int lmax = 0;
-                long long over24 = 0;
-                for (size_t k = 0; k + 1 < mp.size(); ++k) {
-                    lmax = std::max(lmax, mp[k + 1] - mp[k]);
-                    over24 += mp[k + 1] - mp[k] > 24;
-                }
-                fprintf(stderr, "dotmi: merge: %.1f tile partials per dof (longest list %d, %lld lists beyond 24) -> %s\n",
-                        (double)count / std::max(1, 3 * nV), lmax, over24,
-                        P.splitMerge ? "sum per subdomain, then gather (split)" : "one walk over the list");
-            }
-            h->mergeEntries = count;   // tile partials one merge reads (either form)
-        } else {
-            P.splitMerge = 0;
+    return upload(h, &P.trange, trange);
+}
+
+static int upload_merge_lists(dotmi_handle *h, const MergeLists &M)
+{
+    DevParts &P = h->P;
+    if (int rc = upload(h, &P.vp_ptr, M.vp_ptr)) return rc;
+    if (int rc = upload(h, &P.vp_off, M.vp_off)) return rc;
+    P.mt_ptr = nullptr;
+    P.mt_ent = nullptr;
+    P.mt_wave = nullptr;
+    P.mt_il = nullptr;
+    P.splitMerge = M.splitMerge;
+    if (h->flags & DOTMI_FLAG_GSDD) return 0;
+    if (M.walk) {
+        if (int rc = upload(h, &P.mt_ptr, M.mp)) return rc;
+        if (int rc = upload(h, &P.mt_ent, M.ment)) return rc;
+        if (!M.il.empty()) {
+            if (int rc = upload(h, &P.mt_wave, M.mw)) return rc;
+            if (int rc = upload(h, &P.mt_il, M.il)) return rc;
         }
     }
-    if (int rc = upload(h, &P.dup, h->dup)) return rc;
-    if (int rc = upload(h, &P.fill_dst, fill_dst)) return rc;
-    if (int rc = upload(h, &P.fill_src, fill_src)) return rc;
-    if (int rc = upload(h, &P.pad_dst, pad_dst)) return rc;
-    if (int rc = dalloc(h, &P.W, std::max<size_t>(wTotal, 64))) return rc;
-    if (int rc = upload(h, &P.rt, rtab)) return rc;
-    // ---- tile schedule of the factorisation (tile_factor.hpp) ------------------------------------------------
-    if (h->tileMode) {
-        const int nt = P.nmax / TILE;
-        std::vector<std::vector<uint8_t>> live(P.nParts, std::vector<uint8_t>(nt, 0)), pat(P.nParts);
-        for (int ls = 0; ls < P.nParts; ++ls) {
-            for (int r = 0; r < P.nmax; ++r)
-                if (dofmap[(size_t)ls * P.nmax + r] >= 0) live[ls][r / TILE] = 1;
-            pat[ls].assign((size_t)nt * nt, 0);
+    if (h->tune.fuseLog) {
+        int lmax = 0;
+        long long over24 = 0;
+        for (size_t k = 0; k + 1 < M.mp.size(); ++k) {
+            lmax = std::max(lmax, M.mp[k + 1] - M.mp[k]);
+            over24 += M.mp[k + 1] - M.mp[k] > 24;
         }
-        for (const int4 &fb : fillBlk) {
-            const int ls = fb.x, r0 = fb.y, c0 = fb.z;   // memory row / column of the 3x3 block's corner
-            for (int a = 0; a < 3; a += 2)
-                for (int b = 0; b < 3; b += 2) {
-                    const int I = (c0 + b) / TILE, J = (r0 + a) / TILE;   // column-major element (c0+b, r0+a)
-                    if (I <= J) pat[ls][(size_t)I * nt + J] = 1;
-                }
-        }
-        // eager partial updates shorten the launches of a latency-bound factorisation (few subdomains) and cost tile
-        // traffic in a throughput-bound one (measured: profiles/r03_factor_tiles.txt)
-        // (round 4: with very few tile columns in total -- bunny5K: 8 x 32 -- the chain of dependent tasks is all there is, and
-        // the dataflow launch runs finer eager tasks at no barrier cost: 2 / 2 there, factor 0.43 -> 0.39 ms; horse7K, 8 x 47,
-        // keeps 4 / 4)
-        const bool tiny = (long long)P.nParts * nt <= 320;
-        const int eagerMin = h->tune.tileEagerMin > 0 ? h->tune.tileEagerMin : (tiny ? 2 : P.nParts <= 64 ? 4 : 8);
-        const int eagerChunk = tiny ? 2 : P.nParts <= 64 ? 4 : 8;   // early products per eager task
-        // the last task of a Q tile (sum, then the multiplication with -Q_jj): up to 64 subdomains it keeps ONE early product and
-        // hands the others to a task that runs beside DIAG(j) -- the launch between two diagonal launches is then as short as
-        // before round 5 (bar17K 1.125 -> 1.077 ms); above, where every launch is several rounds of workgroups, it keeps them
-        // like any other task and saves the partial sum's round trip (1 M tets 15.5 -> 14.5 ms)
-        const int eagerMinRmul = h->tune.tileEagerMinRmul >= -1 && getenv("DOTMI_TILE_EAGER_MIN_RMUL") ? h->tune.tileEagerMinRmul
-                                                                                                          : (P.nParts <= 64 ? 1 : -1);
-        // the work buffer (H filled in, R in place of it): same layout as the factor buffer W, which only ever holds Q
-        if (int rc = dalloc(h, &h->W2, std::max<size_t>(wTotal, 64))) return rc;
-        TileSchedule S;
-        {
-            std::vector<TileTaskL> all;
-            size_t sn = 0;
-            for (int ls = 0; ls < P.nParts; ++ls)
-                plan_subdomain_tiles(ls, nt, P.W, &rtOff[(size_t)ls * nt], &rtLd[(size_t)ls * nt], &rtC0[(size_t)ls * nt],
-                                     live[ls], pat[ls], h->W2, sn, all, S.clearTiles, S.clearLd, S.flops, S.qTiles,
-                                     eagerMin, eagerChunk, 0, true, eagerMinRmul,
-                                     h->twoLevel ? &rtOffM[(size_t)ls * nt] : nullptr, h->twoLevel ? &rtLdM[(size_t)ls * nt] : nullptr,
-                                     h->twoLevel ? &rtC0M[(size_t)ls * nt] : nullptr, h->twoLevel ? leafTile.data() : nullptr);
-            finish_tile_schedule(all, S);
-        }
-        if (int rc = upload(h, &h->ttasks, S.tasks)) return rc;
-        if (int rc = upload(h, &h->tprods, S.prods)) return rc;
-        if (int rc = upload(h, &h->tclear, S.clearTiles)) return rc;
-        if (int rc = upload(h, &h->tclearLd, S.clearLd)) return rc;
-        h->nTclear = (int)S.clearTiles.size();
-        h->tlevelStart = S.levelStart;
-        h->tlevelDiag = S.levelDiag;
-        h->tileSplit = h->tune.tileSplit >= 0 ? h->tune.tileSplit != 0 : P.nParts > 64;
-        h->nTtasks = (int)S.tasks.size();
-        // Dataflow or levels (profiles/r04_factor_flow.txt): per task the dataflow launch pays a ticket, a look at its
-        // dependencies' flags and write-through stores, and it runs the level kernel's 77 KB workgroups -- it wins where the
-        // levels are launches of less than one round of workgroups, i.e. the chain of dependent tasks paces the phase
-        // (bunny5K / 8 subdomains: 217 tasks per level, 0.57 -> 0.41 ms), and loses where the levels are several rounds
-        // (bar17K / 32: 1000 per level, 1.11 -> 1.21 ms; 1 M tets: 15 -> 23 ms).
-        const size_t nLevels = std::max<size_t>(S.levelStart.size() - 1, 1);
-        h->tileFlow = !S.tasks.empty() &&
-                      (h->tune.tileFlow > 0 || (h->tune.tileFlow < 0 && S.tasks.size() / nLevels <= 512));
-        // the diagonal tasks' per-lane bottom steps (k_tilefactor.hip, block_chol_inv<N, FAST>): every layout (DOTMI_FAST_DIAG=0: the
-        // one-row-per-lane base of round 3); the 256-thread level kernel keeps the old base, and then so does the dataflow launch
-        h->fastDiag = h->tune.fastDiag != 0;
-        if (h->tileFlow) {
-            std::vector<int> depPtr, depIdx;
-            build_tile_deps(S.tasks, S.prods, depPtr, depIdx);
-            if (depIdx.empty()) depIdx.push_back(0);
-            if (int rc = upload(h, &h->tdepPtr, depPtr)) return rc;
-            if (int rc = upload(h, &h->tdepIdx, depIdx)) return rc;
-            if (int rc = dalloc(h, &h->tdone, S.tasks.size())) return rc;
-            if (int rc = dalloc(h, &h->tnext, 2)) return rc;
-            HIPCHECK(h, hipMemset(h->tdone, 0, sizeof(int) * S.tasks.size()));
-            HIPCHECK(h, hipMemset(h->tnext, 0, sizeof(int) * 2));
-            hipDeviceProp_t prop;
-            HIPCHECK(h, hipGetDeviceProperties(&prop, h->device));
-            h->tileFlowWg = 2 * prop.multiProcessorCount;
-            h->tileSplit = false;
-            if (h->tune.fuseLog)
-                fprintf(stderr, "dotmi: tile dataflow: %zu tasks, %zu dependencies, %d workgroups\n", S.tasks.size(), depIdx.size(),
-                        h->tileFlowWg);
-        }
-        if (h->tileSplit) {
-            HIPCHECK(h, hipStreamCreateWithFlags(&h->stDiag, hipStreamNonBlocking));
-            h->tFork.resize(S.levelDiag.size());
-            h->tJoin.resize(S.levelDiag.size());
-            for (auto &e : h->tFork) HIPCHECK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            for (auto &e : h->tJoin) HIPCHECK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        }
-        h->tileFlops = S.flops;
+        fprintf(stderr, "dotmi: merge: %.1f tile partials per dof (longest list %d, %lld lists beyond 24) -> %s\n",
+                (double)M.count / std::max(1, 3 * h->nV), lmax, over24,
+                P.splitMerge ? "sum per subdomain, then gather (split)" : "one walk over the list");
+    }
+    h->mergeEntries = M.count;   // tile partials one merge reads (either form)
+    return 0;
+}
+
+// the tile schedule of the factorisation -> device, and what its launch form needs (flags and counters of the dataflow launch,
+// the side stream and events of the split levels)
+static int upload_factor_schedule(dotmi_handle *h, const FactorSchedule &FS)
+{
+    const TileSchedule &S = FS.S;
+    if (int rc = upload(h, &h->ttasks, S.tasks)) return rc;
+    if (int rc = upload(h, &h->tprods, S.prods)) return rc;
+    if (int rc = upload(h, &h->tclear, S.clearTiles)) return rc;
+    if (int rc = upload(h, &h->tclearLd, S.clearLd)) return rc;
+    h->nTclear = (int)S.clearTiles.size();
+    h->tlevelStart = S.levelStart;
+    h->tlevelDiag = S.levelDiag;
+    h->tileSplit = h->tune.tileSplit >= 0 ? h->tune.tileSplit != 0 : h->P.nParts > 64;
+    h->nTtasks = (int)S.tasks.size();
+    h->tileFlow = FS.flow;
+    // the diagonal tasks' per-lane bottom steps (k_tilefactor.hip, block_chol_inv<N, FAST>): every layout (DOTMI_FAST_DIAG=0: the
+    // one-row-per-lane base of round 3); the 256-thread level kernel keeps the old base, and then so does the dataflow launch
+    h->fastDiag = h->tune.fastDiag != 0;
+    if (h->tileFlow) {
+        if (int rc = upload(h, &h->tdepPtr, FS.depPtr)) return rc;
+        if (int rc = upload(h, &h->tdepIdx, FS.depIdx)) return rc;
+        if (int rc = dalloc(h, &h->tdone, S.tasks.size())) return rc;
+        if (int rc = dalloc(h, &h->tnext, 2)) return rc;
+        HIPCHECK(h, hipMemset(h->tdone, 0, sizeof(int) * S.tasks.size()));
+        HIPCHECK(h, hipMemset(h->tnext, 0, sizeof(int) * 2));
+        hipDeviceProp_t prop;
+        HIPCHECK(h, hipGetDeviceProperties(&prop, h->device));
+        h->tileFlowWg = 2 * prop.multiProcessorCount;
+        h->tileSplit = false;
         if (h->tune.fuseLog)
-            fprintf(stderr, "dotmi: tile schedule: %zu tasks, %zu products, %zu levels, %lld Q tiles, %.1f GF\n", S.tasks.size(),
-                    S.prods.size(), S.levelStart.size() - 1, S.qTiles, S.flops / 1e9);
+            fprintf(stderr, "dotmi: tile dataflow: %zu tasks, %zu dependencies, %d workgroups\n", S.tasks.size(), FS.depIdx.size(),
+                    h->tileFlowWg);
+    }
+    if (h->tileSplit) {
+        HIPCHECK(h, hipStreamCreateWithFlags(&h->stDiag, hipStreamNonBlocking));
+        h->tFork.resize(S.levelDiag.size());
+        h->tJoin.resize(S.levelDiag.size());
+        for (auto &e : h->tFork) HIPCHECK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        for (auto &e : h->tJoin) HIPCHECK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    h->tileFlops = S.flops;
+    if (h->tune.fuseLog)
+        fprintf(stderr, "dotmi: tile schedule: %zu tasks, %zu products, %zu levels, %lld Q tiles, %.1f GF\n", S.tasks.size(),
+                S.prods.size(), S.levelStart.size() - 1, S.qTiles, S.flops / 1e9);
+    return 0;
+}
+
+// the panels of the two-level form (DevTwoLevel) -> device
+static int upload_two_level(dotmi_handle *h, const TwoLevelPanels &T)
+{
+    DevParts &P = h->P;
+    int2 *dItem = nullptr;
+    if (int rc = upload(h, &dItem, T.items)) return rc;
+    P.tl.item = dItem;
+    P.tl.nItems = T.maxRows > 0 ? (int)T.items.size() : 0;
+    int4 *dPanel = nullptr;
+    long long *dBase = nullptr, *dDst = nullptr;
+    if (int rc = upload(h, &dDst, T.rowDst)) return rc;
+    if (int rc = dalloc(h, &P.tl.packed, (size_t)std::max<long long>(T.packedN, 2))) return rc;
+    int *dPos = nullptr, *dPtr = nullptr, *dIdx = nullptr;
+    P.tl.nPanels = T.maxRows > 0 ? (int)T.panel.size() : 0;
+    if (int rc = upload(h, &dPanel, T.panel)) return rc;
+    if (int rc = upload(h, &dBase, T.rowBase)) return rc;
+    if (int rc = upload(h, &dPos, T.rowPos)) return rc;
+    if (int rc = upload(h, &dPtr, T.gPtr)) return rc;
+    if (int rc = upload(h, &dIdx, T.gIdx)) return rc;
+    if (int rc = dalloc(h, &P.tl.cbuf, T.rowBase.size())) return rc;
+    if (int rc = dalloc(h, &P.tl.rpad2, (size_t)P.nParts * P.nmax + 8)) return rc;
+    HIPCHECK(h, hipMemset(P.tl.rpad2, 0, sizeof(double) * ((size_t)P.nParts * P.nmax + 8)));
+    P.tl.panel = dPanel;
+    P.tl.rowSrc = dBase;
+    P.tl.rowBase = dDst;
+    P.tl.rowPos = dPos;
+    P.tl.gPtr = dPtr;
+    P.tl.gIdx = dIdx;
+    P.tl.maxRows = T.maxRows;
+    P.tl.maxCols = T.maxCols;
+    P.tl.on = 1;
+    h->precond_bytes += 2 * T.panelBytes;   // (the panels are streamed twice per application)
+    if (h->tune.fuseLog)
+        fprintf(stderr, "dotmi: two-level back-solve: %d panels (at most %d rows x %d columns), %.1f MB of panels (x 2), %.1f MB in all\n",
+                P.tl.nPanels, T.maxRows, T.maxCols, T.panelBytes / 1e6, h->precond_bytes / 1e6);
+    return 0;
+}
+
+// the subdomain side of the handle: every stage of block_plan.hpp, the uploads of its arrays, the next stage
+int build_device_mesh(dotmi_handle *h)
+{
+    MeshGraph G;
+    std::vector<int> blk_ptr, blk_ent;
+    if (int rc = build_mesh_graph(h, G, blk_ptr, blk_ent)) return rc;
+    if (h->pd) {   // LBFGS-PD: the scalar factor of the constant Laplacian instead of the subdomain block solve (dotmi_pd.hip)
+        if (int rc = build_pd(h, G.adj_ptr, G.adj_idx)) return rc;
+        return build_element_side(h, G.adj_ptr, blk_ptr, blk_ent);
+    }
+    choose_subdomains(h);
+    const std::vector<std::vector<int>> &sets = h->partVerts;
+    const Tuning &tune = h->tune;
+    const int p0 = h->p0, p1 = h->p1;
+    const bool gsdd = (h->flags & DOTMI_FLAG_GSDD) != 0;
+    DevParts &P = h->P;
+    P.nParts = p1 - p0;
+    h->tileMode = P.nParts > 0;   // (a rank without subdomains plans nothing)
+    BlockLayout L;
+    choose_block_layout(G, sets, p0, p1,
+                        LayoutRules{tune.ndLevels, tune.ndMin, tune.ndMinByUser, tune.twoLevel, !gsdd, false, tune.fuseLog}, L);
+    h->nd = L.nd;
+    h->twoLevel = L.twoLevel;
+    P.nmax = L.nmax;
+    RowPlacement rows;
+    place_rows(L, sets, p0, p1, rows);
+    h->precond_bytes = rows.nnzX * 8;
+    // the job table of the back-solve launches (bs_tiles.hpp): tiles per region, wide / narrow / packs, heavy first
+    BsTilePlan TP;
+    plan_backsolve_tiles(L.nd, [&](int k, int ls) { return 3 * (int)L.region[k][ls].size(); }, P.nParts, P.nmax,
+                         BsTileRules{tune.tileRows, tune.tileRowsLong, tune.tilePasses, tune.wavePacks}, TP);
+    if (tune.fuseLog)
+        fprintf(stderr, "dotmi: back-solve: %d one-tile jobs (%d wide), %d packs of four small tiles%s\n", TP.ntiles, TP.ntilesWide,
+                TP.nquad, TP.shallow ? ", shallow launch: long rows in 4-pass tiles" : "");
+    FactorStorage F;
+    plan_factor_storage(L, rows.dofmap, P.nParts, F);
+    if (int rc = check_factors_fit(h, F)) return rc;
+    const RowTileArrays rt = row_tile_arrays(F.rtab), rtM = row_tile_arrays(F.rtabM);
+    h->rtOff = rt.off;
+    h->rtLd = rt.ld;
+    h->rtC0 = rt.c0;
+    h->rtOffM = rtM.off;
+    h->rtLdM = rtM.ld;
+    h->rtC0M = rtM.c0;
+    h->wTotal = F.wTotal;
+    FillLists fill;
+    build_fill_lists(G, sets, p0, p1, rows, P.nmax, F, fill);
+    P.nfill = (int)fill.fill_src.size();
+    P.npad = (int)fill.pad_dst.size();
+    if (int rc = upload_backsolve_tables(h, rows.dofmap, TP)) return rc;
+    std::vector<int> rptr, ridx;
+    build_reduce_lists(TP.ranges, P.nParts, P.nmax, rptr, ridx);
+    if (int rc = upload(h, &P.rp_ptr, rptr)) return rc;
+    if (int rc = upload(h, &P.rp_idx, ridx)) return rc;
+    MergeLists M;
+    build_merge_lists(h->nV, sets, p0, p1, rows, P.nmax, P.nbmax, TP.ranges, tune.splitMerge, L.twoLevel, gsdd, M);
+    if (int rc = upload_merge_lists(h, M)) return rc;
+    if (int rc = upload(h, &P.dup, h->dup)) return rc;
+    if (int rc = upload(h, &P.fill_dst, fill.fill_dst)) return rc;
+    if (int rc = upload(h, &P.fill_src, fill.fill_src)) return rc;
+    if (int rc = upload(h, &P.pad_dst, fill.pad_dst)) return rc;
+    if (int rc = dalloc(h, &P.W, std::max<size_t>(F.wTotal, 64))) return rc;
+    if (int rc = upload(h, &P.rt, F.rtab)) return rc;
+    if (h->tileMode) {
+        // the work buffer (H filled in, R in place of it): same layout as the factor buffer W, which only ever holds Q
+        if (int rc = dalloc(h, &h->W2, std::max<size_t>(F.wTotal, 64))) return rc;
+        FactorSchedule FS;
+        plan_factor_schedule(P.nParts, P.nmax, rows.dofmap, fill.fillBlk, rt, rtM, L.twoLevel ? F.leafTile.data() : nullptr, P.W, h->W2,
+                             ScheduleRules{tune.tileEagerMin, tune.tileEagerMinRmul, tune.tileEagerMinRmulByUser, tune.tileFlow}, FS);
+        if (int rc = upload_factor_schedule(h, FS)) return rc;
     }
     if (int rc = dalloc(h, &P.ppart, (size_t)P.nParts * P.nbmax * P.nmax)) return rc;
     if (int rc = dalloc(h, &P.psub, (size_t)P.nParts * P.nmax)) return rc;
     if (int rc = dalloc(h, &P.rpad, (size_t)P.nParts * P.nmax + 8)) return rc;
     HIPCHECK(h, hipMemset(P.rpad, 0, sizeof(double) * ((size_t)P.nParts * P.nmax + 8)));
     P.tl = DevTwoLevel{};
-    if (h->twoLevel) {
-        // panels: per (subdomain, leaf) the separator vertices next to the leaf (a mesh edge into it; no fill path leaves a leaf),
-        // rows ascending in the layout
-        std::vector<int4> panel;
-        std::vector<long long> rowBase, rowDst;
-        std::vector<int> rowPos, gIdx;
-        long long packedN = 0;
-        std::vector<std::vector<int>> sub((size_t)P.nParts * P.nmax);
-        std::vector<int> leafOf(nV, -1), sepPos(nV, -1);
-        long long panelBytes = 0;
-        int maxRows = 0, maxCols = 0;
-        for (int ls = 0; ls < P.nParts; ++ls) {
-            for (size_t k = 0; k < h->nd.size(); ++k) {
-                const NdNode &N = h->nd[k];
-                const auto &rv = region[k][ls];
-                const int ro = nd_region_first_row(N, 3 * (int)rv.size());
-                for (size_t q = 0; q < rv.size(); ++q) {
-                    if (N.a < 0) leafOf[rv[q]] = (int)k;
-                    else sepPos[rv[q]] = ro + 3 * (int)q;
-                }
-            }
-            for (size_t k = 0; k < h->nd.size(); ++k) {
-                const NdNode &N = h->nd[k];
-                if (N.a >= 0 || region[k][ls].empty()) continue;
-                const auto &rv = region[k][ls];
-                std::vector<int> rows;   // padded positions of the coupled separator vertices
-                for (int v : rv)
-                    for (int e = adj_ptr[v]; e < adj_ptr[v + 1]; ++e)
-                        if (sepPos[adj_idx[e]] >= 0) rows.push_back(sepPos[adj_idx[e]]);
-                std::sort(rows.begin(), rows.end());
-                rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
-                if (rows.empty()) continue;
-                // (the kernels take two columns per lane: the panel starts on an even column -- one column of the leaf's identity
-                // padding in front when its first live column is odd: zeros in M and in the right-hand side -- and ends at the
-                // leaf's end, a multiple of 64)
-                const int c0 = nd_region_first_row(N, 3 * (int)rv.size()) & ~1, used = N.off + N.size - c0;
-                panel.push_back(make_int4((int)rowBase.size(), 3 * (int)rows.size(), ls * P.nmax + c0, used));
-                maxRows = std::max(maxRows, 3 * (int)rows.size());
-                maxCols = std::max(maxCols, used);
-                panelBytes += 8ll * 3 * (long long)rows.size() * used;
-                for (int rp : rows)
-                    for (int d = 0; d < 3; ++d) {
-                        const long long a = waddr(ls, rp + d, c0);
-                        if (a < 0) {
-                            h->err = "two-level layout: a panel row has no storage";
-                            return DOTMI_E_INVALID;
-                        }
-                        sub[(size_t)ls * P.nmax + rp + d].push_back((int)rowBase.size());
-                        rowBase.push_back(a);
-                        rowDst.push_back(packedN);
-                        packedN += used;
-                        rowPos.push_back(ls * P.nmax + rp + d);
-                    }
-            }
-            for (int v : h->partVerts[h->p0 + ls]) leafOf[v] = sepPos[v] = -1;
-        }
-        std::vector<int> gPtr((size_t)P.nParts * P.nmax + 1, 0);
-        for (size_t i = 0; i < sub.size(); ++i) {
-            gPtr[i] = (int)gIdx.size();
-            gIdx.insert(gIdx.end(), sub[i].begin(), sub[i].end());
-        }
-        gPtr[sub.size()] = (int)gIdx.size();
-        if (gIdx.empty()) gIdx.push_back(0);
-        if (panel.empty()) panel.push_back(make_int4(0, 0, 0, 0));
-        if (rowBase.empty()) {
-            rowBase.push_back(0);
-            rowDst.push_back(0);
-            rowPos.push_back(0);
-        }
-        if (maxRows > 7000) {   // (twolevel_backward_kernel keeps a panel's p_G entries in LDS)
-            h->err = "two-level form: a leaf couples to " + std::to_string(maxRows) + " separator rows (limit 7000): split the regions "
-                     "further (DOTMI_ND_LEVELS / DOTMI_ND_MIN) or use DOTMI_TWO_LEVEL=0";
-            return DOTMI_E_INVALID;
-        }
-        std::vector<int2> items;
-        for (size_t q = 0; q < panel.size(); ++q)
-            for (int k0 = 0; k0 < panel[q].y; k0 += 8) items.push_back(make_int2((int)q, k0));
-        if (items.empty()) items.push_back(make_int2(0, 0));
-        int2 *dItem = nullptr;
-        if (int rc = upload(h, &dItem, items)) return rc;
-        P.tl.item = dItem;
-        P.tl.nItems = maxRows > 0 ? (int)items.size() : 0;
-        int4 *dPanel = nullptr;
-        long long *dBase = nullptr, *dDst = nullptr;
-        if (int rc = upload(h, &dDst, rowDst)) return rc;
-        if (int rc = dalloc(h, &P.tl.packed, (size_t)std::max<long long>(packedN, 2))) return rc;
-        int *dPos = nullptr, *dPtr = nullptr, *dIdx = nullptr;
-        P.tl.nPanels = maxRows > 0 ? (int)panel.size() : 0;
-        if (int rc = upload(h, &dPanel, panel)) return rc;
-        if (int rc = upload(h, &dBase, rowBase)) return rc;
-        if (int rc = upload(h, &dPos, rowPos)) return rc;
-        if (int rc = upload(h, &dPtr, gPtr)) return rc;
-        if (int rc = upload(h, &dIdx, gIdx)) return rc;
-        if (int rc = dalloc(h, &P.tl.cbuf, rowBase.size())) return rc;
-        if (int rc = dalloc(h, &P.tl.rpad2, (size_t)P.nParts * P.nmax + 8)) return rc;
-        HIPCHECK(h, hipMemset(P.tl.rpad2, 0, sizeof(double) * ((size_t)P.nParts * P.nmax + 8)));
-        P.tl.panel = dPanel;
-        P.tl.rowSrc = dBase;
-        P.tl.rowBase = dDst;
-        P.tl.rowPos = dPos;
-        P.tl.gPtr = dPtr;
-        P.tl.gIdx = dIdx;
-        P.tl.maxRows = maxRows;
-        P.tl.maxCols = maxCols;
-        P.tl.on = 1;
-        h->precond_bytes += 2 * panelBytes;   // (the panels are streamed twice per application)
-        if (h->tune.fuseLog)
-            fprintf(stderr, "dotmi: two-level back-solve: %d panels (at most %d rows x %d columns), %.1f MB of panels (x 2), %.1f MB in all\n",
-                    P.tl.nPanels, maxRows, maxCols, panelBytes / 1e6, h->precond_bytes / 1e6);
+    if (L.twoLevel) {
+        TwoLevelPanels T;
+        h->err = plan_two_level_panels(G, L, sets, p0, p1, F, T);
+        if (!h->err.empty()) return DOTMI_E_INVALID;
+        if (int rc = upload_two_level(h, T)) return rc;
     }
     if (int rc = dalloc(h, &h->info_dev, (size_t)std::max(P.nParts, 1))) return rc;
     HIPCHECK(h, hipHostMalloc((void **)&h->h_info, sizeof(int) * std::max(P.nParts, 1)));
     memset(h->h_info, 0, sizeof(int) * std::max(P.nParts, 1));
-
-    return build_element_side(h, adj_ptr, blk_ptr, blk_ent);
+    h->partPos = std::move(rows.partPos);
+    return build_element_side(h, G.adj_ptr, blk_ptr, blk_ent);
 }
+
 
 LbfgsArgs lbfgs_args(const dotmi_handle *h)
 {
@@ -1321,48 +944,25 @@ int dotmi_plan_layout(int32_t nV, int32_t nT, const int32_t *T, const double *Xr
                       int32_t nParts, int32_t p0, int32_t p1, int32_t levels, int32_t min_split, int32_t node_cap,
                       int32_t *nodes, int32_t *n_nodes, int32_t *nmax, int32_t *pos)
 {
-    if (nV < 1 || nT < 1 || !T || !Xrest || !epart || nParts < 1 || p0 < 0 || p1 > nParts || p0 > p1 || !n_nodes ||
-        !nmax)
+    if (nV < 1 || nT < 1 || !T || !Xrest || !epart || nParts < 1 || p0 < 0 || p1 > nParts || p0 > p1 || !n_nodes || !nmax ||
+        !mesh_is_valid(nV, nT, T, epart, nParts))
         return DOTMI_E_INVALID;
-    for (int e = 0; e < nT; ++e) {
-        if (epart[e] < 0 || epart[e] >= nParts) return DOTMI_E_INVALID;
-        for (int k = 0; k < 4; ++k)
-            if (T[4 * e + k] < 0 || T[4 * e + k] >= nV) return DOTMI_E_INVALID;
-    }
-    std::vector<int> adj_ptr, adj_idx;
-    build_adjacency(nV, nT, T, adj_ptr, adj_idx);
-    std::vector<std::vector<int>> sets(p1 - p0);
-    {
-        std::vector<int> mark(nV, -1);
-        for (int e = 0; e < nT; ++e) {
-            const int pI = epart[e];
-            if (pI < p0 || pI >= p1) continue;
-            for (int k = 0; k < 4; ++k) sets[pI - p0].push_back(T[4 * e + k]);
-        }
-        for (auto &v : sets) {
-            std::sort(v.begin(), v.end());
-            v.erase(std::unique(v.begin(), v.end()), v.end());
-        }
-    }
-    std::vector<NdNode> tree;
-    std::vector<std::vector<std::vector<int>>> region;
-    // dotmi_create's rule: depth (and, with it, the split threshold) from ALL subdomains of the mesh
-    int levelsUse = levels, minUse = min_split < 128 ? ND_MIN_SPLIT : min_split;
-    if (levels < 0) {
-        std::vector<std::vector<int>> allSets(nParts);
-        for (int e = 0; e < nT; ++e)
-            for (int k = 0; k < 4; ++k) allSets[epart[e]].push_back(T[4 * e + k]);
-        for (auto &v : allSets) {
-            std::sort(v.begin(), v.end());
-            v.erase(std::unique(v.begin(), v.end()), v.end());
-        }
-        if (min_split < 128) nd_choose_depth(allSets, nV, adj_ptr, adj_idx, Xrest, BS_NARROW, ND_MIN_SPLIT, levelsUse, minUse);
-        else levelsUse = nd_default_levels(allSets);
-    }
-    *nmax = nd_plan(sets, nV, adj_ptr, adj_idx, Xrest, levelsUse, minUse, tree, region);
-    // (the leaves-first layout of the two-level back-solve when the environment forces that form: DOTMI_TWO_LEVEL=1; the automatic
-    // choice of dotmi_create -- where the one-pass form would stream 240 MB or more, on at least four levels -- is the caller's to mirror)
-    if (getenv("DOTMI_TWO_LEVEL") && atoi(getenv("DOTMI_TWO_LEVEL")) > 0) nd_relayout_leaves_first(tree);
+    const MeshGraph G = mesh_graph(nV, nT, T, Xrest);
+    const std::vector<std::vector<int>> allSets = part_vertex_sets(nT, T, epart, nParts);
+    // dotmi_create's rule where the caller leaves them open: depth (and, with it, the split threshold) from ALL subdomains of the mesh
+    // (the leaves-first layout of the two-level back-solve when the environment forces that form: DOTMI_TWO_LEVEL=1, on the tree the
+    // caller asks for; the automatic choice of dotmi_create -- where the one-pass form would stream 240 MB or more, on at least four
+    // levels -- is the caller's to mirror)
+    LayoutRules R;
+    R.ndLevels = levels;
+    R.ndMin = min_split < 128 ? ND_MIN_SPLIT : min_split;
+    R.ndMinByUser = min_split >= 128;
+    R.twoLevel = Tuning::from_env().twoLevel > 0;
+    R.keepDepth = true;
+    BlockLayout L;
+    choose_block_layout(G, allSets, p0, p1, R, L);
+    const std::vector<NdNode> &tree = L.nd;
+    *nmax = L.nmax;
     *n_nodes = (int32_t)tree.size();
     if (nodes) {
         if ((int)tree.size() > node_cap) return DOTMI_E_INVALID;
@@ -1373,17 +973,9 @@ int dotmi_plan_layout(int32_t nV, int32_t nT, const int32_t *T, const double *Xr
         }
     }
     if (pos) {
-        size_t base = 0;
-        for (size_t ls = 0; ls < sets.size(); ++ls) {
-            std::unordered_map<int, int> posOf;
-            for (size_t nd = 0; nd < tree.size(); ++nd) {
-                const auto &rv = region[nd][ls];
-                const int ro = nd_region_first_row(tree[nd], 3 * (int)rv.size());
-                for (size_t k = 0; k < rv.size(); ++k) posOf[rv[k]] = ro + 3 * (int)k;
-            }
-            for (size_t i = 0; i < sets[ls].size(); ++i) pos[base + i] = posOf.at(sets[ls][i]);
-            base += sets[ls].size();
-        }
+        RowPlacement rows;
+        place_rows(L, allSets, p0, p1, rows);
+        for (const auto &pp : rows.partPos) pos = std::copy(pp.begin(), pp.end(), pos);
     }
     return 0;
 }
@@ -1397,31 +989,16 @@ int dotmi_plan_layout(int32_t nV, int32_t nT, const int32_t *T, const double *Xr
 int dotmi_plan_backsolve_tiles(int32_t nV, int32_t nT, const int32_t *T, const double *Xrest, const int32_t *epart, int32_t nParts,
                                int32_t p0, int32_t p1, int32_t cap, int32_t *tiles, int32_t *counts)
 {
-    if (nV < 1 || nT < 1 || !T || !Xrest || !epart || nParts < 1 || p0 < 0 || p1 > nParts || p0 > p1 || !counts) return DOTMI_E_INVALID;
-    for (int e = 0; e < nT; ++e) {
-        if (epart[e] < 0 || epart[e] >= nParts) return DOTMI_E_INVALID;
-        for (int k = 0; k < 4; ++k)
-            if (T[4 * e + k] < 0 || T[4 * e + k] >= nV) return DOTMI_E_INVALID;
-    }
-    std::vector<int> adj_ptr, adj_idx;
-    build_adjacency(nV, nT, T, adj_ptr, adj_idx);
-    std::vector<std::vector<int>> allSets(nParts);
-    for (int e = 0; e < nT; ++e)
-        for (int k = 0; k < 4; ++k) allSets[epart[e]].push_back(T[4 * e + k]);
-    for (auto &v : allSets) {
-        std::sort(v.begin(), v.end());
-        v.erase(std::unique(v.begin(), v.end()), v.end());
-    }
+    if (nV < 1 || nT < 1 || !T || !Xrest || !epart || nParts < 1 || p0 < 0 || p1 > nParts || p0 > p1 || !counts ||
+        !mesh_is_valid(nV, nT, T, epart, nParts))
+        return DOTMI_E_INVALID;
+    const MeshGraph G = mesh_graph(nV, nT, T, Xrest);
     const Tuning tune = Tuning::from_env();
-    int levels = tune.ndLevels, minSplit = tune.ndMin;
-    if (levels < 0 && !getenv("DOTMI_ND_MIN")) nd_choose_depth(allSets, nV, adj_ptr, adj_idx, Xrest, BS_NARROW, minSplit, levels, minSplit);
-    else if (levels < 0) levels = nd_default_levels(allSets);
-    std::vector<std::vector<int>> sets(allSets.begin() + p0, allSets.begin() + p1);
-    std::vector<NdNode> tree;
-    std::vector<std::vector<std::vector<int>>> region;
-    const int nmax = nd_plan(sets, nV, adj_ptr, adj_idx, Xrest, levels, minSplit, tree, region);
+    BlockLayout L;   // (the one-pass form's layout)
+    choose_block_layout(G, part_vertex_sets(nT, T, epart, nParts), p0, p1, LayoutRules{tune.ndLevels, tune.ndMin, tune.ndMinByUser, 0}, L);
+    const int nmax = L.nmax;
     BsTilePlan TP;
-    plan_backsolve_tiles(tree, [&](int k, int ls) { return 3 * (int)region[k][ls].size(); }, p1 - p0, nmax,
+    plan_backsolve_tiles(L.nd, [&](int k, int ls) { return 3 * (int)L.region[k][ls].size(); }, p1 - p0, nmax,
                          BsTileRules{tune.tileRows, tune.tileRowsLong, tune.tilePasses, tune.wavePacks}, TP);
     const int nN = TP.ntiles - TP.ntilesWide;
     int n = 0;
@@ -1447,21 +1024,10 @@ int dotmi_plan_rank(int32_t nV, int32_t nT, const int32_t *T, const int32_t *epa
                     int32_t *part_size)
 {
     if (nV < 1 || nT < 1 || !T || !epart || nParts < 1 || world < 1 || rank < 0 || rank >= world) return DOTMI_E_INVALID;
-    std::vector<int32_t> ps(nParts, 0), first(world + 1);
-    {
-        std::vector<int> mark(nV, -1);
-        for (int pI = 0; pI < nParts; ++pI)
-            for (int e = 0; e < nT; ++e)
-                if (epart[e] == pI)
-                    for (int k = 0; k < 4; ++k) {
-                        const int v = T[4 * e + k];
-                        if (v < 0 || v >= nV) return DOTMI_E_INVALID;
-                        if (mark[v] != pI) {
-                            mark[v] = pI;
-                            ps[pI] += 3;
-                        }
-                    }
-    }
+    if (!mesh_is_valid(nV, nT, T, nullptr, nParts)) return DOTMI_E_INVALID;
+    const std::vector<std::vector<int>> sets = part_vertex_sets(nT, T, epart, nParts);
+    std::vector<int32_t> ps(nParts), first(world + 1);
+    for (int pI = 0; pI < nParts; ++pI) ps[pI] = 3 * (int32_t)sets[pI].size();
     dotmi_plan_shards(nParts, ps.data(), world, first.data());
     if (p0) *p0 = first[rank];
     if (p1) *p1 = first[rank + 1];
@@ -1509,29 +1075,11 @@ int32_t dotmi_factor_kind(const dotmi_handle *h)
 int dotmi_plan_backsolve_form(int32_t nV, int32_t nT, const int32_t *T, const double *Xrest, const int32_t *epart, int32_t nParts,
                               int32_t *form, int64_t *one_pass_bytes)
 {
-    if (nV < 1 || nT < 1 || !T || !Xrest || !epart || nParts < 1 || !form) return DOTMI_E_INVALID;
-    for (int e = 0; e < nT; ++e) {
-        if (epart[e] < 0 || epart[e] >= nParts) return DOTMI_E_INVALID;
-        for (int k = 0; k < 4; ++k)
-            if (T[4 * e + k] < 0 || T[4 * e + k] >= nV) return DOTMI_E_INVALID;
-    }
-    std::vector<int> adj_ptr, adj_idx;
-    build_adjacency(nV, nT, T, adj_ptr, adj_idx);
-    std::vector<std::vector<int>> allSets(nParts);
-    for (int e = 0; e < nT; ++e)
-        for (int k = 0; k < 4; ++k) allSets[epart[e]].push_back(T[4 * e + k]);
-    for (auto &v : allSets) {
-        std::sort(v.begin(), v.end());
-        v.erase(std::unique(v.begin(), v.end()), v.end());
-    }
-    int levels = -1, minSplit = ND_MIN_SPLIT;
-    nd_choose_depth(allSets, nV, adj_ptr, adj_idx, Xrest, BS_NARROW, ND_MIN_SPLIT, levels, minSplit);
-    std::vector<NdNode> tree;
-    std::vector<std::vector<std::vector<int>>> region;
-    nd_plan(allSets, nV, adj_ptr, adj_idx, Xrest, levels, minSplit, tree, region);
-    const long long bytes = tree.empty() ? 0 : 8 * one_pass_nnz(tree, region, nParts);
-    *form = (!tree.empty() && tree[0].a >= 0 && bytes >= TWO_LEVEL_FROM_BYTES) ? 1 : 0;
-    if (one_pass_bytes) *one_pass_bytes = bytes;
+    if (nV < 1 || nT < 1 || !T || !Xrest || !epart || nParts < 1 || !form || !mesh_is_valid(nV, nT, T, epart, nParts)) return DOTMI_E_INVALID;
+    BlockLayout L;
+    choose_block_layout(mesh_graph(nV, nT, T, Xrest), part_vertex_sets(nT, T, epart, nParts), 0, nParts, LayoutRules(), L);
+    *form = L.twoLevel ? 1 : 0;
+    if (one_pass_bytes) *one_pass_bytes = L.onePassBytes;
     return 0;
 }
 
@@ -1584,32 +1132,9 @@ void dotmi_destroy(dotmi_handle *h)
     delete h;
 }
 
-static int create_impl(dotmi_handle *h, const dotmi_mesh *mesh, const dotmi_params *prm, const double *x_init)
+// the caller's mesh and parameters -> the handle's configuration and host copies (no device call)
+static int take_arguments(dotmi_handle *h, const dotmi_mesh *mesh, const dotmi_params *prm)
 {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        h->err = "no HIP device available: libdotmi has no CPU fallback";
-        return DOTMI_E_NOGPU;
-    }
-    if (!mesh || !prm || !x_init || mesh->nV <= 0 || mesh->nT <= 0 || !mesh->X_rest || !mesh->T || !mesh->mu ||
-        !mesh->lambda || !mesh->fixed || mesh->nParts < 1 || prm->dt <= 0 ||
-        prm->history < 1 || prm->history > HIST_MAX || prm->world < 1 || prm->rank < 0 ||
-        prm->rank >= prm->world || (prm->world > 1 && !prm->comm_id && !prm->allreduce) ||
-        (prm->energy != DOTMI_ENERGY_FCR && prm->energy != DOTMI_ENERGY_SNH)) {
-        h->err = "invalid argument";
-        return DOTMI_E_INVALID;
-    }
-    for (int e = 0; e < mesh->nT; ++e) {
-        if (mesh->epart && !mesh->vpart && (mesh->epart[e] < 0 || mesh->epart[e] >= mesh->nParts)) {
-            h->err = "epart out of range";
-            return DOTMI_E_INVALID;
-        }
-        for (int k = 0; k < 4; ++k)
-            if (mesh->T[4 * e + k] < 0 || mesh->T[4 * e + k] >= mesh->nV) {
-                h->err = "tet index out of range";
-                return DOTMI_E_INVALID;
-            }
-    }
     h->nV = mesh->nV;
     h->nT = mesh->nT;
     h->n = 3 * mesh->nV;
@@ -1668,6 +1193,111 @@ static int create_impl(dotmi_handle *h, const dotmi_mesh *mesh, const dotmi_para
     h->Xrest.assign(mesh->X_rest, mesh->X_rest + h->n);
     h->mu.assign(mesh->mu, mesh->mu + h->nT);
     h->lam.assign(mesh->lambda, mesh->lambda + h->nT);
+    return 0;
+}
+
+// which loop runs on this handle (device / host, early order, vertex patches): needs the subdomains' tables (build_device_mesh)
+static int choose_loop_form(dotmi_handle *h)
+{
+    h->gsdd = (h->flags & DOTMI_FLAG_GSDD) != 0;
+    h->newton = (h->flags & DOTMI_FLAG_NEWTON) != 0;
+    if (h->newton && (h->dist || h->gsdd)) {
+        h->err = "DOTMI_FLAG_NEWTON: single GPU, not together with DOTMI_FLAG_GSDD";
+        return DOTMI_E_INVALID;
+    }
+    if (h->gsdd && h->dist) {
+        h->err = "DOTMI_FLAG_GSDD: single GPU only";
+        return DOTMI_E_INVALID;
+    }
+    h->devLoop = !h->gsdd && !h->newton && !h->pd && !(h->flags & (DOTMI_FLAG_HOST_LOOP | DOTMI_FLAG_TIME_PHASES));
+    // replicated element pass, merged tile partials: the back-solve of the next direction is issued on the trial
+    // gradient, beside the controller (enqueue_loop_slot); sharded subdomains keep their one collective per iteration
+    // (round 4: also with the sharded element pass -- the scatter of -g and H s_new then happen in pair_stats, behind the
+    // gradient's all-reduce; DOTMI_EARLY_SHARDED=0 keeps the q-based order there)
+    h->earlyBs = h->devLoop && h->tune.earlyBs != 0 &&
+                 (h->P.mt_ptr != nullptr || h->P.splitMerge);
+    if (h->owner && !(h->earlyBs && h->tune.fuseDir)) {
+        h->err = "DOTMI_FLAG_OWNER_EXCHANGE needs the device loop's early order with the fused direction kernel";
+        return DOTMI_E_INVALID;
+    }
+    // the trials' grouping of the energy partials, everywhere: the start-of-step evaluation and the fused-step trials must
+    // sum E in the same grouping or an `E > E_cur` verdict can flip at rounding level (the owner exchange runs the fused
+    // step on its sharded element pass too)
+    if (h->earlyBs && h->tune.fuseStep && (!h->shardElems || h->owner)) h->PT.wgCap = h->PTspec.wgCap = 512;
+    // vertex patches: one rank, the early order with both fused kernels (their statements are what k_elemvert.hip keeps), a
+    // 256-thread back-solve launch to host the controller, every patch a workgroup of its own, its LDS within 64 KB
+    h->vpFits = false;
+    // (Stable Neo-Hookean only: its element work is ~1 us of a workgroup's ~12, so carrying every element 1.9 times is free; with
+    // the fixed-corotational SVD the doubled element work costs what the saved launch gives -- bunny5K 1.656 -> 1.696 ms, measured)
+    if (h->earlyBs && !h->dist && h->world == 1 && h->tune.fuseStep && h->tune.fuseDir && h->tune.vertexPatches != 0 &&
+        (h->mat == DOTMI_ENERGY_SNH || h->tune.vertexPatches > 0) &&
+        h->P.ntiles - h->P.ntilesWide + h->P.nquad > 0 && !(h->flags & (DOTMI_FLAG_GSDD | DOTMI_FLAG_NEWTON | DOTMI_FLAG_HOST_LOOP))) {
+        const HostVPatches HV = build_vpatches(h->nV, h->nT, h->T.data(), h->Xrest.data(), 512, 85);
+        const size_t shm = sizeof(double) * ((size_t)3 * HV.PV + (size_t)3 * HV.RUN) + 2 * (size_t)((HV.PO + 1 + 3) & ~3);
+        if (HV.nPatches > 0 && HV.nPatches <= 512 && HV.nPatches <= ELEM_NB_MAX && shm <= 64 * 1024 && HV.PO + 1 <= 256) {
+            if (int rc = upload_vpatches(h, HV, h->VP)) return rc;
+            h->vpFits = true;
+            if (h->tune.fuseLog)
+                fprintf(stderr, "dotmi: vertex patches: %d patches, %.2f x the elements, up to %d owned / %d touched vertices, runs %d, %zu B LDS\n",
+                        HV.nPatches, (double)h->VP.nSlotsUsed / std::max(1, h->nT), HV.PO, HV.PV, HV.RUN, shm);
+        }
+    }
+    return 0;
+}
+
+// the buffers of the loop chosen above
+static int alloc_loop_state(dotmi_handle *h)
+{
+    if (h->dist) {
+        if (int rc = dalloc(h, &h->zstage, (size_t)h->n)) return rc;
+        HIPCHECK(h, hipMemsetAsync(h->zstage, 0, sizeof(double) * h->n, h->st));   // (owner exchange: stays zero off the held set)
+    }
+    if (h->earlyBs) {
+        if (int rc = dalloc(h, &h->u_old, (size_t)h->n)) return rc;
+        for (int sl = 0; sl <= h->hist; ++sl) {
+            if (int rc = dalloc(h, &h->MY[sl], (size_t)h->n)) return rc;
+            if (int rc = dalloc(h, &h->HS[sl], (size_t)h->n)) return rc;
+        }
+    }
+    h->logCap = std::min(h->iterCap, 10001) + 1;
+    h->kindCap = 4096;
+    HIPCHECK(h, hipHostMalloc((void **)&h->h_ctl, sizeof(DevLoop)));
+    HIPCHECK(h, hipHostMalloc((void **)&h->h_flags, sizeof(int) * 4));
+    HIPCHECK(h, hipMalloc((void **)&h->ctl, sizeof(DevLoop)));
+    h->allocs.push_back(h->ctl);
+    if (int rc = dalloc(h, &h->dlog, (size_t)3 * h->logCap)) return rc;
+    HIPCHECK(h, hipMalloc((void **)&h->dkind, sizeof(int) * h->kindCap));
+    h->allocs.push_back(h->dkind);
+    return 0;
+}
+
+static int create_impl(dotmi_handle *h, const dotmi_mesh *mesh, const dotmi_params *prm, const double *x_init)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        h->err = "no HIP device available: libdotmi has no CPU fallback";
+        return DOTMI_E_NOGPU;
+    }
+    if (!mesh || !prm || !x_init || mesh->nV <= 0 || mesh->nT <= 0 || !mesh->X_rest || !mesh->T || !mesh->mu ||
+        !mesh->lambda || !mesh->fixed || mesh->nParts < 1 || prm->dt <= 0 ||
+        prm->history < 1 || prm->history > HIST_MAX || prm->world < 1 || prm->rank < 0 ||
+        prm->rank >= prm->world || (prm->world > 1 && !prm->comm_id && !prm->allreduce) ||
+        (prm->energy != DOTMI_ENERGY_FCR && prm->energy != DOTMI_ENERGY_SNH)) {
+        h->err = "invalid argument";
+        return DOTMI_E_INVALID;
+    }
+    for (int e = 0; e < mesh->nT; ++e) {
+        if (mesh->epart && !mesh->vpart && (mesh->epart[e] < 0 || mesh->epart[e] >= mesh->nParts)) {
+            h->err = "epart out of range";
+            return DOTMI_E_INVALID;
+        }
+        for (int k = 0; k < 4; ++k)
+            if (mesh->T[4 * e + k] < 0 || mesh->T[4 * e + k] >= mesh->nV) {
+                h->err = "tet index out of range";
+                return DOTMI_E_INVALID;
+            }
+    }
+    if (int rc = take_arguments(h, mesh, prm)) return rc;
 
     HIPCHECK(h, hipSetDevice(h->device));
     HIPCHECK(h, hipStreamCreate(&h->st));
@@ -1746,71 +1376,8 @@ static int create_impl(dotmi_handle *h, const dotmi_mesh *mesh, const dotmi_para
     HIPCHECK(h, hipHostMalloc((void **)&h->h_partE, sizeof(double) * 2 * ELEM_NB_MAX));
     HIPCHECK(h, hipHostMalloc((void **)&h->h_partR, sizeof(double) * NB_RED * RED_K));
     HIPCHECK(h, hipHostMalloc((void **)&h->h_alpha, sizeof(double) * 8));
-    {
-        h->gsdd = (h->flags & DOTMI_FLAG_GSDD) != 0;
-        h->newton = (h->flags & DOTMI_FLAG_NEWTON) != 0;
-        if (h->newton && (h->dist || h->gsdd)) {
-            h->err = "DOTMI_FLAG_NEWTON: single GPU, not together with DOTMI_FLAG_GSDD";
-            return DOTMI_E_INVALID;
-        }
-        if (h->gsdd && h->dist) {
-            h->err = "DOTMI_FLAG_GSDD: single GPU only";
-            return DOTMI_E_INVALID;
-        }
-        h->devLoop = !h->gsdd && !h->newton && !h->pd && !(h->flags & (DOTMI_FLAG_HOST_LOOP | DOTMI_FLAG_TIME_PHASES));
-        // replicated element pass, merged tile partials: the back-solve of the next direction is issued on the trial
-        // gradient, beside the controller (enqueue_loop_slot); sharded subdomains keep their one collective per iteration
-        // (round 4: also with the sharded element pass -- the scatter of -g and H s_new then happen in pair_stats, behind the
-        // gradient's all-reduce; DOTMI_EARLY_SHARDED=0 keeps the q-based order there)
-        h->earlyBs = h->devLoop && h->tune.earlyBs != 0 &&
-                     (h->P.mt_ptr != nullptr || h->P.splitMerge);
-        if (h->owner && !(h->earlyBs && h->tune.fuseDir)) {
-            h->err = "DOTMI_FLAG_OWNER_EXCHANGE needs the device loop's early order with the fused direction kernel";
-            return DOTMI_E_INVALID;
-        }
-        // the trials' grouping of the energy partials, everywhere: the start-of-step evaluation and the fused-step trials must
-        // sum E in the same grouping or an `E > E_cur` verdict can flip at rounding level (the owner exchange runs the fused
-        // step on its sharded element pass too)
-        if (h->earlyBs && h->tune.fuseStep && (!h->shardElems || h->owner)) h->PT.wgCap = h->PTspec.wgCap = 512;
-        // vertex patches: one rank, the early order with both fused kernels (their statements are what k_elemvert.hip keeps), a
-        // 256-thread back-solve launch to host the controller, every patch a workgroup of its own, its LDS within 64 KB
-        h->vpFits = false;
-        // (Stable Neo-Hookean only: its element work is ~1 us of a workgroup's ~12, so carrying every element 1.9 times is free; with
-        // the fixed-corotational SVD the doubled element work costs what the saved launch gives -- bunny5K 1.656 -> 1.696 ms, measured)
-        if (h->earlyBs && !h->dist && h->world == 1 && h->tune.fuseStep && h->tune.fuseDir && h->tune.vertexPatches != 0 &&
-            (h->mat == DOTMI_ENERGY_SNH || h->tune.vertexPatches > 0) &&
-            h->P.ntiles - h->P.ntilesWide + h->P.nquad > 0 && !(h->flags & (DOTMI_FLAG_GSDD | DOTMI_FLAG_NEWTON | DOTMI_FLAG_HOST_LOOP))) {
-            const HostVPatches HV = build_vpatches(h->nV, h->nT, h->T.data(), h->Xrest.data(), 512, 85);
-            const size_t shm = sizeof(double) * ((size_t)3 * HV.PV + (size_t)3 * HV.RUN) + 2 * (size_t)((HV.PO + 1 + 3) & ~3);
-            if (HV.nPatches > 0 && HV.nPatches <= 512 && HV.nPatches <= ELEM_NB_MAX && shm <= 64 * 1024 && HV.PO + 1 <= 256) {
-                if (int rc = upload_vpatches(h, HV, h->VP)) return rc;
-                h->vpFits = true;
-                if (h->tune.fuseLog)
-                    fprintf(stderr, "dotmi: vertex patches: %d patches, %.2f x the elements, up to %d owned / %d touched vertices, runs %d, %zu B LDS\n",
-                            HV.nPatches, (double)h->VP.nSlotsUsed / std::max(1, h->nT), HV.PO, HV.PV, HV.RUN, shm);
-            }
-        }
-        if (h->dist) {
-            if (int rc = dalloc(h, &h->zstage, (size_t)h->n)) return rc;
-            HIPCHECK(h, hipMemsetAsync(h->zstage, 0, sizeof(double) * h->n, h->st));   // (owner exchange: stays zero off the held set)
-        }
-        if (h->earlyBs) {
-            if (int rc = dalloc(h, &h->u_old, (size_t)h->n)) return rc;
-            for (int sl = 0; sl <= h->hist; ++sl) {
-                if (int rc = dalloc(h, &h->MY[sl], (size_t)h->n)) return rc;
-                if (int rc = dalloc(h, &h->HS[sl], (size_t)h->n)) return rc;
-            }
-        }
-        h->logCap = std::min(h->iterCap, 10001) + 1;
-        h->kindCap = 4096;
-        HIPCHECK(h, hipHostMalloc((void **)&h->h_ctl, sizeof(DevLoop)));
-        HIPCHECK(h, hipHostMalloc((void **)&h->h_flags, sizeof(int) * 4));
-        HIPCHECK(h, hipMalloc((void **)&h->ctl, sizeof(DevLoop)));
-        h->allocs.push_back(h->ctl);
-        if (int rc = dalloc(h, &h->dlog, (size_t)3 * h->logCap)) return rc;
-        HIPCHECK(h, hipMalloc((void **)&h->dkind, sizeof(int) * h->kindCap));
-        h->allocs.push_back(h->dkind);
-    }
+    if (int rc = choose_loop_form(h)) return rc;
+    if (int rc = alloc_loop_state(h)) return rc;
 
     // Optimizer.cpp:124-184: result = data0 (+script init), v = 0, x_n = x, x~
     HIPCHECK(h, hipMemcpyAsync(h->x, x_init, sizeof(double) * n, hipMemcpyHostToDevice, h->st));

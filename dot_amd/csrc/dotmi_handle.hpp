@@ -1,5 +1,5 @@
 // dotmi_handle.hpp -- the handle behind the C ABI and what the translation units of libdotmi share (private).
-//   dotmi_create.hip      setup: mesh features, partition maps, dissection layout, tile schedule, buffers; host-only planners
+//   dotmi_create.hip      setup: mesh features, the planning stages of block_plan.hpp with their uploads, buffers; host-only planners
 //   dotmi_refresh.hip     Hessian refresh + subdomain factorisation (issue / finish / asynchronous verdict)
 //   dotmi_collectives.hip all-reduce (RCCL or host hook) and the owner exchange's packets
 //   dotmi_loop.hip        the L-BFGS-H loop: slots of the device loop, host loop, GSDD, Newton, dotmi_step
@@ -62,6 +62,7 @@ using namespace dotmi;
 struct Tuning {
     int ndLevels = -1;        // DOTMI_ND_LEVELS      depth of the nested dissection (-1: nd_default_levels)
     int ndMin = ND_MIN_SPLIT; // DOTMI_ND_MIN         smallest region (scalars) that is still split
+    bool ndMinByUser = false; //                      (set at all: the depth rule of block_plan.hpp keeps the caller's threshold)
     bool wavePacks = true;    // DOTMI_WAVE_PACKS=0   small back-solve tiles as one-tile jobs like the others instead of four per workgroup
     int tilePasses = 4;       // DOTMI_TILE_PASSES    most passes (of 8 rows) a back-solve tile of rows beyond 1024 columns takes (8: 64-row tiles)
     int tileRows = 0;         // DOTMI_TILE_ROWS      rows per back-solve tile (0: 64, or 32 for few subdomains)
@@ -88,6 +89,7 @@ struct Tuning {
                               //                         default: where a level holds fewer tasks than the GPU holds workgroups
     int tileFlowWaitMs = 2000;   // DOTMI_TILE_FLOW_WAIT_MS  a task that waits longer for one of its dependencies gives up (error)
     int tileEagerMinRmul = -1; // DOTMI_TILE_EAGER_MIN_RMUL early products the last task of a Q tile may keep (-1: as the others; 0: none)
+    bool tileEagerMinRmulByUser = false;   //           (unset: one up to 64 subdomains, as the others above)
     bool fuseDir = true;      // DOTMI_FUSE_DIR=0     (early order) build_p and spmv_dots as two launches instead of one on cached H s_j
     bool fuseStep = true;     // DOTMI_FUSE_STEP=0    (early order) step_forward as a launch of its own instead of inside the element pass
     bool earlyAbort = true;   // DOTMI_EARLY_ABORT=0  (ablation) speculative back-solves run to their end even when the trial is rejected
@@ -118,6 +120,7 @@ struct Tuning {
         t.ndLevels = geti("DOTMI_ND_LEVELS", -1);
         if (t.ndLevels < -1) t.ndLevels = 0;
         t.ndMin = std::max(128, geti("DOTMI_ND_MIN", ND_MIN_SPLIT));
+        t.ndMinByUser = getenv("DOTMI_ND_MIN") != nullptr;
         if (const char *ev = getenv("DOTMI_TILE_ROWS")) t.tileRows = std::min(64, std::max(8, atoi(ev) / 8 * 8));
         t.tileRowsLong = geti("DOTMI_TILE_ROWS_LONG", 0);
         if (t.tileRowsLong > 0) t.tileRowsLong = std::min(64, std::max(8, t.tileRowsLong / 8 * 8));
@@ -135,6 +138,7 @@ struct Tuning {
         t.fastDiag = geti("DOTMI_FAST_DIAG", 1);
         t.tileFlowWaitMs = std::max(1, geti("DOTMI_TILE_FLOW_WAIT_MS", 2000));
         t.tileEagerMinRmul = geti("DOTMI_TILE_EAGER_MIN_RMUL", -1);
+        t.tileEagerMinRmulByUser = getenv("DOTMI_TILE_EAGER_MIN_RMUL") != nullptr;
         t.earlyBs = geti("DOTMI_EARLY_BACKSOLVE", 2) != 0 ? 2 : 0;   // (1, round 3's per-step rule, now means "on")
         t.earlyAbort = geti("DOTMI_EARLY_ABORT", 1) != 0;
         t.earlyHold = geti("DOTMI_EARLY_HOLD", 1) != 0;

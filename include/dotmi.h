@@ -4,8 +4,8 @@
  * Drop-in boundary for the reference's DOT stepper: a host adapter with the reference's
  * `DOT::Optimizer<3>` surface (src/TimeStepper/Optimizer.hpp:83-112; picked by the factory in
  * src/main.cpp:905-938) forwards to these entry points.  Plain pointers and sizes only; caller
- * owns every host array; the handle owns all device memory, the rocBLAS handle and (N>1) the
- * RCCL communicator.  One host thread per handle.  No exceptions cross this boundary.
+ * owns every host array; the handle owns all device memory and (N>1) the RCCL communicator.
+ * One host thread per handle.  No exceptions cross this boundary.
  *
  * Return convention (mirrors Optimizer::solve, Optimizer.cpp:327-368):
  *   0  ok / stepped
@@ -29,7 +29,7 @@ extern "C" {
 #define DOTMI_ENERGY_SNH 1 /* StableNHEnergy     (src/Energy/Physics_Elasticity/StableNHEnergy.cpp)  */
 
 #define DOTMI_E_INVALID -1  /* bad argument */
-#define DOTMI_E_DEVICE -2   /* HIP / rocBLAS / RCCL runtime error */
+#define DOTMI_E_DEVICE -2   /* HIP / RCCL runtime error */
 #define DOTMI_E_NOTSPD -3   /* a subdomain Hessian was not positive definite (non-positive pivot);
                                the reference dumps the matrix and exit(-1)s, Optimizer.cpp:301-313 */
 #define DOTMI_E_NOGPU -4    /* no usable HIP device: the product path has no CPU fallback */
