@@ -258,7 +258,7 @@ int dotmi_probe_direction(dotmi_handle *h, const double *x, int32_t m, const dou
     // Gram matrix and the first half of the two-loop on the host (the running loop gets the same numbers from the
     // gather kernel's partial sums)
     L.m = m;
-    double b[HIST_MAX] = {0}, xi[HIST_MAX] = {0};
+    double b[HIST_MAX] = {0}, xi[HIST_MAX];
     auto dot = [&](const double *u, const double *v) {
         double acc = 0.0;
         for (int k = 0; k < n; ++k) acc += u[k] * v[k];
@@ -271,11 +271,7 @@ int dotmi_probe_direction(dotmi_handle *h, const double *x, int32_t m, const dou
         for (int j = 0; j < m; ++j) L.sy[i][j] = dot(S + (size_t)i * n, Y + (size_t)j * n);
         L.ys[i] = L.sy[i][i];
     }
-    for (int i = m - 1; i >= 0; --i) {
-        double sq = -b[i];
-        for (int j = m - 1; j > i; --j) sq -= xi[j] * L.sy[i][j];
-        xi[i] = sq / L.ys[i];
-    }
+    two_loop_xi(m, b, L.sy, L.ys, xi);
     launch_build_q(n, h->g_trial, L, xi, h->q, h->st);
     if (int rc = apply_precond(h, h->q, h->z, L)) return rc;
     launch_build_p(n, h->z, L, h->partC, xi, h->p, h->st);
@@ -589,23 +585,7 @@ int dotmi_bench_kernel(dotmi_handle *h, int32_t kind, int32_t reps, double *ms_p
         bytes = 112 * nTo + 56 * nVo + 48 * (int64_t)nV + 80 * (int64_t)nV + (int64_t)(6 + 2 * L.m) * 8 * n + 24 * held;
         live = true;
         run = [&] {
-            ElemVertArgs ea;
-            memset(&ea, 0, sizeof(ea));
-            ea.mass = h->M.mass;
-            ea.xt = h->xt;
-            ea.p = h->p;
-            ea.hp = h->Hp;
-            ea.spmv_partials = h->partST;
-            ea.fixed = h->M.fixed;
-            ea.vp_ptr = h->P.vp_ptr;
-            ea.vp_off = h->P.vp_off;
-            ea.rpad = h->P.rpad;
-            ea.partE = h->partE;
-            ea.partR = h->partR;
-            ea.alpha_out = h->alpha_dev;
-            ea.dtSq = h->dtSq;
-            ea.alpha_min = h->alphaMin;
-            launch_elem_vertex(h->VP, h->mat, ea, h->st, h->ctl);
+            launch_elem_vertex(h->VP, h->mat, elem_vertex_args(h), h->st, h->ctl);
         };
         break;
     }

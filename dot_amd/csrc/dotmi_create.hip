@@ -1211,7 +1211,7 @@ static int choose_loop_form(dotmi_handle *h)
     }
     h->devLoop = !h->gsdd && !h->newton && !h->pd && !(h->flags & (DOTMI_FLAG_HOST_LOOP | DOTMI_FLAG_TIME_PHASES));
     // replicated element pass, merged tile partials: the back-solve of the next direction is issued on the trial
-    // gradient, beside the controller (enqueue_loop_slot); sharded subdomains keep their one collective per iteration
+    // gradient, beside the controller (enqueue_loop_slot_early, dotmi_devloop.hip); sharded subdomains keep their one collective per iteration
     // (round 4: also with the sharded element pass -- the scatter of -g and H s_new then happen in pair_stats, behind the
     // gradient's all-reduce; DOTMI_EARLY_SHARDED=0 keeps the q-based order there)
     h->earlyBs = h->devLoop && h->tune.earlyBs != 0 &&

@@ -2,7 +2,8 @@
 //   dotmi_create.hip      setup: mesh features, the planning stages of block_plan.hpp with their uploads, buffers; host-only planners
 //   dotmi_refresh.hip     Hessian refresh + subdomain factorisation (issue / finish / asynchronous verdict)
 //   dotmi_collectives.hip all-reduce (RCCL or host hook) and the owner exchange's packets
-//   dotmi_loop.hip        the L-BFGS-H loop: slots of the device loop, host loop, GSDD, Newton, dotmi_step
+//   dotmi_loop.hip        dotmi_step, what the loop drivers share (trial, line search, block solve), host loop, GSDD, Newton
+//   dotmi_devloop.hip     the device-resident L-BFGS-H loop: the stages of a slot in both orders, run_device_loop and its parts
 //   dotmi_api.hip         the remaining ABI entry points (state, kernel-level calls, probes, measurement)
 //
 // Control flow mirrors (paths relative to /root/reference/src)
@@ -105,7 +106,7 @@ struct Tuning {
     bool earlyHold = true;    // DOTMI_EARLY_HOLD=0   the back-solve of a trial that is expected to be rejected still starts speculatively
     int earlyBs = 2;          // DOTMI_EARLY_BACKSOLVE 0: the back-solve after the controller, on q; 1: speculatively on the trial
                               //                      gradient with the controller inside its launch, in the steps where
-                              //                      the last step's counts say it pays (run_device_loop); 2 (default): in
+                              //                      the last step's counts say it pays (choose_step_forms); 2 (default): in
                               //                      every step
     static int geti(const char *name, int dflt)
     {
@@ -239,7 +240,7 @@ struct dotmi_handle {
     double *g = nullptr, *g_trial = nullptr, *p = nullptr, *q = nullptr, *z = nullptr, *Hp = nullptr;
     double *He = nullptr, *Hval = nullptr, *tmpn = nullptr;
     double *S[HIST_MAX + 1] = {nullptr}, *Y[HIST_MAX + 1] = {nullptr};
-    // early back-solve (enqueue_loop_slot): u = -M g of the current iterate, M y_i of the stored pairs (slots as Y)
+    // early back-solve (enqueue_loop_slot_early): u = -M g of the current iterate, M y_i of the stored pairs (slots as Y)
     bool refreshPending = false;   // DOTMI_FLAG_ASYNC_REFRESH: the last step's refresh is enqueued, not yet judged / timed
     double carryHess = 0, carryFact = 0;   // device times of a refresh resolved outside dotmi_step (reported by the next step)
     bool earlyBs = false;     // possible on this handle (buffers exist)
@@ -407,8 +408,24 @@ int exchange_iface(dotmi_handle *h, double *vec, double *tailp, int ntail);
 int exchange_gradient_packed(dotmi_handle *h, int n, int nbE, const double *partials, int ncols);
 int exchange_solve_packed(dotmi_handle *h);
 // dotmi_loop.hip
+struct Bracket {
+    hipEvent_t ev0, ev1;   // DOTMI_FLAG_TIME_BACKSOLVE: the events around a sampled back-solve, else nulls
+    int at;                // index of the pair in evPre, or -1
+};
+struct LoopOut {           // what a loop driver (run_*_loop) hands back to dotmi_step
+    double lastE = 0, g2 = 0, E0 = 0, g20 = 0;   // energy and |g|^2 of the last iterate / at the start of the step
+    int it = 0;
+    bool failed = false;   // the line search ran out of step length
+};
 int apply_precond(dotmi_handle *h, const double *q, double *z, const LbfgsArgs &L);
-int enqueue_loop_slot(dotmi_handle *h);
+Bracket backsolve_bracket(dotmi_handle *h);
+int reduce_step_dots(dotmi_handle *h, const double **spart);
+void stage_energy(dotmi_handle *h, int nb, double *dst);
+GatherArgs gather_args(const dotmi_handle *h);
+ElemVertArgs elem_vertex_args(const dotmi_handle *h);
+void two_loop_xi(int m, const double *b, const double (*sy)[HIST_MAX], const double *ys, double *xi);
+// dotmi_devloop.hip
+int run_device_loop(dotmi_handle *h, LoopOut &r);
 
 }  // namespace dotmi
 

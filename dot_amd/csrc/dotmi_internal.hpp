@@ -231,7 +231,7 @@ struct XiArgs {
 };
 
 // L-BFGS loop state resident in HBM (single-GPU path).  loop_control_kernel advances it after every
-// line-search trial exactly as the host loop of dotmi_step would, and the loop kernels take their
+// line-search trial exactly as the host loop (run_host_loop) would, and the loop kernels take their
 // operands from it, so the host can enqueue iterations ahead of the device instead of synchronising
 // once per trial (that round trip was ~30 us of every ~180 us iteration on bar17K).
 struct DevLoop {
@@ -254,7 +254,7 @@ struct DevLoop {
     double *log_alpha, *log_E, *log_g2;
     int *slot_kind;        // per slot: 1 new direction, 2 retry (slots after the end are not logged)
     int logCap, kindCap;
-    // early back-solve (enqueue_loop_slot): u = -M g of the accepted iterate and M y_i of the stored pairs (same slots as Y)
+    // early back-solve (enqueue_loop_slot_early): u = -M g of the accepted iterate and M y_i of the stored pairs (same slots as Y)
     int pairNew;           // the controller's last accept stored a pair (its M y goes to MY[order[m - 1]])
     int abortEpoch;        // `slots` value of the last slot whose trial was rejected or that ended the loop: the speculative
                            // back-solve of that slot (which knows its epoch) stops when it sees it
