@@ -86,7 +86,7 @@ double host_target_gres(const dotmi_handle *h)
 }
 
 // vertex patches (vpatches.hpp) -> device
-int upload_vpatches(dotmi_handle *h, const HostVPatches &H, DevVPatches &D)
+int upload_vpatches(dotmi_handle *h, const HostVPatches &H, DevVPatches &D, dotmi_handle::SlotMap &SM)
 {
     D.nPatches = H.nPatches;
     D.PE = H.PE;
@@ -122,6 +122,11 @@ int upload_vpatches(dotmi_handle *h, const HostVPatches &H, DevVPatches &D)
         if (int rc = upload(h, &D.mu, mu)) return rc;
         if (int rc = upload(h, &D.lam, lam)) return rc;
     }
+    // the slot -> element table stays on the device: dotmi_set_lame fills the slot arrays through it (k_reconfig.hip)
+    if (int rc = upload(h, &SM.elem, H.elem)) return rc;
+    SM.nSlots = ns;
+    SM.mu = D.mu;
+    SM.lam = D.lam;
     if (int rc = upload(h, &D.vol, vol)) return rc;
     if (int rc = upload(h, &D.volE, volE)) return rc;
     if (int rc = upload(h, &D.pv_gid, H.pv_gid)) return rc;
@@ -132,7 +137,7 @@ int upload_vpatches(dotmi_handle *h, const HostVPatches &H, DevVPatches &D)
 }
 
 // patch lists + the element operands in patch order -> device
-int upload_patches(dotmi_handle *h, const HostPatches &H, DevPatches &D)
+int upload_patches(dotmi_handle *h, const HostPatches &H, DevPatches &D, dotmi_handle::SlotMap &SM)
 {
     D.nPatches = H.nPatches;
     D.PE = H.PE;
@@ -166,6 +171,11 @@ int upload_patches(dotmi_handle *h, const HostPatches &H, DevPatches &D)
         if (int rc = upload(h, &D.mu, mu)) return rc;
         if (int rc = upload(h, &D.lam, lam)) return rc;
     }
+    // the slot -> element table stays on the device: dotmi_set_lame fills the slot arrays through it (k_reconfig.hip)
+    if (int rc = upload(h, &SM.elem, H.elem)) return rc;
+    SM.nSlots = ns;
+    SM.mu = D.mu;
+    SM.lam = D.lam;
     if (int rc = upload(h, &D.vol, vol)) return rc;
     if (int rc = upload(h, &D.pv_gid, H.pv_gid)) return rc;
     if (int rc = upload(h, &D.pv_slot, H.pv_slot)) return rc;
@@ -258,12 +268,12 @@ static int build_element_side(dotmi_handle *h, const std::vector<int> &adj_ptr, 
         int PE = h->tune.patchElems > 0 ? (h->tune.patchElems <= 256 ? 256 : 512) : 256;
         std::vector<int> all(nT);
         for (int e = 0; e < nT; ++e) all[e] = e;
-        if (int rc = upload_patches(h, build_patches(nV, h->T.data(), h->Xrest.data(), all, PE), h->PTall)) return rc;
+        if (int rc = upload_patches(h, build_patches(nV, h->T.data(), h->Xrest.data(), all, PE), h->PTall, h->smAll)) return rc;
         if (h->shardElems) {
             std::vector<int> own;
             for (int e = 0; e < nT; ++e)
                 if (h->epart[e] >= h->p0 && h->epart[e] < h->p1) own.push_back(e);
-            if (int rc = upload_patches(h, build_patches(nV, h->T.data(), h->Xrest.data(), own, PE), h->PT)) return rc;
+            if (int rc = upload_patches(h, build_patches(nV, h->T.data(), h->Xrest.data(), own, PE), h->PT, h->smOwn)) return rc;
         } else {
             h->PT = h->PTall;
         }
@@ -278,7 +288,7 @@ static int build_element_side(dotmi_handle *h, const std::vector<int> &adj_ptr, 
             } else if (h->tune.patchElems == 0 && PE == 256) {
                 const HostPatches H2 = build_patches(nV, h->T.data(), h->Xrest.data(), all, 512);
                 if (std::max(H2.nPatches, nbv) <= room) {
-                    if (int rc = upload_patches(h, H2, h->PTspec)) return rc;
+                    if (int rc = upload_patches(h, H2, h->PTspec, h->smSpec)) return rc;
                     h->specFits = true;
                 }
             }
@@ -1235,7 +1245,7 @@ static int choose_loop_form(dotmi_handle *h)
         const HostVPatches HV = build_vpatches(h->nV, h->nT, h->T.data(), h->Xrest.data(), 512, 85);
         const size_t shm = sizeof(double) * ((size_t)3 * HV.PV + (size_t)3 * HV.RUN) + 2 * (size_t)((HV.PO + 1 + 3) & ~3);
         if (HV.nPatches > 0 && HV.nPatches <= 512 && HV.nPatches <= ELEM_NB_MAX && shm <= 64 * 1024 && HV.PO + 1 <= 256) {
-            if (int rc = upload_vpatches(h, HV, h->VP)) return rc;
+            if (int rc = upload_vpatches(h, HV, h->VP, h->smVP)) return rc;
             h->vpFits = true;
             if (h->tune.fuseLog)
                 fprintf(stderr, "dotmi: vertex patches: %d patches, %.2f x the elements, up to %d owned / %d touched vertices, runs %d, %zu B LDS\n",

@@ -4,6 +4,7 @@
 //   dotmi_collectives.hip all-reduce (RCCL or host hook) and the owner exchange's packets
 //   dotmi_loop.hip        dotmi_step, what the loop drivers share (trial, line search, block solve), host loop, GSDD, Newton
 //   dotmi_devloop.hip     the device-resident L-BFGS-H loop: the stages of a slot in both orders, run_device_loop and its parts
+//   dotmi_reconfig.hip    tolerance, time step and materials changed on a live handle (dotmi_set_rel_tol / _time_step / _lame)
 //   dotmi_api.hip         the remaining ABI entry points (state, kernel-level calls, probes, measurement)
 //
 // Control flow mirrors (paths relative to /root/reference/src)
@@ -235,6 +236,15 @@ struct dotmi_handle {
     // pairs or speculates keeps the element patches -- one patch set per step, so its energies are grouped alike)
     DevVPatches VP;
     bool vpFits = false, vpNow = false;
+    // dotmi_set_lame: per family of patches the slot -> element table (-1: padding) that upload_patches / upload_vpatches fill the
+    // per-slot Lame parameters through, kept on the device, and the family's slot arrays (null until a field that is not one
+    // material needs them; then kept).  PT and PTspec are entered only where they are patch sets of their own.
+    struct SlotMap {
+        int *elem = nullptr;
+        size_t nSlots = 0;
+        double *mu = nullptr, *lam = nullptr;
+    };
+    SlotMap smAll, smOwn, smSpec, smVP;
     int nOwnElem = 0, v0 = 0, v1 = 0;
     double *x = nullptr, *x_trial = nullptr, *xn = nullptr, *v = nullptr, *xt = nullptr;
     double *g = nullptr, *g_trial = nullptr, *p = nullptr, *q = nullptr, *z = nullptr, *Hp = nullptr;
@@ -388,6 +398,7 @@ int upload(dotmi_handle *h, T **ptr, const std::vector<T> &v)
 // ---- shared between the translation units --------------------------------------------------------------------------
 // dotmi_create.hip
 int build_device_mesh(dotmi_handle *h);
+double host_target_gres(const dotmi_handle *h);
 LbfgsArgs lbfgs_args(const dotmi_handle *h);
 int free_slot(const dotmi_handle *h);
 // dotmi_refresh.hip

@@ -511,5 +511,12 @@ void launch_copy(int n, const double *src, double *dst, hipStream_t st);
 // sharded subdomains, after the all-reduce of the merged sums: z_v /= dup_v and the y_i . z partials
 void launch_zfinish(int nV, const int *dup, const LbfgsArgs &L, double *z, double *partials, hipStream_t st,
                     const DevLoop *ctl = nullptr);
+// k_reconfig.hip (dotmi_set_lame / dotmi_set_time_step): the per-slot Lame parameters of a patch family from the global
+// per-element arrays through the family's slot -> element table (padding slots, -1, get the neutral 1.0 that create gives them)
+void launch_gather_lame(const int *slotElem, size_t nSlots, const double *mu, const double *lam, double *mu_s, double *lam_s,
+                        hipStream_t st);
+// x~ = x_n + dt v + dt^2 g on free vertices, x_n on fixed ones (Optimizer::computeXTilta, Optimizer.cpp:585-610), from the resident state
+void launch_x_tilde(int nV, const uint8_t *fixed, const double *xn, const double *v, double dt, const double *gdtsq, double *xt,
+                    hipStream_t st);
 
 }  // namespace dotmi

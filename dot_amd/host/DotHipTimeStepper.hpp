@@ -6,13 +6,14 @@
 //   reference member            here
 //   ------------------------    -----------------------------------------------------------------
 //   Optimizer(mesh, energy,..)  DotHipTimeStepper(MeshView, Options)          (arrays are copied by the ABI)
-//   setTime(duration, dt)       setTime                                       (before precompute)
+//   setTime(duration, dt)       setTime               -> dotmi_set_time_step  once built (x~, tolerance, factors at the current x)
 //   precompute()                precompute            -> dotmi_create         (DOTTimeStepper.cpp:150-178)
-//   setRelGL2Tol(tol)           setRelGL2Tol                                  (before precompute)
+//   setRelGL2Tol(tol)           setRelGL2Tol          -> dotmi_set_rel_tol    once built (main.cpp:108-118 calls it per time step)
 //   solve(maxIter)              solve                 -> script move + dotmi_step, same 0/1/2 codes
 //   getResult().V               getResult             -> dotmi_get_state
 //   getIterNum/getInnerIterAmt  same
 //   updatePrecondMtrAndFactorize same                 -> dotmi_refactor / dotmi_refix
+//   (mesh.u / mesh.lambda)      setLameParam(u, lambda) -> dotmi_set_lame     a material change on the built stepper (nT each)
 //   saveStatus()                saveStatus(path)      -> status<n> text format (Optimizer.cpp:1096-1132)
 #pragma once
 #include <cstdint>
@@ -69,14 +70,20 @@ public:
 
     void setTime(double duration, double dt)  // Optimizer.cpp:249-257
     {
-        require_not_built("setTime");
+        if (h_ && dt != dt_) check(dotmi_set_time_step(h_, dt), "set_time_step");
         dt_ = dt;
         frameAmt_ = (int)(duration / dt);
     }
     void setRelGL2Tol(double relTol = 1.0e-5)  // Optimizer.cpp:222-228 (squares its argument internally)
     {
-        if (h_ && relTol != relTol_) throw std::logic_error("setRelGL2Tol after precompute: rebuild the stepper");
+        if (h_ && relTol != relTol_) check(dotmi_set_rel_tol(h_, relTol), "set_rel_tol");
         relTol_ = relTol;
+    }
+    // Mesh::u / Mesh::lambda changed (nT each).  Before precompute the arrays of MeshView are what create reads: change those
+    void setLameParam(const double *u, const double *lambda)
+    {
+        require_built("setLameParam");
+        check(dotmi_set_lame(h_, u, lambda), "set_lame");
     }
     void setAllowEDecRelTol(bool) {}  // main.cpp:942 switches it off; this path never uses it
     void setScript(Script s) { script_ = std::move(s); }

@@ -17,6 +17,7 @@
 //                [--frames K] [--out DIR] [--device D] [--no-files] [--dump-scene K] [--dump-config] [--dump-formats DIR]
 //                [--echo-config FILE] [--fast]
 //        dot_hip --write-info FILE nV nT steps iters t0..t21
+#include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <iostream>
@@ -247,6 +248,8 @@ int main(int argc, char **argv)
         double tStep = 0;
         std::vector<double> al(10001), En(10001), g2(10001);
         for (int n = firstFrame; n < nFrames; ++n) {
+            // the script's tolerance schedule: entry n, beyond the list's end its last one (main.cpp:108-118)
+            if (!cfg.tol.empty()) ts.setRelGL2Tol(cfg.tol[std::min((size_t)n, cfg.tol.size() - 1)]);
             if (files) {
                 char buf[512];
                 std::snprintf(buf, sizeof(buf), "%s/status%d", outDir.c_str(), n);

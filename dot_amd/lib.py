@@ -75,6 +75,7 @@ EXPORTS = [
     "dotmi_refactor", "dotmi_apply_precond", "dotmi_spmv", "dotmi_get_features", "dotmi_part_size", "dotmi_padded_size",
     "dotmi_part_matrix", "dotmi_factor_storage_bytes", "dotmi_factor_kind", "dotmi_backsolve_form", "dotmi_plan_backsolve_form", "dotmi_probe_direction", "dotmi_bench_precond", "dotmi_bench_energy", "dotmi_bench_kernel", "dotmi_plan_shards", "dotmi_plan_layout", "dotmi_plan_tile_schedule", "dotmi_plan_tile_schedule_two_level", "dotmi_plan_tile_deps", "dotmi_plan_backsolve_tiles", "dotmi_plan_patches", "dotmi_plan_vpatches", "dotmi_plan_rank", "dotmi_partition",
     "dotmi_plan_pd",
+    "dotmi_set_rel_tol", "dotmi_set_time_step", "dotmi_set_lame",
 ]
 
 _lib = None
@@ -107,6 +108,9 @@ def load() -> C.CDLL:
     L.dotmi_get_state.argtypes = [H, c_dp, c_dp, c_dp]
     L.dotmi_set_dirichlet.argtypes = [H, C.c_int32, c_ip, c_dp]
     L.dotmi_refix.argtypes = [H, c_up]
+    L.dotmi_set_rel_tol.argtypes = [H, C.c_double]
+    L.dotmi_set_time_step.argtypes = [H, C.c_double]
+    L.dotmi_set_lame.argtypes = [H, c_dp, c_dp]
     L.dotmi_step.argtypes = [H, C.POINTER(StepStats)]
     L.dotmi_last_iter_log.argtypes = [H, C.c_int32, c_dp, c_dp, c_dp]
     L.dotmi_target_gres.argtypes = [H]

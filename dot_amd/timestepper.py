@@ -17,6 +17,14 @@ from .lib import DotmiError, Mesh, Params, StepStats, dp, ip, up
 from .scene import Scene, lame
 
 
+def tol_for_step(tol, k: int, default: float) -> float:
+    """The relative tolerance of time step k under a script's `tol` list (src/main.cpp:108-118): entry k, beyond the list's
+    end its last entry; without a list the stepper's own value."""
+    if not tol:
+        return default
+    return tol[k] if k < len(tol) else tol[-1]
+
+
 class DOTTimeStepper:
     def __init__(self, scene: Scene, epart: np.ndarray, nparts: int, energy: Optional[int] = None,
                  device: int = 0, rank: int = 0, world: int = 1, comm_id: Optional[bytes] = None,
@@ -33,6 +41,7 @@ class DOTTimeStepper:
         self.scene = scene
         self.nV, self.nT = scene.V_rest.shape[0], scene.T.shape[0]
         self.dt = cfg.dt
+        self.rel_tol = rel_tol
         self.frameAmt = int(cfg.duration / cfg.dt)  # Optimizer::setTime, Optimizer.cpp:249-257
         self.globalIterNum = 0
         self.innerIterAmt = 0
@@ -90,6 +99,8 @@ class DOTTimeStepper:
         self.last_stats: Optional[StepStats] = None
 
     def _per_element(self, a, const, name):
+        if a is None and const is None:
+            raise ValueError(f"{name} must be given")
         if a is None:
             return np.full(self.nT, const, dtype=np.float64)
         a = np.array(a, dtype=np.float64)   # a private copy, kept alive with the handle
@@ -156,6 +167,25 @@ class DOTTimeStepper:
         self._fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
         self._check(self._L.dotmi_refix(self._h, up(self._fixed)), "refix")
 
+    # ---- tolerance, time step and materials of the live handle (include/dotmi.h) -----------------
+    def setRelGL2Tol(self, relTol: float = 1e-5):
+        """Optimizer::setRelGL2Tol (Optimizer.cpp:222-228): the next step's tolerance"""
+        self._check(self._L.dotmi_set_rel_tol(self._h, relTol), "set_rel_tol")
+        self.rel_tol = relTol
+
+    def setTime(self, duration: float, dt: float):
+        """Optimizer::setTime (Optimizer.cpp:249-257): dt with x~, the tolerance and the factors built with it; frameAmt"""
+        self._check(self._L.dotmi_set_time_step(self._h, dt), "set_time_step")
+        self.dt = dt
+        self.frameAmt = int(duration / dt)
+
+    def setLame(self, mu, lam):
+        """per-element Lame parameters, shape (nT,) each (dotmi_set_lame); the factors are refreshed at the current positions"""
+        mu = self._per_element(mu, None, "mu")
+        lam = self._per_element(lam, None, "lam")
+        self._check(self._L.dotmi_set_lame(self._h, dp(mu), dp(lam)), "set_lame")
+        self._mu, self._lam = mu, lam
+
     def solve(self, maxIter: int = 1) -> int:
         """Optimizer::solve (Optimizer.cpp:327-368): script move, one BE step. 0 stepped, 1 all frames
         done, 2 stepped but hit the iteration cap / line-search failure."""
@@ -170,6 +200,11 @@ class DOTTimeStepper:
             if self.globalIterNum >= self.frameAmt:
                 self.globalIterNum += 1
                 return 1
+            tol = self.scene.cfg.tol
+            if tol:                                        # the script's tolerance schedule (main.cpp:108-118)
+                t = tol_for_step(tol, self.globalIterNum, self.rel_tol)
+                if t != self.rel_tol:
+                    self.setRelGL2Tol(t)
             st = self.step()
             if st.status == 2:
                 flag = 2

@@ -301,6 +301,22 @@ int dotmi_set_dirichlet(dotmi_handle *h, int32_t n, const int32_t *idx, const do
  * (DOTTimeStepper::updatePrecondMtrAndFactorize, DOTTimeStepper.cpp:185-270) */
 int dotmi_refix(dotmi_handle *h, const uint8_t *fixed);
 
+/* ---- tolerance, time step and materials of a live handle --------------------------------------- */
+/* Called between steps.  After any of them the handle is the one dotmi_create would have built from the new value, brought to
+ * the same state with dotmi_set_state(x, v, x_n) and dotmi_refactor(h, NULL) -- without the planning create repeats (partition
+ * tables, dissection layout, tile schedules, patches depend on none of the three).  A refresh a step left running
+ * (DOTMI_FLAG_ASYNC_REFRESH) is judged first: its verdict, if it has one, is returned and nothing is changed.  A bad argument
+ * (NULL, non-finite, relTol <= 0, dt <= 0, any mu[e] <= 0 or lambda[e] <= 0) returns DOTMI_E_INVALID and changes nothing.  On a
+ * sharded handle every rank calls them in the same order with the same values, like dotmi_refix: the refresh ends in a collective. */
+/* the next step's tolerance (main.cpp:108-118 sets it per time step from the script's `tol` list); no device work */
+int dotmi_set_rel_tol(dotmi_handle *h, double relTol);                           /* Optimizer::setRelGL2Tol, Optimizer.cpp:222-228 */
+/* dt, dt^2, gravity dt^2, the tolerance, x~ from the handle's x_n and v (on the device), then what was built with dt: the Hessian
+ * and subdomain factors at the current x (LBFGS-PD: L and its factor).  Returns the refresh's code (DOTMI_E_NOTSPD) */
+int dotmi_set_time_step(dotmi_handle *h, double dt);                             /* Optimizer::setTime, Optimizer.cpp:249-257 */
+/* per-element Lame parameters: the tolerance from element 0, the field in front of every form of the element pass (one material
+ * everywhere: as two kernel arguments, like create), then the refresh as above and its return code */
+int dotmi_set_lame(dotmi_handle *h, const double *mu, const double *lambda);     /* nT each; dor_set_lame */
+
 /* ---- the hot path ----------------------------------------------------------------------------- */
 /* One backward-Euler step = Optimizer::solve(1) minus the script move:
  * DOTTimeStepper::fullyImplicit (DOTTimeStepper.cpp:273-346) + BE update (Optimizer.cpp:354-361). */
