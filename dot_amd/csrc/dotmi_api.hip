@@ -207,6 +207,8 @@ int dotmi_apply_precond(dotmi_handle *h, const double *r, double *p)
     memset(&L, 0, sizeof(L));
     if (h->pd) {
         if (int rc = pd_apply(h, h->q, h->z, L)) return rc;
+    } else if (h->hi) {
+        if (int rc = ic_apply(h, h->q, h->z, L)) return rc;
     } else if (int rc = apply_precond(h, h->q, h->z, L)) return rc;
     HIPCHECK(h, hipMemcpyAsync(p, h->z, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->st));
     HIPCHECK(h, hipStreamSynchronize(h->st));
@@ -223,6 +225,10 @@ int dotmi_probe_direction(dotmi_handle *h, const double *x, int32_t m, const dou
     if (!h || !x || m < 0 || m > h->hist || (m > 0 && (!S || !Y))) return DOTMI_E_INVALID;
     if (h->pd) {
         h->err = "dotmi_probe_direction: an LBFGS-PD handle has no Hessian block solve";
+        return DOTMI_E_INVALID;
+    }
+    if (h->hi) {
+        h->err = "dotmi_probe_direction: an LBFGS-HI handle has no Hessian block solve";
         return DOTMI_E_INVALID;
     }
     if (h->dist) {
@@ -325,7 +331,7 @@ int dotmi_get_features(dotmi_handle *h, double *A, double *vol, double *mass)
 
 int32_t dotmi_part_size(const dotmi_handle *h, int32_t part)
 {
-    if (!h || h->pd || part < 0 || part >= h->nPartsAll) return DOTMI_E_INVALID;
+    if (!h || h->pd || h->hi || part < 0 || part >= h->nPartsAll) return DOTMI_E_INVALID;
     return 3 * (int32_t)h->partVerts[part].size();
 }
 
@@ -335,6 +341,10 @@ int64_t dotmi_factor_storage_bytes(const dotmi_handle *h) { return h ? (int64_t)
 
 int dotmi_part_matrix(dotmi_handle *h, int32_t part, int inverse, double *Mout, int32_t *l2g)
 {
+    if (h && h->hi) {   // (no subdomains at all: said before the range test of `part`)
+        h->err = "dotmi_part_matrix: an LBFGS-HI handle has no Hessian block solve";
+        return DOTMI_E_INVALID;
+    }
     if (!h || part < h->p0 || part >= h->p1 || !Mout) return DOTMI_E_INVALID;
     if (h->pd) {
         h->err = "dotmi_part_matrix: an LBFGS-PD handle has no Hessian block solve";
@@ -414,6 +424,10 @@ int dotmi_part_matrix(dotmi_handle *h, int32_t part, int inverse, double *Mout, 
 int dotmi_bench_precond(dotmi_handle *h, int32_t reps, double *ms_per_launch, int64_t *bytes_per_launch)
 {
     if (!h || reps < 1) return DOTMI_E_INVALID;
+    if (h->hi) {
+        h->err = "dotmi_bench_precond: an LBFGS-HI handle has no Hessian block solve";
+        return DOTMI_E_INVALID;
+    }
     HIPCHECK(h, hipSetDevice(h->device));
     if (int rc = enter_with_factors(h)) return rc;
     // (LBFGS-PD: the apply of L^-1 on the three columns of q, merge included)
@@ -441,6 +455,25 @@ int dotmi_bench_kernel(dotmi_handle *h, int32_t kind, int32_t reps, double *ms_p
     if (h->pd) {
         h->err = "dotmi_bench_kernel: an LBFGS-PD handle has no Hessian block solve";
         return DOTMI_E_INVALID;
+    }
+    // LBFGS-HI keeps the kinds that run on the element pass, the vectors and H; the kinds of the block solve and of the device
+    // loop's early order (which reads the padded right-hand sides) are refused by name, so a kind added later is not caught here
+    if (h->hi) {
+        switch (kind) {
+        case DOTMI_BENCH_BACKSOLVE:
+        case DOTMI_BENCH_MERGE:
+        case DOTMI_BENCH_BUILD_QPAD:
+        case DOTMI_BENCH_SPMV_ZP:
+        case DOTMI_BENCH_MERGE_EARLY:
+        case DOTMI_BENCH_ELEM_STEP:
+        case DOTMI_BENCH_GATHER_EARLY:
+        case DOTMI_BENCH_DIRSTEP:
+        case DOTMI_BENCH_ELEM_VERTEX:
+            h->err = "dotmi_bench_kernel: an LBFGS-HI handle has no Hessian block solve";
+            return DOTMI_E_INVALID;
+        default:
+            break;
+        }
     }
     HIPCHECK(h, hipSetDevice(h->device));
     if (int rc = enter_with_factors(h)) return rc;

@@ -611,6 +611,10 @@ int build_device_mesh(dotmi_handle *h)
         if (int rc = build_pd(h, G.adj_ptr, G.adj_idx)) return rc;
         return build_element_side(h, G.adj_ptr, blk_ptr, blk_ent);
     }
+    if (h->hi) {   // LBFGS-HI: the block incomplete Cholesky of H on its own block pattern, no subdomains either (dotmi_ic.hip)
+        if (int rc = build_ic(h, G.adj_ptr, G.adj_idx)) return rc;
+        return build_element_side(h, G.adj_ptr, blk_ptr, blk_ent);
+    }
     choose_subdomains(h);
     const std::vector<std::vector<int>> &sets = h->partVerts;
     const Tuning &tune = h->tune;
@@ -1172,7 +1176,18 @@ static int take_arguments(dotmi_handle *h, const dotmi_mesh *mesh, const dotmi_p
     h->nPartsAll = mesh->nParts;
     h->T.assign(mesh->T, mesh->T + 4 * (size_t)h->nT);
     h->pd = (h->flags & DOTMI_FLAG_LBFGS_PD) != 0;
-    if (h->pd) {
+    h->hi = (h->flags & DOTMI_FLAG_LBFGS_HI) != 0;
+    if (h->hi) {
+        const int bad = DOTMI_FLAG_FORCE_DIST | DOTMI_FLAG_OWNER_EXCHANGE | DOTMI_FLAG_GSDD | DOTMI_FLAG_NEWTON | DOTMI_FLAG_LBFGS_PD |
+                        DOTMI_FLAG_ASYNC_REFRESH;
+        if (prm->world > 1 || (h->flags & bad) || mesh->vpart) {
+            h->err = "DOTMI_FLAG_LBFGS_HI: single GPU, host loop, not with DOTMI_FLAG_FORCE_DIST / OWNER_EXCHANGE / GSDD / NEWTON / "
+                     "LBFGS_PD / ASYNC_REFRESH or a vertex partition";
+            return DOTMI_E_INVALID;
+        }
+        h->nPartsAll = 1;
+        h->epart.assign(h->nT, 0);   // (unused: no subdomains)
+    } else if (h->pd) {
         const int bad = DOTMI_FLAG_FORCE_DIST | DOTMI_FLAG_OWNER_EXCHANGE | DOTMI_FLAG_GSDD | DOTMI_FLAG_NEWTON | DOTMI_FLAG_ASYNC_REFRESH;
         if (prm->world > 1 || (h->flags & bad) || mesh->vpart) {
             h->err = "DOTMI_FLAG_LBFGS_PD: single GPU, host loop, not with DOTMI_FLAG_FORCE_DIST / OWNER_EXCHANGE / GSDD / NEWTON / "
@@ -1219,7 +1234,7 @@ static int choose_loop_form(dotmi_handle *h)
         h->err = "DOTMI_FLAG_GSDD: single GPU only";
         return DOTMI_E_INVALID;
     }
-    h->devLoop = !h->gsdd && !h->newton && !h->pd && !(h->flags & (DOTMI_FLAG_HOST_LOOP | DOTMI_FLAG_TIME_PHASES));
+    h->devLoop = !h->gsdd && !h->newton && !h->pd && !h->hi && !(h->flags & (DOTMI_FLAG_HOST_LOOP | DOTMI_FLAG_TIME_PHASES));
     // replicated element pass, merged tile partials: the back-solve of the next direction is issued on the trial
     // gradient, beside the controller (enqueue_loop_slot_early, dotmi_devloop.hip); sharded subdomains keep their one collective per iteration
     // (round 4: also with the sharded element pass -- the scatter of -g and H s_new then happen in pair_stats, behind the
@@ -1396,7 +1411,7 @@ static int create_impl(dotmi_handle *h, const dotmi_mesh *mesh, const dotmi_para
     HIPCHECK(h, hipStreamSynchronize(h->st));
     // LBFGS-PD: the Laplacian's factor (LBFGSTimeStepper::precompute, :113-194); the Hessian is never assembled
     if (h->pd) return pd_factor(h);
-    // DOTTimeStepper::precompute (DOTTimeStepper.cpp:150-178)
+    // DOTTimeStepper::precompute (DOTTimeStepper.cpp:150-178); an LBFGS-HI handle's refactor is H and its incomplete factor
     return refactor(h, h->x, nullptr, nullptr);
 }
 

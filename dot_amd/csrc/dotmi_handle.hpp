@@ -5,6 +5,7 @@
 //   dotmi_loop.hip        dotmi_step, what the loop drivers share (trial, line search, block solve), host loop, GSDD, Newton
 //   dotmi_devloop.hip     the device-resident L-BFGS-H loop: the stages of a slot in both orders, run_device_loop and its parts
 //   dotmi_reconfig.hip    tolerance, time step and materials changed on a live handle (dotmi_set_rel_tol / _time_step / _lame)
+//   dotmi_pd.hip / dotmi_ic.hip   the preconditioners of LBFGS-PD (scalar Laplacian) and LBFGS-HI (block incomplete Cholesky of H)
 //   dotmi_api.hip         the remaining ABI entry points (state, kernel-level calls, probes, measurement)
 //
 // Control flow mirrors (paths relative to /root/reference/src)
@@ -307,6 +308,14 @@ struct dotmi_handle {
     bool newton = false; // DOTMI_FLAG_NEWTON
     bool pd = false;     // DOTMI_FLAG_LBFGS_PD: no subdomain block solve; the scalar factor of L below instead (dotmi_pd.hip)
     DevPD PD;
+    // DOTMI_FLAG_LBFGS_HI: no subdomain block solve either; the block incomplete Cholesky factor of H below instead (dotmi_ic.hip),
+    // rebuilt by every refresh.  icShift: the diagonal shift of the last successful factorisation (the next one starts from half
+    // of it); icAttempts: the attempts that one took
+    bool hi = false;
+    DevIC IC;
+    std::vector<int> icStart;   // nColours + 1: the order positions of every colour
+    double icShift = 0.0;
+    int icAttempts = 0;
     bool devLoop = false;
     DevLoop *ctl = nullptr, *h_ctl = nullptr;  // device / pinned staging
     int *h_flags = nullptr;                    // pinned: {status, slots done}, written by the controller
@@ -412,6 +421,10 @@ int run_factor(dotmi_handle *h);
 int build_pd(dotmi_handle *h, const std::vector<int> &adj_ptr, const std::vector<int> &adj_idx);
 int pd_factor(dotmi_handle *h);
 int pd_apply(dotmi_handle *h, const double *q, double *z, const LbfgsArgs &L);
+// dotmi_ic.hip (LBFGS-HI)
+int build_ic(dotmi_handle *h, const std::vector<int> &adj_ptr, const std::vector<int> &adj_idx);
+int ic_refresh(dotmi_handle *h, const double *x, double *ms_hess, double *ms_fact);
+int ic_apply(dotmi_handle *h, const double *q, double *z, const LbfgsArgs &L);
 // dotmi_collectives.hip
 int allreduce_sum(dotmi_handle *h, double *dev, size_t n);
 int adopt_rank0(dotmi_handle *h, double *vals, int n);

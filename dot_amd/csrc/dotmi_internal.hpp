@@ -196,6 +196,19 @@ struct DevPD {
     long long *ment = nullptr;
 };
 
+// ---- LBFGS-HI (DOTMI_FLAG_LBFGS_HI, dotmi_ic.hip / k_ic.hip): block IC(0) of H in the multicolour ordering of ic_plan.hpp -----------
+struct DevIC {
+    int nV = 0, nL = 0;             // vertices; lower blocks (edges of the vertex graph)
+    int *vert = nullptr;            // nV: order position -> vertex
+    int *lptr = nullptr, *lidx = nullptr;   // per position: its lower blocks' column positions, ascending
+    int *lsrc = nullptr, *dsrc = nullptr;   // block of Hval behind a lower block / behind a position's diagonal
+    int *pptr = nullptr, *pa = nullptr, *pb = nullptr;   // per lower block: the products L[pa] L[pb]^T, ascending position of k
+    int *uptr = nullptr, *ublk = nullptr, *uvert = nullptr;   // per position: the later rows' blocks in its column / those rows' vertices
+    double *F = nullptr;            // the factor: nL lower blocks (plan order), then nV lower-triangular diagonals (order position), row-major
+    double *yw = nullptr;           // 3 nV: the forward sweep's result in order position
+    int *flag = nullptr;            // set by a non-positive pivot
+};
+
 constexpr int MT_PAD = -2147483647 - 1;   // end of a dof's interleaved list (no offset, plain or complemented, has this value)
 
 struct LbfgsArgs {
@@ -501,6 +514,12 @@ void launch_clear_tiles(double *const *tiles, const int *lds_, int ntiles, hipSt
 void launch_pd_assemble(const DevMesh &M, const DevPD &D, double dtSq, hipStream_t st);
 void launch_pd_fill(const DevPD &D, int nnz, double *W2, hipStream_t st);
 void launch_pd_apply(const DevPD &D, int nV, const double *q, double *z, hipStream_t st);
+// k_ic.hip (LBFGS-HI): H's lower blocks and shifted diagonals into the factor storage; per colour [c0, c1) of order positions the
+// factorisation, y = L^-1 b (b in vertex order, y in D.yw) and x = L^-T y (x in vertex order)
+void launch_ic_fill(const DevIC &D, const double *Hval, double sigma, hipStream_t st);
+void launch_ic_factor_colour(const DevIC &D, int c0, int c1, hipStream_t st);
+void launch_ic_forward_colour(const DevIC &D, int c0, int c1, const double *b, hipStream_t st);
+void launch_ic_backward_colour(const DevIC &D, int c0, int c1, double *x, hipStream_t st);
 // small helpers
 void launch_init_x(int nV, const uint8_t *fixed, const double *v, double dt, const double *gdtsq,
                    double *x, hipStream_t st);

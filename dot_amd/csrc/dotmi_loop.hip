@@ -308,7 +308,7 @@ static void push_pair(dotmi_handle *h, int slot, const double *R)
     h->m = m + 1;
 }
 
-// The host-driven L-BFGS-H loop (DOTMI_FLAG_HOST_LOOP, and LBFGS-PD): one stream synchronisation per line-search trial, the
+// The host-driven L-BFGS-H loop (DOTMI_FLAG_HOST_LOOP, LBFGS-PD and LBFGS-HI): one stream synchronisation per line-search trial, the
 // two-loop's scalars and the accept / halve / converged decisions on the host.  In the q-based order of the reference
 static int run_host_loop(dotmi_handle *h, LoopOut &r)
 {
@@ -325,6 +325,11 @@ static int run_host_loop(dotmi_handle *h, LoopOut &r)
             launch_build_q(n, h->g, L, xi, h->q, h->st);
             phase_mark(h, DOTMI_T_MODIFY_GRAD);
             if (int rc = pd_apply(h, h->q, h->z, L)) return rc;
+        } else if (h->hi) {
+            // LBFGS-HI (D0T_HI, LBFGSTimeStepper.cpp:376-378): q interleaved, z = (L L^T)^-1 q through the colour launches (dotmi_ic.hip)
+            launch_build_q(n, h->g, L, xi, h->q, h->st);
+            phase_mark(h, DOTMI_T_MODIFY_GRAD);
+            if (int rc = ic_apply(h, h->q, h->z, L)) return rc;
         } else {
             launch_build_qpad(h->P, h->g, L, xi, h->st);   // q, straight into the padded right-hand sides
             phase_mark(h, DOTMI_T_MODIFY_GRAD);
@@ -335,7 +340,7 @@ static int run_host_loop(dotmi_handle *h, LoopOut &r)
         launch_build_p(n, h->z, L, h->partC, xi, h->p, h->st);
         phase_mark(h, DOTMI_T_MODIFY_SEARCHDIR);
         // ---- alpha_0 and the first trial ---------------------------------------------------------------
-        if (h->pd) {
+        if (h->pd || h->hi) {
             // only TST_DOT estimates alpha_0 (Optimizer::initStepSize, Optimizer.cpp:1076-1093): the unit step, no H p
             launch_step_forward(n, h->x, h->p, h->x_trial, nullptr, 1.0, 0, h->alphaMin, h->alpha_dev, h->h_alpha, h->st);
         } else {
@@ -483,7 +488,8 @@ int dotmi_step(dotmi_handle *h, dotmi_step_stats *st)
     if (r.failed) status = 2;
     else {
         if (r.it >= h->iterCap) status = 2;
-        if (refreshAtEnd)
+        // (LBFGS-HI: its refresh takes one read-back per factorisation attempt, so it runs whole behind the BE update below)
+        if (refreshAtEnd && !h->hi)
             if (int rc = refactor_issue(h, h->x)) return rc;
     }
     // BE update (Optimizer.cpp:354-361)
@@ -499,7 +505,7 @@ int dotmi_step(dotmi_handle *h, dotmi_step_stats *st)
         HIPCHECK(h, hipStreamSynchronize(h->st));
         phase_collect(h);
         HIPCHECK(h, hipGetLastError());
-        if (refreshAtEnd) rcFactor = refactor_finish(h, &ms_hess, &ms_fact);
+        if (refreshAtEnd) rcFactor = h->hi ? ic_refresh(h, h->x, &ms_hess, &ms_fact) : refactor_finish(h, &ms_hess, &ms_fact);
         if (rcFactor == DOTMI_E_DEVICE) return rcFactor;
     }
     if (st) {

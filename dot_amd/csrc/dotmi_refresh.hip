@@ -179,6 +179,7 @@ int refactor_finish(dotmi_handle *h, double *ms_hess, double *ms_fact)
 // (DOTTimeStepper::updateHessianAndFactor, DOTTimeStepper.cpp:349-380)
 int refactor(dotmi_handle *h, const double *x, double *ms_hess, double *ms_fact)
 {
+    if (h->hi) return ic_refresh(h, x, ms_hess, ms_fact);   // LBFGS-HI: H, then its incomplete factor (dotmi_ic.hip)
     if (int rc = refactor_issue(h, x)) return rc;
     HIPCHECK(h, hipStreamSynchronize(h->st));
     return refactor_finish(h, ms_hess, ms_fact);

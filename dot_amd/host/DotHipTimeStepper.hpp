@@ -50,6 +50,9 @@ struct Options {  // the Config fields the DOT stepper reads (src/Config.hpp)
     // `timeStepper LBFGS` (LBFGSTimeStepper with D0T_PD, main.cpp:918-919): L-BFGS on the constant projective-dynamics Laplacian
     // (DOTMI_FLAG_LBFGS_PD).  No subdomains: partitionAmt / epart / vpart are not passed on; the first trial is the unit step
     bool lbfgsPD = false;
+    // `timeStepper LBFGSHI` (LBFGSTimeStepper with D0T_HI): L-BFGS on a block incomplete Cholesky factor of the projected Hessian,
+    // rebuilt at the end of every step (DOTMI_FLAG_LBFGS_HI).  The whole mesh, no partition, unit first step, like lbfgsPD
+    bool lbfgsHI = false;
 };
 
 class DotHipTimeStepper {
@@ -100,9 +103,10 @@ public:
         m.lambda = mesh_.lambda;
         m.density = mesh_.density;
         m.fixed = fixed_.data();
-        m.epart = opt_.lbfgsPD ? nullptr : opt_.epart;
-        m.nParts = opt_.lbfgsPD ? 1 : opt_.partitionAmt;
-        m.vpart = opt_.lbfgsPD ? nullptr : opt_.vpart;
+        const bool whole = opt_.lbfgsPD || opt_.lbfgsHI;   // no subdomains
+        m.epart = whole ? nullptr : opt_.epart;
+        m.nParts = whole ? 1 : opt_.partitionAmt;
+        m.vpart = whole ? nullptr : opt_.vpart;
         dotmi_params p{};
         p.energy = opt_.energyType;
         p.dt = dt_;
@@ -110,12 +114,12 @@ public:
         p.relTol = relTol_;
         p.history = 5;        // DOTTimeStepper.cpp:45
         p.iterCap = 10000;    // DOTTimeStepper.cpp:302
-        p.alphaMin = opt_.lbfgsPD ? 1.0 : opt_.alphaMin;
+        p.alphaMin = whole ? 1.0 : opt_.alphaMin;
         p.device = opt_.device;
         p.rank = opt_.rank;
         p.world = opt_.world;
         p.comm_id = opt_.commId;
-        p.flags = opt_.flags | (opt_.lbfgsPD ? DOTMI_FLAG_LBFGS_PD : 0);
+        p.flags = opt_.flags | (opt_.lbfgsPD ? DOTMI_FLAG_LBFGS_PD : 0) | (opt_.lbfgsHI ? DOTMI_FLAG_LBFGS_HI : 0);
         if (int rc = dotmi_create(&m, &p, x0_.data(), &h_))
             throw std::runtime_error(std::string("dotmi_create: ") + dotmi_last_error(nullptr) + " (" +
                                      std::to_string(rc) + ")");

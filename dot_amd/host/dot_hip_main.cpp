@@ -10,7 +10,7 @@
 //   output/<name>/config.txt      echo of the effective script (Config::saveToFile, Config.cpp:209-302; main.cpp:786)
 //   output/<name>/info.txt        nV nT / steps innerIters / wall-clock summary (main.cpp:338-358)
 //   output/<name>/label.obj, wire.poly   partition labels of the surface triangles, surface wire frame
-//                                 (ADMMDDTimeStepper.cpp:375-442; not for `timeStepper LBFGS`, which has no partition)
+//                                 (ADMMDDTimeStepper.cpp:375-442; not for `timeStepper LBFGS` / `LBFGSHI`, which have no partition)
 // Script token `restart <status file>` resumes from a saved status (Optimizer.cpp:126-177).
 //
 // usage: dot_hip 100 <script.txt> [--mesh-root DIR] [--parts N] [--energy FCR|SNH] [--epart raw.i32]
@@ -116,13 +116,16 @@ int main(int argc, char **argv)
         // `timeStepper LBFGS` (LBFGSTimeStepper with D0T_PD): LBFGS-PD on the whole mesh -- no partition, and none of the partition
         // files (label.obj / wire.poly are written by the ADMMDD constructor only)
         const bool lbfgsPD = cfg.timeStepper == "LBFGS";
+        // `timeStepper LBFGSHI` (D0T_HI): LBFGS-HI, the block incomplete Cholesky of H -- the whole mesh, no partition files either
+        const bool lbfgsHI = cfg.timeStepper == "LBFGSHI";
+        const bool whole = lbfgsPD || lbfgsHI;
         int nParts = partsOverride > 0 ? partsOverride : cfg.partitionAmt;
-        if (lbfgsH || lbfgsPD) nParts = 1;
+        if (lbfgsH || whole) nParts = 1;
         if (cfg.blockSize > 0 && partsOverride <= 0) nParts = mesh.nV() / cfg.blockSize + 1;  // main.cpp:792-798
-        if (lbfgsPD) nParts = 1;   // (block-size scripts included: the stepper has no subdomains)
-        if (nParts < 2 && !lbfgsH && !lbfgsPD) nParts = 4;
+        if (whole) nParts = 1;   // (block-size scripts included: the stepper has no subdomains)
+        if (nParts < 2 && !lbfgsH && !whole) nParts = 4;
         std::vector<int32_t> epart;
-        if (lbfgsH || lbfgsPD) {
+        if (lbfgsH || whole) {
             epart.assign(mesh.nT(), 0);
         } else if (!epartFile.empty()) {
             std::ifstream f(epartFile, std::ios::binary);
@@ -168,7 +171,7 @@ int main(int argc, char **argv)
             }
             if (outGiven) {
                 mkdir(outDir.c_str(), 0755);
-                if (!lbfgsPD) write_partition_files(outDir, mesh, x0, epart);
+                if (!whole) write_partition_files(outDir, mesh, x0, epart);
             }
             if (cfg.restart) {
                 int t = 0;
@@ -198,6 +201,7 @@ int main(int argc, char **argv)
         if (lbfgsH) opt.alphaMin = 1.0;
         if (newton) opt.flags |= DOTMI_FLAG_NEWTON;
         opt.lbfgsPD = lbfgsPD;
+        opt.lbfgsHI = lbfgsHI;
         // `timeStepper LBFGSJH <n>`: block-Jacobi on a vertex partition (the reference takes METIS::partMesh_nodes;
         // without METIS a vertex goes to the lowest-numbered subdomain among its elements) and a unit first step
         std::vector<int32_t> vpart;
@@ -216,7 +220,7 @@ int main(int argc, char **argv)
             fIter = std::fopen((outDir + "/iterStats.txt").c_str(), "w");
             fLog = std::fopen((outDir + "/log.txt").c_str(), "w");
             if (!fIter || !fLog) throw std::runtime_error("cannot write into " + outDir);
-            if (!lbfgsPD) write_partition_files(outDir, mesh, x0, epart);
+            if (!whole) write_partition_files(outDir, mesh, x0, epart);
             write_config_txt(outDir + "/config.txt", cfg);   // main.cpp:786
         }
         const SurfaceMesh surf = files ? build_surface_mesh(mesh) : SurfaceMesh();
@@ -242,6 +246,13 @@ int main(int argc, char **argv)
             std::printf("restarted from %s at time step %d\n", cfg.statusPath.c_str(), firstFrame);
         }
         std::printf("setup %.3f s, nV %d nT %d, %d subdomains, tol %.6e\n", now_s() - tSetup, mesh.nV(), mesh.nT(), nParts, ts.getTargetGRes());
+
+        if (lbfgsHI) {
+            int32_t colours = 0, attempts = 0;
+            double shift = 0;
+            if (dotmi_ic_info(ts.handle(), &colours, &shift, &attempts) != 0) throw std::runtime_error("dotmi_ic_info failed");
+            std::printf("LBFGS-HI: %d colours, shift %g, %d attempts\n", colours, shift, attempts);
+        }
 
         const int nFrames = frames > 0 ? frames : (int)(cfg.duration / cfg.dt);
         long lineSearch = 0;

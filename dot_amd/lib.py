@@ -28,6 +28,7 @@ FLAG_NEWTON = 64
 FLAG_ASYNC_REFRESH = 128
 FLAG_OWNER_EXCHANGE = 256
 FLAG_LBFGS_PD = 512
+FLAG_LBFGS_HI = 1024
 
 
 class Mesh(C.Structure):
@@ -75,6 +76,7 @@ EXPORTS = [
     "dotmi_refactor", "dotmi_apply_precond", "dotmi_spmv", "dotmi_get_features", "dotmi_part_size", "dotmi_padded_size",
     "dotmi_part_matrix", "dotmi_factor_storage_bytes", "dotmi_factor_kind", "dotmi_backsolve_form", "dotmi_plan_backsolve_form", "dotmi_probe_direction", "dotmi_bench_precond", "dotmi_bench_energy", "dotmi_bench_kernel", "dotmi_plan_shards", "dotmi_plan_layout", "dotmi_plan_tile_schedule", "dotmi_plan_tile_schedule_two_level", "dotmi_plan_tile_deps", "dotmi_plan_backsolve_tiles", "dotmi_plan_patches", "dotmi_plan_vpatches", "dotmi_plan_rank", "dotmi_partition",
     "dotmi_plan_pd",
+    "dotmi_plan_ic", "dotmi_ic_info", "dotmi_ic_factor",
     "dotmi_set_rel_tol", "dotmi_set_time_step", "dotmi_set_lame",
 ]
 
@@ -145,6 +147,10 @@ def load() -> C.CDLL:
     L.dotmi_partition.argtypes = [C.c_int32, C.c_int32, c_ip, c_dp, C.c_int32, c_ip]
     if hasattr(L, "dotmi_plan_pd"):
         L.dotmi_plan_pd.argtypes = [C.c_int32, C.c_int32, c_ip, c_dp, c_ip, C.POINTER(C.c_int64)]
+    if hasattr(L, "dotmi_plan_ic"):
+        L.dotmi_plan_ic.argtypes = [C.c_int32, C.c_int32, c_ip] + [c_ip] * 10
+        L.dotmi_ic_info.argtypes = [H, c_ip, c_dp, c_ip]
+        L.dotmi_ic_factor.argtypes = [H, C.c_int32, c_dp]
     L.dotmi_plan_layout.argtypes = [C.c_int32, C.c_int32, c_ip, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32,
                                     C.c_int32, C.c_int32, C.c_int32, c_ip, c_ip, c_ip, c_ip]
     if hasattr(L, "dotmi_plan_backsolve_tiles"):   # (round 5 entry; guarded like the two above -- ADVICE r05)

@@ -52,7 +52,7 @@ class DOTTimeStepper:
         self._mu = self._per_element(mu, mu0, "mu")
         self._lam = self._per_element(lam, lam0, "lam")
         self._fixed = np.ascontiguousarray(scene.fixed, dtype=np.uint8)
-        # (epart None: no element partition -- an LBFGS-PD handle, _lib.FLAG_LBFGS_PD, builds no subdomains)
+        # (epart None: no element partition -- an LBFGS-PD or LBFGS-HI handle, _lib.FLAG_LBFGS_PD / _HI, builds no subdomains)
         self._epart = np.ascontiguousarray(epart, dtype=np.int32) if epart is not None else None
         self.nparts = int(nparts)
         self._vpart = np.ascontiguousarray(vpart, dtype=np.int32) if vpart is not None else None
@@ -268,6 +268,20 @@ class DOTTimeStepper:
             "probe_direction")
         out["alpha0"], out["E"] = a0.value, E.value
         return out
+
+    def icInfo(self):
+        """LBFGS-HI (_lib.FLAG_LBFGS_HI): (colours, shift, attempts) of the last incomplete factorisation (dotmi_ic_info)"""
+        nc, sh, na = C.c_int32(), C.c_double(), C.c_int32()
+        self._check(self._L.dotmi_ic_info(self._h, C.cast(C.byref(nc), _lib.c_ip), C.cast(C.byref(sh), _lib.c_dp),
+                                          C.cast(C.byref(na), _lib.c_ip)), "ic_info")
+        return nc.value, sh.value, na.value
+
+    def icFactor(self) -> np.ndarray:
+        """LBFGS-HI: the factor's blocks (nL + nV, 3, 3) in plan order, lower blocks then diagonals (dotmi_ic_factor)"""
+        nb = self._check(self._L.dotmi_ic_factor(self._h, 0, None), "ic_factor")
+        F = np.empty((nb, 3, 3))
+        self._check(self._L.dotmi_ic_factor(self._h, nb, dp(F)), "ic_factor")
+        return F
 
     def multiply(self, p) -> np.ndarray:
         p = np.ascontiguousarray(p, dtype=np.float64)

@@ -154,6 +154,24 @@ enum {
                                      * OWNER_EXCHANGE, GSDD, NEWTON, ASYNC_REFRESH or a vpart.  Entries of the Hessian block solve
                                      * (dotmi_refactor, dotmi_part_matrix, dotmi_spmv, dotmi_probe_direction, the bench entries) return
                                      * DOTMI_E_INVALID on such a handle. */
+#define DOTMI_FLAG_LBFGS_HI 1024    /* dotmi_step runs the reference's LBFGS-HI (`timeStepper LBFGSHI`, LBFGSTimeStepper with D0T_HI,
+                                     * LBFGSTimeStepper.cpp:214-233, :308-316, :376-378): L-BFGS whose initial inverse Hessian is an
+                                     * INCOMPLETE Cholesky factor of the projected Hessian, rebuilt at the end of every step; the first
+                                     * trial of every line search is the unit step.  A GPU form of the method, not of
+                                     * Eigen::IncompleteCholesky: a block (3 x 3) IC(0) on H's own block pattern in a multicolour
+                                     * ordering of the vertex graph (dotmi_plan_ic), one launch per colour, with a diagonal shift
+                                     * A_ii += sigma diag(A_ii) on breakdown: the first attempt takes half the last successful shift
+                                     * (0 stays 0), a breakdown doubles it from 1e-3, at most 40 attempts, then DOTMI_E_NOTSPD.  The
+                                     * reference's iteration counts are therefore not reproduced; the oracle running the same
+                                     * preconditioner is (tests/ic_reference.py).  The handle builds NO subdomain block solve (epart,
+                                     * vpart and nParts are ignored: pass NULL / 1).  The refresh -- after create, at the end of every
+                                     * step, after dotmi_refix, dotmi_refactor, dotmi_set_time_step and dotmi_set_lame -- assembles H
+                                     * and factors it: ms_hessian as usual, ms_factor = all attempts, precond_bytes = 72 x (lower
+                                     * blocks + diagonals) x 2.  dotmi_apply_precond returns (L L^T)^-1 r; dotmi_spmv works.
+                                     * Host-driven loop, single GPU: not with world > 1, FORCE_DIST, OWNER_EXCHANGE, GSDD, NEWTON,
+                                     * LBFGS_PD, ASYNC_REFRESH or a vpart.  dotmi_part_matrix, dotmi_part_size, dotmi_probe_direction,
+                                     * dotmi_bench_precond and the bench kinds of the block solve and of the device loop return
+                                     * DOTMI_E_INVALID on such a handle. */
 
 typedef struct {
     int32_t iters;        /* L-BFGS iterations (innerIterAmt delta, DOTTimeStepper.cpp:338) */
@@ -373,6 +391,20 @@ int dotmi_part_matrix(dotmi_handle *h, int32_t part, int inverse, double *M, int
  * structural non-zeros of X, as dotmi_step_stats.precond_bytes counts them (64-row blocks whose rows are longer than 2048 columns take
  * two passes, dots then scatter, and read their rows a second time, like the 3-dof back-solve beyond 5120 columns) */
 int dotmi_plan_pd(int32_t nV, int32_t nT, const int32_t *T, const double *Xrest, int32_t *padded, int64_t *apply_bytes);
+/* (host only) the plan of a DOTMI_FLAG_LBFGS_HI handle's block incomplete Cholesky (dot_amd/csrc/ic_plan.hpp): the vertex adjacency
+ * coloured greedily in ascending vertex id (smallest colour no neighbour holds), the vertices ordered by (colour, id).  sizes[3] =
+ * {colours, lower blocks nL, products nP}; call with NULL arrays first.  colour[nV], pos[nV] (order position of a vertex);
+ * lptr[nV + 1] / lidx[nL]: per order position its lower neighbours' positions, ascending; lsrc[nL] / dsrc[nV]: the block of the global
+ * block-CSR (vertex adjacency incl. self, ascending) behind a lower block / behind a position's diagonal; pptr[nL + 1], pa[nP], pb[nP]:
+ * per lower block (i, j) the products L[pa] L[pb]^T = L_ik L_jk^T over the common lower neighbours k, ascending position of k.  Any
+ * array may be NULL. */
+int dotmi_plan_ic(int32_t nV, int32_t nT, const int32_t *T, int32_t *sizes, int32_t *colour, int32_t *pos, int32_t *lptr,
+                  int32_t *lidx, int32_t *lsrc, int32_t *dsrc, int32_t *pptr, int32_t *pa, int32_t *pb);
+/* DOTMI_FLAG_LBFGS_HI handles: the last factorisation's colour count, successful shift sigma and number of attempts */
+int dotmi_ic_info(dotmi_handle *h, int32_t *colours, double *shift, int32_t *attempts);
+/* DOTMI_FLAG_LBFGS_HI handles: the factor's 3 x 3 blocks, row-major, in plan order -- the nL lower blocks, then the nV lower-triangular
+ * diagonal blocks by order position.  Returns their number nL + nV (blocks == NULL: only that); cap: room in blocks, in blocks. */
+int dotmi_ic_factor(dotmi_handle *h, int32_t cap, double *blocks);
 
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* Launch the subdomain back-solve kernel `reps` times on the handle's stream between two HIP events
