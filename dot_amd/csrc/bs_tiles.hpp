@@ -40,6 +40,13 @@ struct BsTilePlan {
 };
 
 inline int bs_tile_len(const int4 &t) { return t.y + (t.z >> 16) - t.w; }
+// A tile beyond BS_LONG columns goes to the two-phase kernel in column chunks of BS_LONG_CHUNK: the width backsolve_long_kernel gives
+// its workgroups (BSL_CW, k_backsolve.hip: 512 threads x 4 x 2), NOT the register tile BS_LONG of the single-pass kernel.  The two
+// were one number until the register tile grew from 4096 to 5120 columns; counted in units of 5120, a tile of more than 8192 columns
+// got a work item too few, its last columns were never visited and the kernel's second phase summed chunk partials nobody had
+// written (the whole mesh as one subdomain: bunny5K, 14 976 columns, |H M r - r| / |r| = 2)
+constexpr int BS_LONG_CHUNK = 4096;
+inline int bs_long_chunks(int len) { return (((len + 15) & ~15) + BS_LONG_CHUNK - 1) / BS_LONG_CHUNK; }
 
 // usedRows(nd, ls) = live scalar rows of tree node nd (its leaf block / separator) in owned subdomain ls
 template <class UsedRows>
@@ -120,7 +127,7 @@ inline void plan_backsolve_tiles(const std::vector<NdNode> &nd, UsedRows usedRow
     out.partLworkPtr.assign(nParts + 1, 0);
     for (const int4 &t : tiles) {   // generated part after part
         if (bs_tile_len(t) > BS_LONG) {
-            const int nch = (((bs_tile_len(t) + 15) & ~15) + BS_LONG - 1) / BS_LONG;
+            const int nch = bs_long_chunks(bs_tile_len(t));
             for (int c = 0; c < nch; ++c) out.lworkByPart.push_back(make_int2((int)out.ltilesByPart.size(), c));
             out.ltilesByPart.push_back(t);
             out.partLworkPtr[t.x + 1] += nch;
@@ -137,13 +144,13 @@ inline void plan_backsolve_tiles(const std::vector<NdNode> &nd, UsedRows usedRow
     auto tile_work = [](const int4 &t) { return (long long)(t.z >> 16) * (t.y + 64 - t.w); };
     std::stable_sort(tiles.begin(), tiles.end(), [&](const int4 &a, const int4 &b) { return tile_work(a) > tile_work(b); });
     // rows longer than the register tile of the single-pass kernel go through the two-phase kernel, cut into
-    // column chunks of BS_LONG
+    // column chunks of BS_LONG_CHUNK
     {
         std::vector<int4> shortTiles;
         for (const int4 &t : tiles) {
             const int len = bs_tile_len(t);
             if (len > BS_LONG) {
-                const int nch = (((len + 15) & ~15) + BS_LONG - 1) / BS_LONG;
+                const int nch = bs_long_chunks(len);
                 for (int c = 0; c < nch; ++c) out.lwork.push_back(make_int2((int)out.ltiles.size(), c));
                 out.maxChunks = std::max(out.maxChunks, nch);
                 out.ltiles.push_back(t);

@@ -1126,6 +1126,7 @@ void dotmi_destroy(dotmi_handle *h)
     if (h->h_partR) hipHostFree(h->h_partR);
     if (h->h_alpha) hipHostFree(h->h_alpha);
     if (h->h_ctl) hipHostFree(h->h_ctl);
+    if (h->h_pcg) hipHostFree(h->h_pcg);
     if (h->dposPinned) hipHostFree(h->dposPinned);
     if (h->evDir) hipEventDestroy(h->evDir);
     if (h->h_info) hipHostFree(h->h_info);
@@ -1177,6 +1178,16 @@ static int take_arguments(dotmi_handle *h, const dotmi_mesh *mesh, const dotmi_p
     h->T.assign(mesh->T, mesh->T + 4 * (size_t)h->nT);
     h->pd = (h->flags & DOTMI_FLAG_LBFGS_PD) != 0;
     h->hi = (h->flags & DOTMI_FLAG_LBFGS_HI) != 0;
+    h->newtonPcg = (h->flags & DOTMI_FLAG_NEWTON_PCG) != 0;
+    if (h->newtonPcg) {
+        const int bad = DOTMI_FLAG_FORCE_DIST | DOTMI_FLAG_OWNER_EXCHANGE | DOTMI_FLAG_GSDD | DOTMI_FLAG_NEWTON | DOTMI_FLAG_LBFGS_PD |
+                        DOTMI_FLAG_LBFGS_HI | DOTMI_FLAG_ASYNC_REFRESH;
+        if (prm->world > 1 || (h->flags & bad) || mesh->vpart) {
+            h->err = "DOTMI_FLAG_NEWTON_PCG: single GPU, host loop, not with DOTMI_FLAG_FORCE_DIST / OWNER_EXCHANGE / GSDD / NEWTON / "
+                     "LBFGS_PD / LBFGS_HI / ASYNC_REFRESH or a vertex partition";
+            return DOTMI_E_INVALID;
+        }
+    }
     if (h->hi) {
         const int bad = DOTMI_FLAG_FORCE_DIST | DOTMI_FLAG_OWNER_EXCHANGE | DOTMI_FLAG_GSDD | DOTMI_FLAG_NEWTON | DOTMI_FLAG_LBFGS_PD |
                         DOTMI_FLAG_ASYNC_REFRESH;
@@ -1225,7 +1236,7 @@ static int take_arguments(dotmi_handle *h, const dotmi_mesh *mesh, const dotmi_p
 static int choose_loop_form(dotmi_handle *h)
 {
     h->gsdd = (h->flags & DOTMI_FLAG_GSDD) != 0;
-    h->newton = (h->flags & DOTMI_FLAG_NEWTON) != 0;
+    h->newton = (h->flags & (DOTMI_FLAG_NEWTON | DOTMI_FLAG_NEWTON_PCG)) != 0;   // (Newton-PCG: the same loop, dotmi_pcg.hip for the solve)
     if (h->newton && (h->dist || h->gsdd)) {
         h->err = "DOTMI_FLAG_NEWTON: single GPU, not together with DOTMI_FLAG_GSDD";
         return DOTMI_E_INVALID;
@@ -1256,7 +1267,7 @@ static int choose_loop_form(dotmi_handle *h)
     // the fixed-corotational SVD the doubled element work costs what the saved launch gives -- bunny5K 1.656 -> 1.696 ms, measured)
     if (h->earlyBs && !h->dist && h->world == 1 && h->tune.fuseStep && h->tune.fuseDir && h->tune.vertexPatches != 0 &&
         (h->mat == DOTMI_ENERGY_SNH || h->tune.vertexPatches > 0) &&
-        h->P.ntiles - h->P.ntilesWide + h->P.nquad > 0 && !(h->flags & (DOTMI_FLAG_GSDD | DOTMI_FLAG_NEWTON | DOTMI_FLAG_HOST_LOOP))) {
+        h->P.ntiles - h->P.ntilesWide + h->P.nquad > 0 && !(h->flags & (DOTMI_FLAG_GSDD | DOTMI_FLAG_NEWTON | DOTMI_FLAG_NEWTON_PCG | DOTMI_FLAG_HOST_LOOP))) {
         const HostVPatches HV = build_vpatches(h->nV, h->nT, h->T.data(), h->Xrest.data(), 512, 85);
         const size_t shm = sizeof(double) * ((size_t)3 * HV.PV + (size_t)3 * HV.RUN) + 2 * (size_t)((HV.PO + 1 + 3) & ~3);
         if (HV.nPatches > 0 && HV.nPatches <= 512 && HV.nPatches <= ELEM_NB_MAX && shm <= 64 * 1024 && HV.PO + 1 <= 256) {
@@ -1370,6 +1381,8 @@ static int create_impl(dotmi_handle *h, const dotmi_mesh *mesh, const dotmi_para
     host_features(h);
     h->targetGRes = host_target_gres(h);
     if (int rc = build_device_mesh(h)) return rc;
+    if (!h->pd && !h->hi)
+        if (int rc = pcg_build_scaling(h)) return rc;   // 1 / sqrt(dup) of dotmi_solve_hessian's preconditioner (dotmi_pcg.hip)
     const int n = h->n;
     double **vecs[] = {&h->x, &h->x_trial, &h->xn, &h->v, &h->xt, &h->g, &h->g_trial, &h->p, &h->q, &h->z,
                        &h->Hp, &h->tmpn};

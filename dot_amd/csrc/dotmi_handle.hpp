@@ -6,6 +6,7 @@
 //   dotmi_devloop.hip     the device-resident L-BFGS-H loop: the stages of a slot in both orders, run_device_loop and its parts
 //   dotmi_reconfig.hip    tolerance, time step and materials changed on a live handle (dotmi_set_rel_tol / _time_step / _lame)
 //   dotmi_pd.hip / dotmi_ic.hip   the preconditioners of LBFGS-PD (scalar Laplacian) and LBFGS-HI (block incomplete Cholesky of H)
+//   dotmi_pcg.hip         Newton-PCG: conjugate gradients on the global H with the block solve (dotmi_solve_hessian, DOTMI_FLAG_NEWTON_PCG)
 //   dotmi_api.hip         the remaining ABI entry points (state, kernel-level calls, probes, measurement)
 //
 // Control flow mirrors (paths relative to /root/reference/src)
@@ -316,6 +317,17 @@ struct dotmi_handle {
     std::vector<int> icStart;   // nColours + 1: the order positions of every colour
     double icShift = 0.0;
     int icAttempts = 0;
+    // DOTMI_FLAG_NEWTON_PCG: `newton` with the PCG of dotmi_pcg.hip in place of the single block-solve application, any number of
+    // subdomains.  The PCG's state exists on every single-rank handle with H and the block solve (dotmi_solve_hessian): isd from
+    // create, the vectors from the first solve; its iterate u is the handle's p
+    bool newtonPcg = false;
+    DevPcg pcg;
+    double *h_pcg = nullptr;                   // pinned: PCG_READBACK doubles, the records and the |r|^2 partials of a batch's end
+    double pcgTol = 1e-3;                      // dotmi_set_pcg: the step's relative tolerance, iteration cap, iterations per read-back
+    int pcgCap = 500, pcgEvery = 8;   // (8: the best of 1, 2, 4, 8 in profiles/newton_pcg.txt)
+    long long pcgSolves = 0, pcgItersTotal = 0;   // dotmi_pcg_info
+    int pcgLastIters = 0;
+    double pcgLastRes = 0.0;
     bool devLoop = false;
     DevLoop *ctl = nullptr, *h_ctl = nullptr;  // device / pinned staging
     int *h_flags = nullptr;                    // pinned: {status, slots done}, written by the controller
@@ -425,6 +437,9 @@ int pd_apply(dotmi_handle *h, const double *q, double *z, const LbfgsArgs &L);
 int build_ic(dotmi_handle *h, const std::vector<int> &adj_ptr, const std::vector<int> &adj_idx);
 int ic_refresh(dotmi_handle *h, const double *x, double *ms_hess, double *ms_fact);
 int ic_apply(dotmi_handle *h, const double *q, double *z, const LbfgsArgs &L);
+// dotmi_pcg.hip (Newton-PCG)
+int pcg_build_scaling(dotmi_handle *h);
+int pcg_solve(dotmi_handle *h, const double *b, double rel_tol, int max_iter, int check_every, int *iters, double *rel_res);
 // dotmi_collectives.hip
 int allreduce_sum(dotmi_handle *h, double *dev, size_t n);
 int adopt_rank0(dotmi_handle *h, double *vals, int n);
@@ -439,6 +454,7 @@ struct Bracket {
 struct LoopOut {           // what a loop driver (run_*_loop) hands back to dotmi_step
     double lastE = 0, g2 = 0, E0 = 0, g20 = 0;   // energy and |g|^2 of the last iterate / at the start of the step
     int it = 0;
+    long long applies = 0; // Newton-PCG: block-solve applications (the CG iterations of the step's solves)
     bool failed = false;   // the line search ran out of step length
 };
 int apply_precond(dotmi_handle *h, const double *q, double *z, const LbfgsArgs &L);

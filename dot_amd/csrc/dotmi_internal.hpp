@@ -538,4 +538,29 @@ void launch_gather_lame(const int *slotElem, size_t nSlots, const double *mu, co
 void launch_x_tilde(int nV, const uint8_t *fixed, const double *xn, const double *v, double dt, const double *gdtsq, double *xt,
                     hipStream_t st);
 
+// ---- Newton-PCG (DOTMI_FLAG_NEWTON_PCG, dotmi_solve_hessian; dotmi_pcg.hip / k_pcg.hip): conjugate gradients on H with the block solve ----
+// the scalars of a CG iteration, one record per parity of the iteration (k_pcg.hip)
+enum { PCG_RUNNING = 0, PCG_CONVERGED = 1, PCG_BREAKDOWN = 2 };
+struct PcgRec {
+    double gamma, alpha;   // r.w and the step of iteration `iter`
+    double rr;             // |r|^2: after iteration `iter` once the solve has ended, after iteration iter - 1 while it runs
+    double bb;             // |b|^2
+    int iter;              // iterations done
+    int state;             // PCG_*
+    int pad[6];
+};
+static_assert(sizeof(PcgRec) == 64, "two records and the |r|^2 columns are read back as one block");
+struct DevPcg {
+    PcgRec *rec = nullptr;       // [2], and behind them partBT: what the host reads once per batch (PCG_READBACK doubles)
+    double *partBT = nullptr;    // [2][NB_RED]: the |r|^2 partials of the even / odd iterations, column-major (write_partials' partialsT)
+    double *partAT = nullptr;    // [2][NB_RED]: the gamma / delta partials of the running iteration, column-major
+    double *partA = nullptr, *partB = nullptr;   // their row-major twins (NB_RED x RED_K)
+    double *isd = nullptr;       // nV: 1 / sqrt(dup)
+    double *r = nullptr, *d = nullptr, *Hd = nullptr, *w = nullptr, *s = nullptr;   // 3 nV each, allocated by the first solve
+};
+constexpr int PCG_READBACK = 2 * (int)(sizeof(PcgRec) / sizeof(double)) + 2 * NB_RED;
+void launch_pcg_init(const DevPcg &C, int n, const double *b, double *u, double *q, hipStream_t st);
+void launch_pcg_spmv(const DevMesh &M, const DevPcg &C, const double *Hval, const double *zsum, int it, hipStream_t st);
+void launch_pcg_update(const DevPcg &C, int n, double *u, double *q, int it, double rel_tol, hipStream_t st);
+
 }  // namespace dotmi

@@ -247,6 +247,7 @@ static int run_gsdd_loop(dotmi_handle *h, LoopOut &r)
 // Optimizer::solve_oneStep :703-749 and needRefactorize set): per iteration the projected Hessian at the current iterate
 // is assembled and factorised (:705-729), p = H^-1 (-g) (:735-737), the line search starts from step 1 (initStepSize
 // :1088) and the gradient is refreshed (:745).  Uses the same refresh / back-solve kernels as the DOT path.
+// DOTMI_FLAG_NEWTON_PCG: the same loop with H p = -g solved by conjugate gradients on the subdomain factors (dotmi_pcg.hip).
 static int run_newton_loop(dotmi_handle *h, LoopOut &r, double *ms_hess, double *ms_fact)
 {
     const int n = h->n;
@@ -255,8 +256,17 @@ static int run_newton_loop(dotmi_handle *h, LoopOut &r, double *ms_hess, double 
     double R[RED_K];
     do {
         if (int rc = refactor(h, h->x, ms_hess, ms_fact)) return rc;
-        launch_build_q(n, h->g, L0, nullptr, h->q, h->st);                     // q = -g
-        if (int rc = apply_precond(h, h->q, h->p, L0)) return rc;               // p = H^-1 q (one subdomain: no averaging)
+        if (h->newtonPcg) {
+            // DOTMI_FLAG_NEWTON_PCG: p = PCG(H, -g) on any number of subdomains (dotmi_pcg.hip).  A solve that ends at its cap or in
+            // breakdown hands over its iterate all the same -- every CG iterate from zero is a descent direction -- and the step goes on
+            launch_build_q(n, h->g, L0, nullptr, h->tmpn, h->st);              // b = -g
+            int cg = 0;
+            if (int rc = pcg_solve(h, h->tmpn, h->pcgTol, h->pcgCap, h->pcgEvery, &cg, nullptr); rc < 0) return rc;
+            r.applies += cg;
+        } else {
+            launch_build_q(n, h->g, L0, nullptr, h->q, h->st);                 // q = -g
+            if (int rc = apply_precond(h, h->q, h->p, L0)) return rc;           // p = H^-1 q (one subdomain: no averaging)
+        }
         double alpha = 1.0, E = 0;
         launch_step_forward(n, h->x, h->p, h->x_trial, nullptr, alpha, 0, h->alphaMin, h->alpha_dev, h->h_alpha, h->st);
         if (int rc = trial(h, h->x_trial, h->g_trial, 0, L0, 0, &E)) return rc;
@@ -396,7 +406,7 @@ static void fill_step_stats(dotmi_handle *h, dotmi_step_stats *st, const LoopOut
     }
     st->precond_bytes = h->precond_bytes;
     st->factor_flops = h->factorFlops;
-    st->backsolve_launches = r.it;
+    st->backsolve_launches = h->newtonPcg ? r.applies : r.it;   // (Newton-PCG: one block-solve application per CG iteration)
     st->backsolve_stopped = (h->devLoop && h->earlyNow) ? halvings + 1 : 0;
     // (a paired slot whose full step was rejected takes a halving without a stopped launch; one that is redone stops without one)
     if (h->devLoop && h->pairNow) st->backsolve_stopped += 2 * h->pairRedo - h->pairSlots;

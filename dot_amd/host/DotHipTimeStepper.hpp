@@ -53,6 +53,12 @@ struct Options {  // the Config fields the DOT stepper reads (src/Config.hpp)
     // `timeStepper LBFGSHI` (LBFGSTimeStepper with D0T_HI): L-BFGS on a block incomplete Cholesky factor of the projected Hessian,
     // rebuilt at the end of every step (DOTMI_FLAG_LBFGS_HI).  The whole mesh, no partition, unit first step, like lbfgsPD
     bool lbfgsHI = false;
+    // `timeStepper Newton` on MORE than one subdomain (DOTMI_FLAG_NEWTON_PCG): H p = -g by conjugate gradients on the subdomain factors
+    // instead of one factor of the whole mesh; partitionAmt / epart as for DOT, unit first step.  The solves' forcing term, iteration
+    // cap and iterations per read-back (dotmi_set_pcg)
+    bool newtonPCG = false;
+    double pcgRelTol = 1e-3;
+    int pcgMaxIter = 500, pcgCheckEvery = 8;
 };
 
 class DotHipTimeStepper {
@@ -119,10 +125,12 @@ public:
         p.rank = opt_.rank;
         p.world = opt_.world;
         p.comm_id = opt_.commId;
-        p.flags = opt_.flags | (opt_.lbfgsPD ? DOTMI_FLAG_LBFGS_PD : 0) | (opt_.lbfgsHI ? DOTMI_FLAG_LBFGS_HI : 0);
+        p.flags = opt_.flags | (opt_.lbfgsPD ? DOTMI_FLAG_LBFGS_PD : 0) | (opt_.lbfgsHI ? DOTMI_FLAG_LBFGS_HI : 0) |
+                  (opt_.newtonPCG ? DOTMI_FLAG_NEWTON_PCG : 0);
         if (int rc = dotmi_create(&m, &p, x0_.data(), &h_))
             throw std::runtime_error(std::string("dotmi_create: ") + dotmi_last_error(nullptr) + " (" +
                                      std::to_string(rc) + ")");
+        if (opt_.newtonPCG) check(dotmi_set_pcg(h_, opt_.pcgRelTol, opt_.pcgMaxIter, opt_.pcgCheckEvery), "set_pcg");
     }
 
     // 0 stepped, 1 all frames done, 2 stepped but iteration cap / line-search failure (Optimizer.cpp:327-368)

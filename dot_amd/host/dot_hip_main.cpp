@@ -15,7 +15,7 @@
 //
 // usage: dot_hip 100 <script.txt> [--mesh-root DIR] [--parts N] [--energy FCR|SNH] [--epart raw.i32]
 //                [--frames K] [--out DIR] [--device D] [--no-files] [--dump-scene K] [--dump-config] [--dump-formats DIR]
-//                [--echo-config FILE] [--fast]
+//                [--echo-config FILE] [--fast] [--newton-pcg N]
 //        dot_hip --write-info FILE nV nT steps iters t0..t21
 #include <algorithm>
 #include <chrono>
@@ -48,7 +48,7 @@ int main(int argc, char **argv)
     }
     if (argc < 3) {
         std::fprintf(stderr, "usage: %s 100 <script.txt> [--mesh-root DIR] [--parts N] [--energy FCR|SNH] "
-                             "[--epart raw.i32] [--frames K] [--out DIR] [--device D] [--no-files] [--dump-scene K] [--dump-config] [--dump-formats DIR] [--fast]\n", argv[0]);
+                             "[--epart raw.i32] [--frames K] [--out DIR] [--device D] [--no-files] [--dump-scene K] [--dump-config] [--dump-formats DIR] [--fast] [--newton-pcg N]\n", argv[0]);
         return 2;
     }
     if (std::string(argv[1]) != "100") {
@@ -57,7 +57,7 @@ int main(int argc, char **argv)
     }
     const std::string scriptPath = argv[2];
     std::string meshRoot = ".", outDir, epartFile, energyOverride;
-    int partsOverride = -1, frames = -1, device = 0, dumpScene = -1;
+    int partsOverride = -1, frames = -1, device = 0, dumpScene = -1, newtonPcgParts = 0;
     bool files = true, dumpConfig = false, fast = false;
     std::string dumpFormats, echoConfig;
     for (int i = 3; i < argc; ++i) {
@@ -76,6 +76,9 @@ int main(int argc, char **argv)
         else if (a == "--dump-formats") dumpFormats = next();   // write 0.obj + info.txt of the initial scene into DIR (no GPU)
         else if (a == "--echo-config") echoConfig = next();   // write config.txt (Config::saveToFile's echo) to this path and exit
         else if (a == "--fast") fast = true;   // device-resident loop: the loop slots of info.txt stay 0
+        // `timeStepper Newton` scripts: the mesh in N subdomains of the built-in partitioner under DOTMI_FLAG_NEWTON_PCG (H p = -g by
+        // conjugate gradients on the subdomain factors) instead of one subdomain under DOTMI_FLAG_NEWTON; the output files are Newton's
+        else if (a == "--newton-pcg") newtonPcgParts = std::stoi(next());
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     try {
@@ -111,7 +114,10 @@ int main(int argc, char **argv)
         // `timeStepper LBFGSH` (LBFGSTimeStepper with D0T_H, LBFGSTimeStepper.cpp:196-262, :338-420): L-BFGS whose initial
         // inverse Hessian is the factored GLOBAL projected Hessian and whose line search starts from step 1 -- this
         // path with the whole mesh as ONE subdomain (no averaging: dup = 1) and the alpha_0 clamp at 1
-        const bool newton = cfg.timeStepper == "Newton";   // projected Newton: one subdomain, DOTMI_FLAG_NEWTON
+        if (newtonPcgParts != 0 && (cfg.timeStepper != "Newton" || newtonPcgParts < 1))
+            throw std::runtime_error("--newton-pcg <N> takes N >= 1 and a script with `timeStepper Newton`");
+        const bool newtonPcg = newtonPcgParts > 0;
+        const bool newton = cfg.timeStepper == "Newton" && !newtonPcg;   // projected Newton: one subdomain, DOTMI_FLAG_NEWTON
         const bool lbfgsH = cfg.timeStepper == "LBFGSH" || newton;
         // `timeStepper LBFGS` (LBFGSTimeStepper with D0T_PD): LBFGS-PD on the whole mesh -- no partition, and none of the partition
         // files (label.obj / wire.poly are written by the ADMMDD constructor only)
@@ -123,11 +129,12 @@ int main(int argc, char **argv)
         if (lbfgsH || whole) nParts = 1;
         if (cfg.blockSize > 0 && partsOverride <= 0) nParts = mesh.nV() / cfg.blockSize + 1;  // main.cpp:792-798
         if (whole) nParts = 1;   // (block-size scripts included: the stepper has no subdomains)
-        if (nParts < 2 && !lbfgsH && !whole) nParts = 4;
+        if (newtonPcg) nParts = newtonPcgParts;
+        if (nParts < 2 && !lbfgsH && !whole && !newtonPcg) nParts = 4;
         std::vector<int32_t> epart;
         if (lbfgsH || whole) {
             epart.assign(mesh.nT(), 0);
-        } else if (!epartFile.empty()) {
+        } else if (!epartFile.empty() && !newtonPcg) {
             std::ifstream f(epartFile, std::ios::binary);
             epart.resize(mesh.nT());
             f.read((char *)epart.data(), sizeof(int32_t) * epart.size());
@@ -200,6 +207,10 @@ int main(int argc, char **argv)
         if (cfg.timeStepper == "GSDD") opt.flags |= DOTMI_FLAG_GSDD;
         if (lbfgsH) opt.alphaMin = 1.0;
         if (newton) opt.flags |= DOTMI_FLAG_NEWTON;
+        if (newtonPcg) {
+            opt.newtonPCG = true;
+            opt.alphaMin = 1.0;
+        }
         opt.lbfgsPD = lbfgsPD;
         opt.lbfgsHI = lbfgsHI;
         // `timeStepper LBFGSJH <n>`: block-Jacobi on a vertex partition (the reference takes METIS::partMesh_nodes;

@@ -29,6 +29,7 @@ FLAG_ASYNC_REFRESH = 128
 FLAG_OWNER_EXCHANGE = 256
 FLAG_LBFGS_PD = 512
 FLAG_LBFGS_HI = 1024
+FLAG_NEWTON_PCG = 2048
 
 
 class Mesh(C.Structure):
@@ -78,6 +79,7 @@ EXPORTS = [
     "dotmi_plan_pd",
     "dotmi_plan_ic", "dotmi_ic_info", "dotmi_ic_factor",
     "dotmi_set_rel_tol", "dotmi_set_time_step", "dotmi_set_lame",
+    "dotmi_solve_hessian", "dotmi_set_pcg", "dotmi_pcg_info",
 ]
 
 _lib = None
@@ -151,6 +153,10 @@ def load() -> C.CDLL:
         L.dotmi_plan_ic.argtypes = [C.c_int32, C.c_int32, c_ip] + [c_ip] * 10
         L.dotmi_ic_info.argtypes = [H, c_ip, c_dp, c_ip]
         L.dotmi_ic_factor.argtypes = [H, C.c_int32, c_dp]
+    if hasattr(L, "dotmi_solve_hessian"):
+        L.dotmi_solve_hessian.argtypes = [H, c_dp, c_dp, C.c_double, C.c_int32, c_ip, c_dp]
+        L.dotmi_set_pcg.argtypes = [H, C.c_double, C.c_int32, C.c_int32]
+        L.dotmi_pcg_info.argtypes = [H, C.POINTER(C.c_int64), C.POINTER(C.c_int64), c_ip, c_dp]
     L.dotmi_plan_layout.argtypes = [C.c_int32, C.c_int32, c_ip, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32,
                                     C.c_int32, C.c_int32, C.c_int32, c_ip, c_ip, c_ip, c_ip]
     if hasattr(L, "dotmi_plan_backsolve_tiles"):   # (round 5 entry; guarded like the two above -- ADVICE r05)

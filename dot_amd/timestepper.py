@@ -283,6 +283,29 @@ class DOTTimeStepper:
         self._check(self._L.dotmi_ic_factor(self._h, nb, dp(F)), "ic_factor")
         return F
 
+    def solveHessian(self, b, rel_tol: float = 1e-8, max_iter: int = 500):
+        """H u = b with the handle's current projected Hessian by conjugate gradients on the subdomain factors (dotmi_solve_hessian)
+        -> (u (nV,3), iterations, |r|/|b|).  self.last_solve_status is the call's return value: 0 converged, 2 stopped at max_iter
+        or broke down (u is then the last iterate)."""
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        u = np.empty((self.nV, 3))
+        it, res = C.c_int32(), C.c_double()
+        rc = self._check(self._L.dotmi_solve_hessian(self._h, dp(b), dp(u), rel_tol, max_iter, C.cast(C.byref(it), _lib.c_ip),
+                                                     C.cast(C.byref(res), _lib.c_dp)), "solve_hessian")
+        self.last_solve_status = rc
+        return u, it.value, res.value
+
+    def setPCG(self, rel_tol: float = 1e-3, max_iter: int = 500, check_every: int = 8):
+        """the solves of a _lib.FLAG_NEWTON_PCG step: forcing term, iteration cap; iterations between two read-backs (dotmi_set_pcg)"""
+        self._check(self._L.dotmi_set_pcg(self._h, rel_tol, max_iter, check_every), "set_pcg")
+
+    def pcgInfo(self):
+        """(solves, iterations of all solves, iterations and |r|/|b| of the last one) since create (dotmi_pcg_info)"""
+        ns, ni, li, lr = C.c_int64(), C.c_int64(), C.c_int32(), C.c_double()
+        self._check(self._L.dotmi_pcg_info(self._h, C.byref(ns), C.byref(ni), C.cast(C.byref(li), _lib.c_ip),
+                                           C.cast(C.byref(lr), _lib.c_dp)), "pcg_info")
+        return ns.value, ni.value, li.value, lr.value
+
     def multiply(self, p) -> np.ndarray:
         p = np.ascontiguousarray(p, dtype=np.float64)
         out = np.empty((self.nV, 3))

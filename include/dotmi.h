@@ -169,9 +169,23 @@ enum {
                                      * and factors it: ms_hessian as usual, ms_factor = all attempts, precond_bytes = 72 x (lower
                                      * blocks + diagonals) x 2.  dotmi_apply_precond returns (L L^T)^-1 r; dotmi_spmv works.
                                      * Host-driven loop, single GPU: not with world > 1, FORCE_DIST, OWNER_EXCHANGE, GSDD, NEWTON,
-                                     * LBFGS_PD, ASYNC_REFRESH or a vpart.  dotmi_part_matrix, dotmi_part_size, dotmi_probe_direction,
+                                     * NEWTON_PCG, LBFGS_PD, ASYNC_REFRESH or a vpart.  dotmi_part_matrix, dotmi_part_size, dotmi_probe_direction,
                                      * dotmi_bench_precond and the bench kinds of the block solve and of the device loop return
                                      * DOTMI_E_INVALID on such a handle. */
+#define DOTMI_FLAG_NEWTON_PCG 2048   /* dotmi_step runs projected Newton like DOTMI_FLAG_NEWTON, with H p = -g solved by preconditioned
+                                     * conjugate gradients on the subdomain factors instead of by one factor of the whole mesh: any
+                                     * nParts >= 1, one subdomain factorisation plus a few dozen streaming block-solve applications per
+                                     * Newton iteration.  A GPU form of the method (the reference's Newton is CHOLMOD on one subdomain):
+                                     * the preconditioner is the SYMMETRIC scaling D^-1/2 S D^-1/2 of DOT's block solve D^-1 S (which
+                                     * is not symmetric and makes plain PCG diverge; they agree where dup = 1), the recurrences are the
+                                     * single-reduction form of Chronopoulos and Gear, convergence |r| <= eta |g| is decided on the
+                                     * device.  Per iteration: refresh and factorise at x, p = PCG(-g; eta, cap), line search from
+                                     * step 1; no refresh at the end of the step.  A solve that stops at its cap or breaks down hands
+                                     * over its iterate (a descent direction) and the step goes on.  eta = 1e-3, cap 500, a read-back
+                                     * every 8 iterations unless dotmi_set_pcg says otherwise.  stats.iters = Newton iterations,
+                                     * stats.backsolve_launches = block-solve applications (the CG iterations of the step's solves).
+                                     * Host-driven loop, single GPU: not with world > 1, FORCE_DIST, OWNER_EXCHANGE, GSDD, NEWTON,
+                                     * LBFGS_PD, LBFGS_HI, ASYNC_REFRESH or a vpart. */
 
 typedef struct {
     int32_t iters;        /* L-BFGS iterations (innerIterAmt delta, DOTTimeStepper.cpp:338) */
@@ -405,6 +419,22 @@ int dotmi_ic_info(dotmi_handle *h, int32_t *colours, double *shift, int32_t *att
 /* DOTMI_FLAG_LBFGS_HI handles: the factor's 3 x 3 blocks, row-major, in plan order -- the nL lower blocks, then the nV lower-triangular
  * diagonal blocks by order position.  Returns their number nL + nV (blocks == NULL: only that); cap: room in blocks, in blocks. */
 int dotmi_ic_factor(dotmi_handle *h, int32_t cap, double *blocks);
+/* Newton-PCG (dot_amd/csrc/dotmi_pcg.hip): solve H u = b with the handle's current global projected Hessian (fixed rows are
+ * identity) from u = 0 by conjugate gradients preconditioned with D^-1/2 S D^-1/2, S = the sum of the handle's current subdomain
+ * solves.  b, u: nV*3.  Stops when the recursive residual |r| <= rel_tol |b|, after max_iter iterations, or on breakdown (a
+ * non-positive or non-finite r.M r or curvature: NaN or rounding, H and the preconditioner being SPD); *iters = iterations done,
+ * *rel_res = |r| / |b| at exit (either may be NULL); b = 0 returns u = 0 after 0 iterations.  Two solves of one system are
+ * bit-identical, whatever the read-back interval.  Any single-rank handle that has both H and the block solve (DOT, two-level form,
+ * Newton, a vpart); DOTMI_E_INVALID on LBFGS-PD, LBFGS-HI, GSDD and sharded handles, NULL b or u, rel_tol <= 0 or non-finite,
+ * max_iter < 1.  Returns 0 converged, 2 cap or breakdown (u is the last iterate), < 0 error. */
+int dotmi_solve_hessian(dotmi_handle *h, const double *b, double *u, double rel_tol, int32_t max_iter, int32_t *iters,
+                        double *rel_res);
+/* the settings of DOTMI_FLAG_NEWTON_PCG's solves (rel_tol = the forcing term eta, max_iter) and, for dotmi_solve_hessian too, the
+ * iterations enqueued between two reads of the device's verdict (check_every >= 1).  A bad value returns DOTMI_E_INVALID and
+ * changes nothing.  No device work. */
+int dotmi_set_pcg(dotmi_handle *h, double rel_tol, int32_t max_iter, int32_t check_every);
+/* counters of the handle's PCG solves since create (steps and dotmi_solve_hessian alike); any pointer may be NULL */
+int dotmi_pcg_info(const dotmi_handle *h, int64_t *solves, int64_t *iters_total, int32_t *last_iters, double *last_rel_res);
 
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* Launch the subdomain back-solve kernel `reps` times on the handle's stream between two HIP events
