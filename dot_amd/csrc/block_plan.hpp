@@ -406,9 +406,11 @@ struct ScheduleRules {
     int eagerMinRmul = -1;         // DOTMI_TILE_EAGER_MIN_RMUL
     bool eagerMinRmulByUser = false;
     int tileFlow = -1;             // DOTMI_TILE_FLOW
+    int groups = 1;                // subdomain groups of the level launches (tile_factor.hpp; the dataflow launch has one)
 };
 struct FactorSchedule {
-    TileSchedule S;
+    TileSchedule S;                    // with its per-group level ranges and clear tiles (S.groupLevel, S.clearStart)
+    std::vector<int> fillPerm, fillStart;   // the dense fill's entries group by group (partition_by_group)
     bool flow = false;                 // the dataflow launch (tile_flow_kernel) instead of one launch per level
     std::vector<int> depPtr, depIdx;   // its dependencies
 };
@@ -447,25 +449,34 @@ inline void plan_factor_schedule(int nParts, int nmax, const std::vector<int> &d
     // like any other task and saves the partial sum's round trip (1 M tets 15.5 -> 14.5 ms)
     const int eagerMinRmul = R.eagerMinRmul >= -1 && R.eagerMinRmulByUser ? R.eagerMinRmul : (nParts <= 64 ? 1 : -1);
     TileSchedule &S = out.S;
+    std::vector<SubdomainTiles> subs(nParts);
+    size_t nTasks = 0;
+    int maxLevel = 0;
     {
-        std::vector<TileTaskL> all;
         size_t sn = 0;
         for (int ls = 0; ls < nParts; ++ls) {
             const size_t at = (size_t)ls * nt;
-            plan_subdomain_tiles(ls, nt, W, &rt.off[at], &rt.ld[at], &rt.c0[at], live[ls], pat[ls], W2, sn, all, S.clearTiles,
-                                 S.clearLd, S.flops, S.qTiles, eagerMin, eagerChunk, 0, true, eagerMinRmul,
+            plan_subdomain_tiles(ls, nt, W, &rt.off[at], &rt.ld[at], &rt.c0[at], live[ls], pat[ls], W2, sn, subs[ls].tasks,
+                                 subs[ls].clearTiles, subs[ls].clearLd, S.flops, S.qTiles, eagerMin, eagerChunk, 0, true, eagerMinRmul,
                                  leafTile ? &rtM.off[at] : nullptr, leafTile ? &rtM.ld[at] : nullptr,
                                  leafTile ? &rtM.c0[at] : nullptr, leafTile);
+            nTasks += subs[ls].tasks.size();
+            for (auto &t : subs[ls].tasks) maxLevel = std::max(maxLevel, t.level);
         }
-        finish_tile_schedule(all, S);
     }
     // Dataflow or levels (profiles/r04_factor_flow.txt): per task the dataflow launch pays a ticket, a look at its
     // dependencies' flags and write-through stores, and it runs the level kernel's 77 KB workgroups -- it wins where the
     // levels are launches of less than one round of workgroups, i.e. the chain of dependent tasks paces the phase
     // (bunny5K / 8 subdomains: 217 tasks per level, 0.57 -> 0.41 ms), and loses where the levels are several rounds
     // (bar17K / 32: 1000 per level, 1.11 -> 1.21 ms; 1 M tets: 15 -> 23 ms).
-    const size_t nLevels = std::max<size_t>(S.levelStart.size() - 1, 1);
-    out.flow = !S.tasks.empty() && (R.tileFlow > 0 || (R.tileFlow < 0 && S.tasks.size() / nLevels <= 512));
+    const size_t nLevels = (size_t)std::max(maxLevel, 1);
+    out.flow = nTasks > 0 && (R.tileFlow > 0 || (R.tileFlow < 0 && nTasks / nLevels <= 512));
+    finish_grouped_schedule(subs, out.flow ? 1 : R.groups, S);
+    {
+        std::vector<int> subOf(fillBlk.size());
+        for (size_t e = 0; e < fillBlk.size(); ++e) subOf[e] = fillBlk[e].x;
+        partition_by_group(subOf.data(), subOf.size(), S.groupOf, (int)S.groupLevel.size() - 1, out.fillPerm, out.fillStart);
+    }
     if (out.flow) {
         build_tile_deps(S.tasks, S.prods, out.depPtr, out.depIdx);
         if (out.depIdx.empty()) out.depIdx.push_back(0);

@@ -518,6 +518,21 @@ static int upload_merge_lists(dotmi_handle *h, const MergeLists &M)
 
 // the tile schedule of the factorisation -> device, and what its launch form needs (flags and counters of the dataflow launch,
 // the side stream and events of the split levels)
+static bool tile_split_levels(const Tuning &tune, int nParts) { return tune.tileSplit >= 0 ? tune.tileSplit != 0 : nParts > 64; }
+
+// Subdomain groups of the level launches (DOTMI_TILE_GROUPS; profiles/r07_factor_groups.txt).  Two by default wherever the
+// levels run as one launch each: bar17K / 32 subdomains 0.979 -> 0.893 ms per factorisation, kingkong18K / 18 1.155 -> 1.046,
+// the stiff monkey / 64 0.549 -> 0.507; three groups are level with two on the latter two and behind on bar17K, four lose again
+// (every chain's diagonal-paced levels then hold slots the others' bulk levels want).  The split levels keep their one chain
+// (their diagonal tasks already run beside the rest), and beside st there are at most three streams -- a process has four
+// hardware queues.
+static int choose_tile_groups(const Tuning &tune, int nParts)
+{
+    if (tile_split_levels(tune, nParts)) return 1;
+    const int G = tune.tileGroups >= 0 ? tune.tileGroups : 2;
+    return std::max(1, std::min(G, 4));
+}
+
 static int upload_factor_schedule(dotmi_handle *h, const FactorSchedule &FS)
 {
     const TileSchedule &S = FS.S;
@@ -528,7 +543,8 @@ static int upload_factor_schedule(dotmi_handle *h, const FactorSchedule &FS)
     h->nTclear = (int)S.clearTiles.size();
     h->tlevelStart = S.levelStart;
     h->tlevelDiag = S.levelDiag;
-    h->tileSplit = h->tune.tileSplit >= 0 ? h->tune.tileSplit != 0 : h->P.nParts > 64;
+    h->tgroupLevel = S.groupLevel;
+    h->tileSplit = tile_split_levels(h->tune, h->P.nParts);
     h->nTtasks = (int)S.tasks.size();
     h->tileFlow = FS.flow;
     // the diagonal tasks' per-lane bottom steps (k_tilefactor.hip, block_chol_inv<N, FAST>): every layout (DOTMI_FAST_DIAG=0: the
@@ -548,6 +564,17 @@ static int upload_factor_schedule(dotmi_handle *h, const FactorSchedule &FS)
         if (h->tune.fuseLog)
             fprintf(stderr, "dotmi: tile dataflow: %zu tasks, %zu dependencies, %d workgroups\n", S.tasks.size(), FS.depIdx.size(),
                     h->tileFlowWg);
+    }
+    if (h->tgroupLevel.size() > 2) {   // one stream per group beside st, one fork event, one join event per stream
+        h->stGroup.assign(h->tgroupLevel.size() - 2, nullptr);
+        h->evGroupJoin.assign(h->stGroup.size(), nullptr);
+        for (auto &s : h->stGroup) HIPCHECK(h, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        HIPCHECK(h, hipEventCreateWithFlags(&h->evGroupFork, hipEventDisableTiming));
+        for (auto &e : h->evGroupJoin) HIPCHECK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        if (h->tune.fuseLog)
+            for (size_t g = 0; g + 1 < h->tgroupLevel.size(); ++g)
+                fprintf(stderr, "dotmi: tile group %zu: %d levels, %d tasks\n", g, h->tgroupLevel[g + 1] - h->tgroupLevel[g],
+                        h->tlevelStart[h->tgroupLevel[g + 1]] - h->tlevelStart[h->tgroupLevel[g]]);
     }
     if (h->tileSplit) {
         HIPCHECK(h, hipStreamCreateWithFlags(&h->stDiag, hipStreamNonBlocking));
@@ -673,7 +700,9 @@ int build_device_mesh(dotmi_handle *h)
         if (int rc = dalloc(h, &h->W2, std::max<size_t>(F.wTotal, 64))) return rc;
         FactorSchedule FS;
         plan_factor_schedule(P.nParts, P.nmax, rows.dofmap, fill.fillBlk, rt, rtM, L.twoLevel ? F.leafTile.data() : nullptr, P.W, h->W2,
-                             ScheduleRules{tune.tileEagerMin, tune.tileEagerMinRmul, tune.tileEagerMinRmulByUser, tune.tileFlow}, FS);
+                             ScheduleRules{tune.tileEagerMin, tune.tileEagerMinRmul, tune.tileEagerMinRmulByUser, tune.tileFlow,
+                                           choose_tile_groups(tune, P.nParts)},
+                             FS);
         if (int rc = upload_factor_schedule(h, FS)) return rc;
     }
     if (int rc = dalloc(h, &P.ppart, (size_t)P.nParts * P.nbmax * P.nmax)) return rc;
@@ -910,6 +939,87 @@ int dotmi_plan_tile_schedule_two_level(int32_t nt, const uint8_t *live, const ui
                                    nullptr, row_off, row_ld, leaf_tile, c0m, ntm, row_off_m, row_ld_m);
 }
 
+// host-only: the subdomain groups of the level launches (tile_factor.hpp, plan_tile_groups): group_of[i] for n_parts weights;
+// returns the number of groups used (groups clamped to [1, n_parts]), or an error
+int dotmi_plan_tile_groups(int32_t n_parts, const int64_t *weight, int32_t groups, int32_t *group_of)
+{
+    if (n_parts < 1 || !weight || !group_of) return DOTMI_E_INVALID;
+    std::vector<long long> w(weight, weight + n_parts);
+    std::vector<int> g(n_parts, 0);
+    const int G = plan_tile_groups(n_parts, w.data(), groups, g.data());
+    std::copy(g.begin(), g.end(), group_of);
+    return G;
+}
+
+// host-only: the grouped level table plan_factor_schedule builds, for n_blocks blocks of nt x nt tiles (live / pattern per block,
+// every row block stored from tile column 0, block b's storage behind block b - 1's).
+//   tasks: 6 int64 per task, in the order of the task array {group, level inside the group (from 1), block, offset of the tile
+//          written, post, products};  clear: 2 int64 per cleared tile {group, offset};  group_level[g + 1] - group_level[g] =
+//          levels of group g;  fill_perm / fill_start: the n_fill entries of a list whose entry e belongs to block fill_sub[e],
+//          group by group (partition_by_group).
+// With tasks == NULL only the counts are returned.  Returns the number of groups used.  tests/test_tile_groups.py
+int dotmi_plan_grouped_tile_schedule(int32_t n_blocks, int32_t nt, const uint8_t *live, const uint8_t *pattern, int32_t eager_min,
+                                     int32_t eager_chunk, int32_t groups, int64_t *tasks, int64_t *n_tasks, int32_t *group_of,
+                                     int32_t *group_level, int64_t *clear, int64_t *n_clear, int32_t n_fill, const int32_t *fill_sub,
+                                     int32_t *fill_perm, int32_t *fill_start)
+{
+    if (n_blocks < 1 || nt < 1 || !live || !pattern || !n_tasks || !n_clear || n_fill < 0 || (n_fill > 0 && !fill_sub))
+        return DOTMI_E_INVALID;
+    for (int e = 0; e < n_fill; ++e)
+        if (fill_sub[e] < 0 || fill_sub[e] >= n_blocks) return DOTMI_E_INVALID;
+    std::vector<long long> rtOff(nt);
+    std::vector<int> rtLd(nt), rtC0(nt, 0);
+    long long tot = 0;
+    for (int j = 0; j < nt; ++j) {
+        rtLd[j] = 64 * (j + 1);
+        rtOff[j] = tot;
+        tot += 64ll * rtLd[j];
+    }
+    double *const W = reinterpret_cast<double *>(1ull << 40);   // never dereferenced: only offsets leave this function
+    double *const W2 = W + (long long)n_blocks * tot;
+    std::vector<SubdomainTiles> subs(n_blocks);
+    TileSchedule S;
+    size_t sn = 0;
+    for (int b = 0; b < n_blocks; ++b) {
+        std::vector<uint8_t> lv(live + (size_t)b * nt, live + (size_t)(b + 1) * nt);
+        std::vector<uint8_t> pat(pattern + (size_t)b * nt * nt, pattern + (size_t)(b + 1) * nt * nt);
+        std::vector<long long> off(rtOff);
+        for (auto &o : off) o += b * tot;
+        plan_subdomain_tiles(b, nt, W, off.data(), rtLd.data(), rtC0.data(), lv, pat, W2, sn, subs[b].tasks, subs[b].clearTiles,
+                             subs[b].clearLd, S.flops, S.qTiles, std::max(1, eager_min), std::max(1, eager_chunk));
+    }
+    finish_grouped_schedule(subs, groups, S);
+    const int G = (int)S.groupLevel.size() - 1;
+    *n_tasks = (int64_t)S.tasks.size();
+    *n_clear = (int64_t)S.clearTiles.size();
+    if (!tasks) return G;
+    if (!group_of || !group_level || !clear || !fill_perm || !fill_start) return DOTMI_E_INVALID;
+    std::copy(S.groupOf.begin(), S.groupOf.end(), group_of);
+    std::copy(S.groupLevel.begin(), S.groupLevel.end(), group_level);
+    for (int g = 0; g < G; ++g) {
+        for (int l = S.groupLevel[g]; l < S.groupLevel[g + 1]; ++l)
+            for (int k = S.levelStart[l]; k < S.levelStart[l + 1]; ++k) {
+                const TileTask &t = S.tasks[k];
+                int64_t *o = tasks + 6 * (size_t)k;
+                o[0] = g;
+                o[1] = l - S.groupLevel[g] + 1;
+                o[2] = t.sub;
+                o[3] = t.o - W;
+                o[4] = t.post;
+                o[5] = t.nprod;
+            }
+        for (int k = S.clearStart[g]; k < S.clearStart[g + 1]; ++k) {
+            clear[2 * (size_t)k] = g;
+            clear[2 * (size_t)k + 1] = S.clearTiles[k] - W;
+        }
+    }
+    std::vector<int> perm, start;
+    partition_by_group(fill_sub, (size_t)n_fill, S.groupOf, G, perm, start);
+    std::copy(perm.begin(), perm.end(), fill_perm);
+    std::copy(start.begin(), start.end(), fill_start);
+    return G;
+}
+
 // host-only: the dependencies the dataflow kernel (tile_flow_kernel) waits on, for the task list dotmi_plan_tile_schedule
 // returns (same arguments, same task order): task v may run once the tasks dep_idx[dep_ptr[v] .. dep_ptr[v+1]) have finished.
 // With dep_idx == NULL only *n_deps is returned.  tests/test_tile_schedule.py executes the tasks in random orders that
@@ -1083,6 +1193,14 @@ int32_t dotmi_factor_kind(const dotmi_handle *h)
     return h->tileFlow ? 2 : h->tileSplit ? 3 : 1;
 }
 
+// the independent launch chains of the factorisation: the subdomain groups of the level launches (1: one chain, the dataflow
+// launch and the split levels included)
+int32_t dotmi_factor_groups(const dotmi_handle *h)
+{
+    if (!h) return DOTMI_E_INVALID;
+    return h->tgroupLevel.size() > 2 ? (int32_t)h->tgroupLevel.size() - 1 : 1;
+}
+
 // host-only: the form of the block solve dotmi_create chooses for this mesh and partition when DOTMI_TWO_LEVEL is unset (0 = explicit
 // inverse in one pass, 1 = two-level), and the bytes per application of the one-pass form on its own layout, counted over all
 // subdomains, that decide it (>= 240 MB and a tree with separators: two-level)
@@ -1140,6 +1258,11 @@ void dotmi_destroy(dotmi_handle *h)
     for (hipEvent_t e : h->tFork) hipEventDestroy(e);
     for (hipEvent_t e : h->tJoin) hipEventDestroy(e);
     if (h->stDiag) hipStreamDestroy(h->stDiag);
+    if (h->evGroupFork) hipEventDestroy(h->evGroupFork);
+    for (hipEvent_t e : h->evGroupJoin)
+        if (e) hipEventDestroy(e);
+    for (hipStream_t s : h->stGroup)
+        if (s) hipStreamDestroy(s);
     for (hipEvent_t e : h->evPre) hipEventDestroy(e);
     for (hipEvent_t e : h->evAr) hipEventDestroy(e);
     if (h->factorGraph) hipGraphExecDestroy(h->factorGraph);

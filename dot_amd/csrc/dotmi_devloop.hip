@@ -137,7 +137,7 @@ static void slot_backsolve(dotmi_handle *h, const Slot &s)
     CtlArgs ca{h->ctl, s.ctlE, ctlR, h->alpha_dev, h->h_flags, s.nb, h->pairNow ? 2 : 0};
     (h->pairNow ? (h->vpNow ? launch_gemv_pair_vp : launch_gemv_pair) : h->specNow ? launch_gemv_spec : h->vpNow ? launch_gemv_vp : launch_gemv)(
         h->P, nullptr, h->st, h->ctl, br.ev0, br.ev1, &ca,
-        h->tune.earlyAbort ? (int)h->slotTimed.size() /* the slot's epoch, 1-based */ : (1 << 30) /* never stopped */);
+        (int)h->slotTimed.size() /* the slot's epoch, 1-based */);
 }
 
 // stage 5, merge: z = u - sum_j xi_j (M y_j) from the tile partials and the cached M y_j
@@ -252,12 +252,12 @@ static void choose_step_forms(dotmi_handle *h)
     h->earlyNow = h->earlyBs;
     // paired trials: one rank, the fused step inside the element pass, the early order with held launches (the tiles of a paired
     // slot wait for the verdict); -1: only in steps that follow a step with halvings in at least a quarter of its iterations
-    h->pairNow = h->earlyNow && !h->dist && h->tune.fuseStep && h->tune.fuseDir && h->tune.earlyAbort && h->tune.earlyHold &&
+    h->pairNow = h->earlyNow && !h->dist && h->tune.fuseStep && h->tune.fuseDir && h->tune.earlyHold &&
                  (h->tune.pairTrials > 0 || (h->tune.pairTrials < 0 && h->prevIters > 0 && 4 * h->prevHalv >= h->prevIters));
     // the unit step speculatively beside the direction kernel: one rank, the fused kernels, every patch a workgroup, no pairing
     // in this step (a step whose predecessor halved often); -1: only after a step whose first trials took the unit estimate at
     // least nine times in ten (a slot whose estimate is below 1 is redone: ~45 us lost against ~10 saved)
-    h->specNow = h->earlyNow && !h->dist && !h->pairNow && h->tune.fuseStep && h->tune.fuseDir && h->tune.earlyAbort &&
+    h->specNow = h->earlyNow && !h->dist && !h->pairNow && h->tune.fuseStep && h->tune.fuseDir &&
                  h->specFits &&
                  (h->tune.specStep > 0 || (h->tune.specStep < 0 && h->prevFirst > 0 && 10 * h->prevUnit >= 9 * h->prevFirst));
     // the trial's element pass + gather as one launch on vertex patches (paired steps too: elem_vertex_kernel<MAT, true>); a step that
@@ -293,7 +293,7 @@ static int init_devloop(dotmi_handle *h, int *notifyFrom)
     }
     C.u_old = h->u_old;
     devloop_resolve(C);   // (slot 0, no pair yet)
-    C.holdEnable = h->tune.earlyHold && h->tune.earlyAbort ? 1 : 0;
+    C.holdEnable = h->tune.earlyHold ? 1 : 0;
     // the forecast carries over from the last step (a function of the handle's own history)
     memcpy(C.predHist, h->predState, sizeof(int) * 2);
     memcpy(&C.predCtr[0][0], h->predState + 2, sizeof(int) * 8);

@@ -85,6 +85,8 @@ struct Tuning {
     int patchElems = 0;       // DOTMI_PATCH_ELEMS    elements per patch of the element pass (0: default)
     int tileSplit = -1;       // DOTMI_TILE_SPLIT     0 / 1: one task kernel per level / diagonal and half-tile kernels side by side
                               //                      (-1: the latter above 64 subdomains, where the factorisation is throughput-bound)
+    int tileGroups = -1;      // DOTMI_TILE_GROUPS    the level launches of the factorisation as G independent chains of subdomain groups,
+                              //                      each on a stream of its own (0 / 1: one chain; at most 4; -1: two -- choose_tile_groups)
     int tileEagerMin = 0;     // DOTMI_TILE_EAGER_MIN early products a critical-path tile task may keep
     int fastDiag = 1;         // DOTMI_FAST_DIAG      1 / 0: the diagonal tile tasks' 16 x 16 bottom steps on 4 x 4 blocks every lane factors for
                               //                      itself (12.0 us per 64 x 64 step) / one row per lane with v_readlane operands (15.3 us)
@@ -96,7 +98,6 @@ struct Tuning {
     bool tileEagerMinRmulByUser = false;   //           (unset: one up to 64 subdomains, as the others above)
     bool fuseDir = true;      // DOTMI_FUSE_DIR=0     (early order) build_p and spmv_dots as two launches instead of one on cached H s_j
     bool fuseStep = true;     // DOTMI_FUSE_STEP=0    (early order) step_forward as a launch of its own instead of inside the element pass
-    bool earlyAbort = true;   // DOTMI_EARLY_ABORT=0  (ablation) speculative back-solves run to their end even when the trial is rejected
     int pairTrials = -1;      // DOTMI_PAIR_TRIALS    -1 (default): paired line-search trials (StepArgs::pairBlocks) in a step whose predecessor
                               //                      halved in at least a quarter of its iterations; 1: in every step; 0: never
     int vertexPatches = -1;   // DOTMI_VERTEX_PATCHES 0: the element pass and the vertex gather of a trial as two launches on element patches
@@ -137,6 +138,7 @@ struct Tuning {
         t.timeStride = std::max(1, geti("DOTMI_TIME_STRIDE", 8));
         t.patchElems = std::max(0, geti("DOTMI_PATCH_ELEMS", 0));
         t.tileSplit = geti("DOTMI_TILE_SPLIT", -1);
+        t.tileGroups = geti("DOTMI_TILE_GROUPS", -1);
         t.tileEagerMin = std::max(0, geti("DOTMI_TILE_EAGER_MIN", 0));
         t.tileFlow = geti("DOTMI_TILE_FLOW", -1);
         t.fastDiag = geti("DOTMI_FAST_DIAG", 1);
@@ -144,7 +146,6 @@ struct Tuning {
         t.tileEagerMinRmul = geti("DOTMI_TILE_EAGER_MIN_RMUL", -1);
         t.tileEagerMinRmulByUser = getenv("DOTMI_TILE_EAGER_MIN_RMUL") != nullptr;
         t.earlyBs = geti("DOTMI_EARLY_BACKSOLVE", 2) != 0 ? 2 : 0;   // (1, round 3's per-step rule, now means "on")
-        t.earlyAbort = geti("DOTMI_EARLY_ABORT", 1) != 0;
         t.earlyHold = geti("DOTMI_EARLY_HOLD", 1) != 0;
         t.pairTrials = geti("DOTMI_PAIR_TRIALS", -1);
         t.specStep = geti("DOTMI_SPEC_STEP", 0);
@@ -216,6 +217,12 @@ struct dotmi_handle {
     double *W2 = nullptr;             // tile factorisation: the work buffer (H, then R), laid out like P.W (which holds Q only)
     int nTclear = 0;
     std::vector<int> tlevelStart, tlevelDiag;
+    // subdomain groups (tile_factor.hpp): group g runs the levels [tgroupLevel[g], tgroupLevel[g + 1]) of the two tables above --
+    // group 0 on st, group g > 0 on stGroup[g - 1], one fork in front of all chains and one join behind them (issue_factor)
+    std::vector<int> tgroupLevel;
+    std::vector<hipStream_t> stGroup;
+    hipEvent_t evGroupFork = nullptr;
+    std::vector<hipEvent_t> evGroupJoin;
     bool tileSplit = false;
     int predState[10] = {0, 0, 1, 1, 1, 1, 1, 1, 1, 1};   // DevLoop::predHist / predCtr between the steps
     int heldSlots = 0, heldRejected = 0;                  // held back-solves of the last step (DevLoop::holdNext)

@@ -4,6 +4,7 @@
 namespace dotmi {
 
 // issue the tile factorisation of every owned subdomain on h->st (tile_factor.hpp): one dataflow launch, or one launch per level
+// (of every subdomain group, on the groups' streams: joined into h->st before this returns)
 int issue_factor(dotmi_handle *h)
 {
     if (h->tileFlow) {
@@ -12,7 +13,28 @@ int issue_factor(dotmi_handle *h)
         h->flopCount = h->tileFlops;
         return 0;
     }
-    {
+    if (h->tgroupLevel.size() > 2) {
+        // Subdomain groups: every group's levels in order on a stream of its own (group 0 on st), nothing between the chains
+        // but one fork in front and one join behind -- the groups share no tile.  The launches are issued level by level
+        // across the groups, so that no chain waits for the host to finish another one's.
+        const size_t G = h->tgroupLevel.size() - 1;
+        HIPCHECK(h, hipEventRecord(h->evGroupFork, h->st));
+        for (hipStream_t s : h->stGroup) HIPCHECK(h, hipStreamWaitEvent(s, h->evGroupFork, 0));
+        for (int k = 0, more = 1; more; ++k) {
+            more = 0;
+            for (size_t g = 0; g < G; ++g) {
+                const int l = h->tgroupLevel[g] + k;
+                if (l >= h->tgroupLevel[g + 1]) continue;
+                more = 1;
+                launch_tile_level(h->ttasks + h->tlevelStart[l], h->tlevelStart[l + 1] - h->tlevelStart[l], h->tprods, h->info_dev,
+                                  g == 0 ? h->st : h->stGroup[g - 1], h->fastDiag);
+            }
+        }
+        for (size_t g = 1; g < G; ++g) {
+            HIPCHECK(h, hipEventRecord(h->evGroupJoin[g - 1], h->stGroup[g - 1]));
+            HIPCHECK(h, hipStreamWaitEvent(h->st, h->evGroupJoin[g - 1], 0));
+        }
+    } else {
         // one launch per level of the static tile schedule; a launch boundary is the only synchronisation
         for (size_t l = 0; l + 1 < h->tlevelStart.size(); ++l) {
             const int n = h->tlevelStart[l + 1] - h->tlevelStart[l];

@@ -70,6 +70,11 @@ struct TileSchedule {
     std::vector<double *> clearTiles; // origins of the tiles the fill writes into (cleared before the refill; fill-in tiles are
                                       // written before they are read)
     std::vector<int> clearLd;         // and their leading dimensions
+    // subdomain groups (finish_grouped_schedule): the tasks, products, levels and clear tiles of group g lie behind those of
+    // group g - 1; one group = the schedule as a whole
+    std::vector<int> groupOf;         // owned subdomain -> group
+    std::vector<int> groupLevel;      // the levels of group g are entries [groupLevel[g], groupLevel[g + 1]) of levelStart / levelDiag
+    std::vector<int> clearStart;      // its clear tiles are [clearStart[g], clearStart[g + 1])
     size_t scratchTiles = 0;          // 64 x 64 scratch tiles needed (none since round 5)
     double flops = 0;                 // FP64 flop of one factorisation as executed
     long long liveTiles = 0, qTiles = 0;
@@ -320,15 +325,15 @@ inline void plan_subdomain_tiles(int sub, int nt, double *W, const long long *rt
     for (size_t k = 0; k < n; ++k) out[o0 + k].level = fin[k];
 }
 
-// merge the per-subdomain task lists into level order
+// merge the per-subdomain task lists into level order; the levels are appended to the ones S already holds (the groups of
+// finish_grouped_schedule follow each other in one task array)
 inline void finish_tile_schedule(std::vector<TileTaskL> &all, TileSchedule &S, bool xcdGroups = true)
 {
     int maxLevel = 0;
     for (auto &t : all) maxLevel = std::max(maxLevel, t.level);
     std::vector<std::vector<size_t>> byLevel(maxLevel + 1);
     for (size_t k = 0; k < all.size(); ++k) byLevel[all[k].level].push_back(k);
-    S.levelStart.assign(1, 0);
-    S.levelDiag.clear();
+    if (S.levelStart.empty()) S.levelStart.assign(1, 0);
     for (int l = 1; l <= maxLevel; ++l) {
         // Order inside a level: tasks of the same subdomain and target row read the same A tiles (R_mk / Q_im), so
         // they are made neighbours ON ONE XCD -- workgroup b runs on XCD b % 8, each XCD has its own 4 MB L2 -- and their
@@ -396,6 +401,79 @@ inline void finish_tile_schedule(std::vector<TileTaskL> &all, TileSchedule &S, b
         }
         S.levelStart.push_back((int)S.tasks.size());
     }
+}
+
+// ---- subdomain groups ---------------------------------------------------------------------------------------------------------
+// Subdomains share no tile, so the level chain of one set of subdomains needs nothing from another set's: split into G groups,
+// every group is a schedule of its own whose launches go to a stream of its own (dotmi_refresh.hip, issue_factor) -- while
+// one group sits in a level its diagonal task paces, or in the part-empty last round of a bulk level, another group's tasks take
+// the free workgroup slots.
+// Longest processing time first: the subdomains by falling weight (ties: by index) each into the lightest group so far (ties:
+// the one with fewer members, then the lower index -- so no group stays empty even among zero weights).  Returns the number of
+// groups used, G clamped to [1, nParts].
+inline int plan_tile_groups(int nParts, const long long *weight, int G, int *groupOf)
+{
+    G = std::max(1, std::min(G, nParts));
+    std::vector<int> ord(std::max(nParts, 0));
+    for (int i = 0; i < nParts; ++i) ord[i] = i;
+    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return weight[a] > weight[b]; });
+    std::vector<long long> load(G, 0);
+    std::vector<int> members(G, 0);
+    for (int i : ord) {
+        int g = 0;
+        for (int y = 1; y < G; ++y)
+            if (load[y] < load[g] || (load[y] == load[g] && members[y] < members[g])) g = y;
+        groupOf[i] = g;
+        load[g] += weight[i];
+        ++members[g];
+    }
+    return G;
+}
+
+// what plan_subdomain_tiles leaves for ONE subdomain
+struct SubdomainTiles {
+    std::vector<TileTaskL> tasks;
+    std::vector<double *> clearTiles;
+    std::vector<int> clearLd;
+};
+
+// the subdomains dealt to G groups by their product counts, finish_tile_schedule once per group (the dealing to the XCD lanes
+// stays inside a group), the groups' arrays one behind the other.  G = 1: the schedule over all subdomains.
+inline void finish_grouped_schedule(std::vector<SubdomainTiles> &subs, int G, TileSchedule &S)
+{
+    const int n = (int)subs.size();
+    std::vector<long long> weight(n, 0);
+    for (int s = 0; s < n; ++s)
+        for (auto &t : subs[s].tasks) weight[s] += (long long)t.prods.size();
+    S.groupOf.assign(n, 0);
+    G = plan_tile_groups(n, weight.data(), G, S.groupOf.data());
+    S.groupLevel.assign(1, 0);
+    S.clearStart.assign(1, 0);
+    for (int g = 0; g < G; ++g) {
+        std::vector<TileTaskL> all;
+        for (int s = 0; s < n; ++s) {
+            if (S.groupOf[s] != g) continue;
+            for (auto &t : subs[s].tasks) all.push_back(std::move(t));
+            S.clearTiles.insert(S.clearTiles.end(), subs[s].clearTiles.begin(), subs[s].clearTiles.end());
+            S.clearLd.insert(S.clearLd.end(), subs[s].clearLd.begin(), subs[s].clearLd.end());
+        }
+        finish_tile_schedule(all, S);
+        S.groupLevel.push_back((int)S.levelDiag.size());
+        S.clearStart.push_back((int)S.clearTiles.size());
+    }
+}
+
+// the entries of a list that is ordered by subdomain (the dense fill's: FillLists, block_plan.hpp) group by group: perm = the
+// entries' indices, those of group g at [start[g], start[g + 1]), each group's in their old order
+inline void partition_by_group(const int *subOfEntry, size_t nEntries, const std::vector<int> &groupOf, int G, std::vector<int> &perm,
+                               std::vector<int> &start)
+{
+    start.assign((size_t)G + 1, 0);
+    for (size_t e = 0; e < nEntries; ++e) ++start[(size_t)groupOf[subOfEntry[e]] + 1];
+    for (int g = 0; g < G; ++g) start[g + 1] += start[g];
+    std::vector<int> at(start.begin(), start.end() - 1);
+    perm.resize(nEntries);
+    for (size_t e = 0; e < nEntries; ++e) perm[at[groupOf[subOfEntry[e]]]++] = (int)e;
 }
 
 // ---- dependencies of the ordered task list, for the dataflow kernel (tile_flow_kernel, k_tilefactor.hip) ------------------------

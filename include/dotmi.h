@@ -295,6 +295,19 @@ int dotmi_plan_tile_schedule_two_level(int32_t nt, const uint8_t *live, const ui
  * order as dotmi_plan_tile_schedule; dep_idx == NULL returns the count only. */
 int dotmi_plan_tile_deps(int32_t nt, const uint8_t *live, const uint8_t *pattern, const int32_t *c0, int32_t eager_min,
                          int32_t eager_chunk, int64_t *dep_ptr, int64_t *dep_idx, int64_t *n_deps);
+/* (host only) the subdomain groups of the factorisation's level launches (DOTMI_TILE_GROUPS; dot_amd/csrc/tile_factor.hpp): the
+ * subdomains by falling weight, each into the lightest group so far.  group_of[n_parts]; returns the number of groups used (groups
+ * clamped to [1, n_parts]) or an error.  tests/test_tile_groups.py */
+int dotmi_plan_tile_groups(int32_t n_parts, const int64_t *weight, int32_t groups, int32_t *group_of);
+/* (host only) the grouped level table for n_blocks blocks of nt x nt tiles (live[n_blocks * nt], pattern[n_blocks * nt * nt]; every
+ * row block stored from tile column 0, the blocks' storage one behind the other): tasks, 6 int64 each in the order of the task array
+ * {group, level inside the group, block, offset of the tile written, post, products}; clear, 2 int64 per cleared tile {group,
+ * offset}; group_of[n_blocks]; group_level[groups + 1]; and a list of n_fill entries (entry e of block fill_sub[e]) group by group:
+ * fill_perm[n_fill], fill_start[groups + 1].  tasks == NULL: the counts only.  Returns the number of groups used or an error. */
+int dotmi_plan_grouped_tile_schedule(int32_t n_blocks, int32_t nt, const uint8_t *live, const uint8_t *pattern, int32_t eager_min,
+                                     int32_t eager_chunk, int32_t groups, int64_t *tasks, int64_t *n_tasks, int32_t *group_of,
+                                     int32_t *group_level, int64_t *clear, int64_t *n_clear, int32_t n_fill, const int32_t *fill_sub,
+                                     int32_t *fill_perm, int32_t *fill_start);
 /* (host only) the job table of the back-solve launches dotmi_create builds for parts [p0, p1) of this mesh: how the rows of every
  * tree region are cut into tiles, which launch / kernel form takes them and which workgroup runs them (dot_amd/csrc/bs_tiles.hpp;
  * the reference has no counterpart: CHOLMODSolver::solve, CHOLMODSolver.cpp:149-163, walks CHOLMOD's supernodes).  tiles: up to cap
@@ -389,6 +402,9 @@ int64_t dotmi_factor_storage_bytes(const dotmi_handle *h);
  * (tile_task_kernel), 2 = tile tasks as one dataflow launch (tile_flow_kernel), 3 = one launch pair per level: the diagonal
  * tasks in tile_task_kernel beside the product / row / inverse tasks on half tiles in tile_gemm_kernel (above 64 subdomains) */
 int32_t dotmi_factor_kind(const dotmi_handle *h);
+/* how many independent launch chains factorise this handle's subdomains: the subdomain groups of kind 1 (DOTMI_TILE_GROUPS: every
+ * group's levels on a stream of its own, one fork in front, one join behind); 1 for one chain and for kinds 2 and 3 */
+int32_t dotmi_factor_groups(const dotmi_handle *h);
 /* which form of the block solve this handle's factors are in: 0 = the explicit inverse X_s = chol(H_s)^-1 of every subdomain,
  * streamed in one pass (p_s = X_s^T X_s r_s); 1 = the two-level form (round 6; default where form 0 would stream 240 MB or more per application over all subdomains of the mesh,
  * DOTMI_TWO_LEVEL): the inverse factors of the dissection's leaves and of the separator complement, and between them the panels
