@@ -407,6 +407,7 @@ struct ScheduleRules {
     bool eagerMinRmulByUser = false;
     int tileFlow = -1;             // DOTMI_TILE_FLOW
     int groups = 1;                // subdomain groups of the level launches (tile_factor.hpp; the dataflow launch has one)
+    bool hfill = false;            // DOTMI_TILE_HFILL: H tiles built inside their first task from entry lists (build_tile_fill)
 };
 struct FactorSchedule {
     TileSchedule S;                    // with its per-group level ranges and clear tiles (S.groupLevel, S.clearStart)
@@ -414,6 +415,62 @@ struct FactorSchedule {
     bool flow = false;                 // the dataflow launch (tile_flow_kernel) instead of one launch per level
     std::vector<int> depPtr, depIdx;   // its dependencies
 };
+// The fill of the work buffer as per-tile entry lists (TileSchedule::fillPtr / fill, tile_factor.hpp): every stored scalar the dense
+// fill writes (fill_dst >= 0; source hval_idx(fill_src, rc)) and every 1.0 of the identity padding (pad_dst; source -1) goes to the
+// list of the clear tile that holds its address -- through the row blocks' main table and, in the two-level form, the second one --
+// and every task planned with init == 2 receives its tile's range.  Inside a list the entries ascend by source, so neighbouring
+// lanes gather neighbouring scalars of Hval.  Returns the error text, empty when every address has found its tile.
+inline std::string build_tile_fill(TileSchedule &S, const double *W2, const FillLists &fill, const RowTileArrays &rt,
+                                   const RowTileArrays &rtM)
+{
+    struct Blk {
+        long long off;
+        int ld, c0;
+    };
+    std::vector<Blk> blks;
+    for (const RowTileArrays *A : {&rt, &rtM})
+        for (size_t k = 0; k < A->off.size(); ++k)
+            if (A->off[k] >= 0 && A->ld[k] > 0) blks.push_back({A->off[k], A->ld[k], A->c0[k]});
+    std::sort(blks.begin(), blks.end(), [](const Blk &a, const Blk &b) { return a.off < b.off; });
+    std::unordered_map<long long, int> tileAt;   // offset of a clear tile's origin in the work buffer -> its index
+    tileAt.reserve(S.clearTiles.size() * 2);
+    for (size_t k = 0; k < S.clearTiles.size(); ++k) tileAt[S.clearTiles[k] - W2] = (int)k;
+    std::vector<std::vector<TileFillEntry>> lists(S.clearTiles.size());
+    auto put = [&](long long d, long long src) -> bool {
+        auto it = std::upper_bound(blks.begin(), blks.end(), d, [](long long v, const Blk &b) { return v < b.off; });
+        if (it == blks.begin()) return false;
+        const Blk &B = *(it - 1);
+        const long long local = d - B.off;
+        if (local >= 64ll * B.ld) return false;
+        const int j = (int)(local / B.ld), col = (int)(local % B.ld) + B.c0, i = col / TILE, k = col % TILE;
+        auto at = tileAt.find(B.off + (long long)TILE * i - B.c0);
+        if (at == tileAt.end() || S.clearLd[at->second] != B.ld || src >= (1ll << 31)) return false;
+        lists[at->second].push_back(TileFillEntry{(int)src, (unsigned short)(k * TILE_LDS_LD + j), 0});
+        return true;
+    };
+    for (size_t e = 0; e < fill.fill_dst.size(); ++e)
+        if (fill.fill_dst[e] >= 0 && !put(fill.fill_dst[e], (long long)hval_idx(fill.fill_src[e / 9], (int)(e % 9))))
+            return "tile fill: a scalar of H has no tile of the work buffer";
+    for (long long d : fill.pad_dst)
+        if (!put(d, -1)) return "tile fill: a padding scalar has no tile of the work buffer";
+    S.fillPtr.assign(1, 0);
+    S.fill.clear();
+    for (auto &l : lists) {
+        std::stable_sort(l.begin(), l.end(), [](const TileFillEntry &a, const TileFillEntry &b) { return a.src < b.src; });
+        S.fill.insert(S.fill.end(), l.begin(), l.end());
+        if (S.fill.size() >= (size_t)1 << 31) return "tile fill: more than 2^31 entries";
+        S.fillPtr.push_back((int)S.fill.size());
+    }
+    for (TileTask &t : S.tasks) {
+        if (t.init != 2) continue;
+        auto at = tileAt.find(t.c - W2);
+        if (at == tileAt.end()) return "tile fill: a task starts from a tile without an entry list";
+        t.fillFirst = S.fillPtr[at->second];
+        t.fillCount = S.fillPtr[at->second + 1] - t.fillFirst;
+    }
+    return std::string();
+}
+
 // rt / rtM: row_tile_arrays of the storage's two tables; W, W2: the device addresses of the factor and the work buffer, which the
 // tasks carry
 inline void plan_factor_schedule(int nParts, int nmax, const std::vector<int> &dofmap, const std::vector<int4> &fillBlk,
@@ -459,7 +516,7 @@ inline void plan_factor_schedule(int nParts, int nmax, const std::vector<int> &d
             plan_subdomain_tiles(ls, nt, W, &rt.off[at], &rt.ld[at], &rt.c0[at], live[ls], pat[ls], W2, sn, subs[ls].tasks,
                                  subs[ls].clearTiles, subs[ls].clearLd, S.flops, S.qTiles, eagerMin, eagerChunk, 0, true, eagerMinRmul,
                                  leafTile ? &rtM.off[at] : nullptr, leafTile ? &rtM.ld[at] : nullptr,
-                                 leafTile ? &rtM.c0[at] : nullptr, leafTile);
+                                 leafTile ? &rtM.c0[at] : nullptr, leafTile, R.hfill);
             nTasks += subs[ls].tasks.size();
             for (auto &t : subs[ls].tasks) maxLevel = std::max(maxLevel, t.level);
         }

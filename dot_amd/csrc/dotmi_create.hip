@@ -541,6 +541,15 @@ static int upload_factor_schedule(dotmi_handle *h, const FactorSchedule &FS)
     if (int rc = upload(h, &h->tclear, S.clearTiles)) return rc;
     if (int rc = upload(h, &h->tclearLd, S.clearLd)) return rc;
     h->nTclear = (int)S.clearTiles.size();
+    h->tileHfill = !S.fillPtr.empty();
+    if (h->tileHfill) {
+        std::vector<TileFillEntry> fl = S.fill;
+        if (fl.empty()) fl.push_back(TileFillEntry{-1, 0, 0});
+        if (int rc = upload(h, &h->tfill, fl)) return rc;
+        if (h->tune.fuseLog)
+            fprintf(stderr, "dotmi: tile fill: %zu entries in %zu tiles (%.1f MB of lists)\n", S.fill.size(), S.clearTiles.size(),
+                    8e-6 * S.fill.size());
+    }
     h->tlevelStart = S.levelStart;
     h->tlevelDiag = S.levelDiag;
     h->tgroupLevel = S.groupLevel;
@@ -701,8 +710,12 @@ int build_device_mesh(dotmi_handle *h)
         FactorSchedule FS;
         plan_factor_schedule(P.nParts, P.nmax, rows.dofmap, fill.fillBlk, rt, rtM, L.twoLevel ? F.leafTile.data() : nullptr, P.W, h->W2,
                              ScheduleRules{tune.tileEagerMin, tune.tileEagerMinRmul, tune.tileEagerMinRmulByUser, tune.tileFlow,
-                                           choose_tile_groups(tune, P.nParts)},
+                                           choose_tile_groups(tune, P.nParts), tune.tileHfill != 0},
                              FS);
+        if (tune.tileHfill) {
+            h->err = build_tile_fill(FS.S, h->W2, fill, rt, rtM);
+            if (!h->err.empty()) return DOTMI_E_INVALID;
+        }
         if (int rc = upload_factor_schedule(h, FS)) return rc;
     }
     if (int rc = dalloc(h, &P.ppart, (size_t)P.nParts * P.nbmax * P.nmax)) return rc;
@@ -1018,6 +1031,139 @@ int dotmi_plan_grouped_tile_schedule(int32_t n_blocks, int32_t nt, const uint8_t
     std::copy(perm.begin(), perm.end(), fill_perm);
     std::copy(start.begin(), start.end(), fill_start);
     return G;
+}
+
+// host-only: what the two entries below return of a schedule planned with hfill and its entry lists (build_tile_fill).
+//   counts[8] = {tasks, clear tiles, entries, fill blocks, padding scalars, groups, doubles of one buffer, 0}
+//   tasks: 10 int64 each, in the order of the task array {group, level inside the group (from 1), block, offset of the c tile and
+//          of the tile written (each in its own buffer: the work buffer, or the factor buffer for the inversion's tiles and the tile
+//          a diagonal task writes), init, post, first entry, entries, form};
+//   clear: 5 int64 per clear tile {group, offset in the work buffer, leading dimension, first entry, entries};
+//   entry_pos / entry_src: per entry its place in the 64 x 65 LDS tile and its scalar of Hval (-1: the padding's 1.0).
+static void export_tile_fill(const TileSchedule &S, const double *W, const double *W2, int64_t *tasks, int64_t *clear,
+                             int32_t *entry_pos, int32_t *entry_src)
+{
+    const int G = (int)S.groupLevel.size() - 1;
+    for (int g = 0; g < G; ++g) {
+        for (int l = S.groupLevel[g]; l < S.groupLevel[g + 1]; ++l)
+            for (int k = S.levelStart[l]; k < S.levelStart[l + 1]; ++k) {
+                const TileTask &t = S.tasks[k];
+                const bool inv = t.form == TF_INV;   // (its tiles lie in the factor buffer, like the tile a diagonal task writes)
+                const int64_t row[10] = {g, l - S.groupLevel[g] + 1, t.sub, t.c - (inv ? W : W2),
+                                         t.o - (inv || t.post == TP_DIAG ? W : W2), t.init, t.post, t.fillFirst, t.fillCount, t.form};
+                std::copy(row, row + 10, tasks + 10 * (size_t)k);
+            }
+        for (int k = S.clearStart[g]; k < S.clearStart[g + 1]; ++k) {
+            const int64_t row[5] = {g, S.clearTiles[k] - W2, S.clearLd[k], S.fillPtr[k], S.fillPtr[k + 1] - S.fillPtr[k]};
+            std::copy(row, row + 5, clear + 5 * (size_t)k);
+        }
+    }
+    for (size_t e = 0; e < S.fill.size(); ++e) {
+        entry_pos[e] = S.fill[e].pos;
+        entry_src[e] = S.fill[e].src;
+    }
+}
+
+// host-only: the H tiles' entry lists (DOTMI_TILE_HFILL; build_tile_fill, block_plan.hpp) for n_blocks blocks of nt x nt tiles in the
+// layout of dotmi_plan_grouped_tile_schedule, from the CALLER's fill lists: fill_dst[9 n_fill] (offsets in the work buffer, -1: not
+// stored), fill_src[n_fill] (blocks of Hval), pad_dst[n_pad].  tasks == NULL: counts only.  Returns the groups used or an error
+// (DOTMI_E_INVALID also when an address lies in no H-pattern tile).  tests/test_tile_fill.py
+int dotmi_plan_tile_fill(int32_t n_blocks, int32_t nt, const uint8_t *live, const uint8_t *pattern, int32_t eager_min,
+                         int32_t eager_chunk, int32_t groups, int64_t n_fill, const int64_t *fill_dst, const int32_t *fill_src,
+                         int64_t n_pad, const int64_t *pad_dst, int64_t *counts, int64_t *tasks, int64_t *clear, int32_t *entry_pos,
+                         int32_t *entry_src)
+{
+    if (n_blocks < 1 || nt < 1 || !live || !pattern || !counts || n_fill < 0 || n_pad < 0 || (n_fill > 0 && (!fill_dst || !fill_src)) ||
+        (n_pad > 0 && !pad_dst))
+        return DOTMI_E_INVALID;
+    RowTileArrays rt, rtM;
+    long long tot = 0;
+    for (int j = 0; j < nt; ++j) tot += 64ll * 64 * (j + 1);
+    for (int b = 0; b < n_blocks; ++b) {
+        long long at = b * tot;
+        for (int j = 0; j < nt; ++j) {
+            rt.off.push_back(at);
+            rt.ld.push_back(64 * (j + 1));
+            rt.c0.push_back(0);
+            at += 64ll * 64 * (j + 1);
+        }
+    }
+    double *const W = reinterpret_cast<double *>(1ull << 40);   // never dereferenced: only offsets leave this function
+    double *const W2 = W + (long long)n_blocks * tot;
+    std::vector<SubdomainTiles> subs(n_blocks);
+    TileSchedule S;
+    size_t sn = 0;
+    for (int b = 0; b < n_blocks; ++b) {
+        std::vector<uint8_t> lv(live + (size_t)b * nt, live + (size_t)(b + 1) * nt);
+        std::vector<uint8_t> pat(pattern + (size_t)b * nt * nt, pattern + (size_t)(b + 1) * nt * nt);
+        plan_subdomain_tiles(b, nt, W, &rt.off[(size_t)b * nt], &rt.ld[(size_t)b * nt], &rt.c0[(size_t)b * nt], lv, pat, W2, sn,
+                             subs[b].tasks, subs[b].clearTiles, subs[b].clearLd, S.flops, S.qTiles, std::max(1, eager_min),
+                             std::max(1, eager_chunk), 0, true, -1, nullptr, nullptr, nullptr, nullptr, true);
+    }
+    finish_grouped_schedule(subs, groups, S);
+    FillLists fill;
+    fill.fill_dst.assign(fill_dst, fill_dst + 9 * n_fill);
+    fill.fill_src.assign(fill_src, fill_src + n_fill);
+    fill.pad_dst.assign(pad_dst, pad_dst + n_pad);
+    for (long long d : fill.fill_dst)
+        if (d >= (long long)n_blocks * tot) return DOTMI_E_INVALID;
+    for (long long d : fill.pad_dst)
+        if (d < 0 || d >= (long long)n_blocks * tot) return DOTMI_E_INVALID;
+    if (!build_tile_fill(S, W2, fill, rt, rtM).empty()) return DOTMI_E_INVALID;
+    const int G = (int)S.groupLevel.size() - 1;
+    const int64_t c[8] = {(int64_t)S.tasks.size(), (int64_t)S.clearTiles.size(), (int64_t)S.fill.size(), n_fill, n_pad, G,
+                          (int64_t)n_blocks * tot, 0};
+    std::copy(c, c + 8, counts);
+    if (!tasks) return G;
+    if (!clear || !entry_pos || !entry_src) return DOTMI_E_INVALID;
+    export_tile_fill(S, W, W2, tasks, clear, entry_pos, entry_src);
+    return G;
+}
+
+// host-only: the same for ALL parts of the caller's mesh, through the stages dotmi_create runs (block_plan.hpp: layout -- two_level:
+// the leaves-first form with its second row-block table --, rows, storage, fill lists, level schedule with `groups` chains, entry
+// lists); additionally returns the fill lists the entry lists were derived from: fill_dst[9 * counts[3]], fill_src[counts[3]],
+// pad_dst[counts[4]].  tasks == NULL: counts only.
+int dotmi_plan_tile_fill_mesh(int32_t nV, int32_t nT, const int32_t *T, const double *Xrest, const int32_t *epart, int32_t nParts,
+                              int32_t groups, int32_t two_level, int64_t *counts, int64_t *tasks, int64_t *clear, int32_t *entry_pos,
+                              int32_t *entry_src, int64_t *fill_dst, int32_t *fill_src, int64_t *pad_dst)
+{
+    if (nV < 1 || nT < 1 || !T || !Xrest || !epart || nParts < 1 || !counts || !mesh_is_valid(nV, nT, T, epart, nParts))
+        return DOTMI_E_INVALID;
+    const MeshGraph G = mesh_graph(nV, nT, T, Xrest);
+    const std::vector<std::vector<int>> sets = part_vertex_sets(nT, T, epart, nParts);
+    LayoutRules LR;
+    LR.twoLevel = two_level ? 1 : 0;
+    BlockLayout L;
+    choose_block_layout(G, sets, 0, nParts, LR, L);
+    RowPlacement rows;
+    place_rows(L, sets, 0, nParts, rows);
+    FactorStorage F;
+    plan_factor_storage(L, rows.dofmap, nParts, F);
+    const RowTileArrays rt = row_tile_arrays(F.rtab), rtM = row_tile_arrays(F.rtabM);
+    FillLists fill;
+    build_fill_lists(G, sets, 0, nParts, rows, L.nmax, F, fill);
+    double *const W = reinterpret_cast<double *>(1ull << 40);   // never dereferenced
+    double *const W2 = W + (long long)F.wTotal;
+    FactorSchedule FS;
+    ScheduleRules SR;
+    SR.tileFlow = 0;
+    SR.groups = groups;
+    SR.hfill = true;
+    plan_factor_schedule(nParts, L.nmax, rows.dofmap, fill.fillBlk, rt, rtM, L.twoLevel ? F.leafTile.data() : nullptr, W, W2, SR, FS);
+    if (!build_tile_fill(FS.S, W2, fill, rt, rtM).empty()) return DOTMI_E_INVALID;
+    const TileSchedule &S = FS.S;
+    const int Gn = (int)S.groupLevel.size() - 1;
+    const int64_t c[8] = {(int64_t)S.tasks.size(), (int64_t)S.clearTiles.size(), (int64_t)S.fill.size(), (int64_t)fill.fill_src.size(),
+                          (int64_t)fill.pad_dst.size(), Gn, (int64_t)F.wTotal, L.twoLevel ? 1 : 0};
+    std::copy(c, c + 8, counts);
+    if (!tasks) return Gn;
+    if (!clear || !entry_pos || !entry_src || !fill_dst || !fill_src || !pad_dst) return DOTMI_E_INVALID;
+    export_tile_fill(S, W, W2, tasks, clear, entry_pos, entry_src);
+    std::copy(fill.fill_dst.begin(), fill.fill_dst.end(), fill_dst);
+    std::copy(fill.fill_src.begin(), fill.fill_src.end(), fill_src);
+    std::copy(fill.pad_dst.begin(), fill.pad_dst.end(), pad_dst);
+    return Gn;
 }
 
 // host-only: the dependencies the dataflow kernel (tile_flow_kernel) waits on, for the task list dotmi_plan_tile_schedule

@@ -87,6 +87,9 @@ struct Tuning {
                               //                      (-1: the latter above 64 subdomains, where the factorisation is throughput-bound)
     int tileGroups = -1;      // DOTMI_TILE_GROUPS    the level launches of the factorisation as G independent chains of subdomain groups,
                               //                      each on a stream of its own (0 / 1: one chain; at most 4; -1: two -- choose_tile_groups)
+    int tileHfill = 1;        // DOTMI_TILE_HFILL     1 (default): the first task of an H tile builds it in LDS from the tile's entry list --
+                              //                      the refresh neither clears nor fills the work buffer; 0: clear_tiles + dense_fill
+                              //                      into the work buffer, which the first task reads back (until round 7)
     int tileEagerMin = 0;     // DOTMI_TILE_EAGER_MIN early products a critical-path tile task may keep
     int fastDiag = 1;         // DOTMI_FAST_DIAG      1 / 0: the diagonal tile tasks' 16 x 16 bottom steps on 4 x 4 blocks every lane factors for
                               //                      itself (12.0 us per 64 x 64 step) / one row per lane with v_readlane operands (15.3 us)
@@ -139,6 +142,7 @@ struct Tuning {
         t.patchElems = std::max(0, geti("DOTMI_PATCH_ELEMS", 0));
         t.tileSplit = geti("DOTMI_TILE_SPLIT", -1);
         t.tileGroups = geti("DOTMI_TILE_GROUPS", -1);
+        t.tileHfill = geti("DOTMI_TILE_HFILL", 1) != 0;
         t.tileEagerMin = std::max(0, geti("DOTMI_TILE_EAGER_MIN", 0));
         t.tileFlow = geti("DOTMI_TILE_FLOW", -1);
         t.fastDiag = geti("DOTMI_FAST_DIAG", 1);
@@ -209,12 +213,14 @@ struct dotmi_handle {
     TileProd *tprods = nullptr;
     double **tclear = nullptr;
     int *tclearLd = nullptr;
+    TileFillEntry *tfill = nullptr;   // DOTMI_TILE_HFILL: the H tiles' entry lists (TileSchedule::fill); the tasks carry their ranges
+    bool tileHfill = false;           // the work buffer never holds H: no clear, no fill in front of the factorisation
     std::vector<long long> rtOff;   // host copy of the RowTile table (dotmi_part_matrix)
     std::vector<int> rtLd, rtC0;
     std::vector<long long> rtOffM;  // two-level form: the separators' row blocks' second range (their sub-tree's leaf columns)
     std::vector<int> rtLdM, rtC0M;
     size_t wTotal = 0;
-    double *W2 = nullptr;             // tile factorisation: the work buffer (H, then R), laid out like P.W (which holds Q only)
+    double *W2 = nullptr;             // tile factorisation: the work buffer (R; with tileHfill off H before it), laid out like P.W (which holds Q only)
     int nTclear = 0;
     std::vector<int> tlevelStart, tlevelDiag;
     // subdomain groups (tile_factor.hpp): group g runs the levels [tgroupLevel[g], tgroupLevel[g + 1]) of the two tables above --

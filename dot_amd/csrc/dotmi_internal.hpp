@@ -504,11 +504,15 @@ void launch_assemble(const DevMesh &M, const double *He, double *Hval, hipStream
 void launch_dense_fill(const DevParts &P, const double *Hval, hipStream_t st);
 // one level of the tile schedule (tile_factor.hpp): one workgroup per task
 // fastDiag: the diagonal tasks' 16 x 16 bottom steps in the per-lane 8 x 8 form (k_tilefactor.hip, block_chol_inv<N, FAST>; 512 threads)
-void launch_tile_level(const TileTask *tasks, int ntasks, const TileProd *prods, int *info, hipStream_t st, bool fastDiag = true);
+// fill / Hval: the H tiles' entry lists and the values they index (tasks with init == 2; none without the lists)
+void launch_tile_level(const TileTask *tasks, int ntasks, const TileProd *prods, int *info, hipStream_t st, bool fastDiag = true,
+                       const TileFillEntry *fill = nullptr, const double *Hval = nullptr);
 // the non-diagonal tasks of a level on half tiles, four workgroups per CU (tile_gemm_kernel)
-void launch_tile_gemm(const TileTask *tasks, int ntasks, const TileProd *prods, hipStream_t st);
+void launch_tile_gemm(const TileTask *tasks, int ntasks, const TileProd *prods, hipStream_t st, const TileFillEntry *fill = nullptr,
+                      const double *Hval = nullptr);
 void launch_tile_flow(const TileTask *tasks, int ntasks, const TileProd *prods, const int *depPtr, const int *depIdx, int *done,
-                      int *next, int epoch, int *info, int nwg, hipStream_t st, double waitMs, bool fastDiag = true);
+                      int *next, int epoch, int *info, int nwg, hipStream_t st, double waitMs, bool fastDiag = true,
+                      const TileFillEntry *fill = nullptr, const double *Hval = nullptr);
 void launch_clear_tiles(double *const *tiles, const int *lds_, int ntiles, hipStream_t st);
 // k_pd.hip (LBFGS-PD): L on the device, its fill into the work buffer, z = L^-1 q per coordinate
 void launch_pd_assemble(const DevMesh &M, const DevPD &D, double dtSq, hipStream_t st);

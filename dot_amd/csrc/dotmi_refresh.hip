@@ -9,7 +9,7 @@ int issue_factor(dotmi_handle *h)
 {
     if (h->tileFlow) {
         launch_tile_flow(h->ttasks, h->nTtasks, h->tprods, h->tdepPtr, h->tdepIdx, h->tdone, h->tnext, ++h->tileEpoch, h->info_dev,
-                         h->tileFlowWg, h->st, (double)h->tune.tileFlowWaitMs, h->fastDiag);
+                         h->tileFlowWg, h->st, (double)h->tune.tileFlowWaitMs, h->fastDiag, h->tfill, h->Hval);
         h->flopCount = h->tileFlops;
         return 0;
     }
@@ -27,7 +27,7 @@ int issue_factor(dotmi_handle *h)
                 if (l >= h->tgroupLevel[g + 1]) continue;
                 more = 1;
                 launch_tile_level(h->ttasks + h->tlevelStart[l], h->tlevelStart[l + 1] - h->tlevelStart[l], h->tprods, h->info_dev,
-                                  g == 0 ? h->st : h->stGroup[g - 1], h->fastDiag);
+                                  g == 0 ? h->st : h->stGroup[g - 1], h->fastDiag, h->tfill, h->Hval);
             }
         }
         for (size_t g = 1; g < G; ++g) {
@@ -39,7 +39,7 @@ int issue_factor(dotmi_handle *h)
         for (size_t l = 0; l + 1 < h->tlevelStart.size(); ++l) {
             const int n = h->tlevelStart[l + 1] - h->tlevelStart[l];
             if (!h->tileSplit) {
-                launch_tile_level(h->ttasks + h->tlevelStart[l], n, h->tprods, h->info_dev, h->st, h->fastDiag);
+                launch_tile_level(h->ttasks + h->tlevelStart[l], n, h->tprods, h->info_dev, h->st, h->fastDiag, h->tfill, h->Hval);
                 continue;
             }
             // the level's diagonal-block tasks (77 KB of LDS, ~20 us each) on the side stream, its product / row / inverse
@@ -49,14 +49,14 @@ int issue_factor(dotmi_handle *h)
             if (nd > 0 && ng > 0) {
                 HIPCHECK(h, hipEventRecord(h->tFork[l], h->st));
                 HIPCHECK(h, hipStreamWaitEvent(h->stDiag, h->tFork[l], 0));
-                launch_tile_level(t0, nd, h->tprods, h->info_dev, h->stDiag, h->fastDiag);
-                launch_tile_gemm(t0 + nd, ng, h->tprods, h->st);
+                launch_tile_level(t0, nd, h->tprods, h->info_dev, h->stDiag, h->fastDiag, h->tfill, h->Hval);
+                launch_tile_gemm(t0 + nd, ng, h->tprods, h->st, h->tfill, h->Hval);
                 HIPCHECK(h, hipEventRecord(h->tJoin[l], h->stDiag));
                 HIPCHECK(h, hipStreamWaitEvent(h->st, h->tJoin[l], 0));
             } else if (nd > 0) {
-                launch_tile_level(t0, nd, h->tprods, h->info_dev, h->st, h->fastDiag);
+                launch_tile_level(t0, nd, h->tprods, h->info_dev, h->st, h->fastDiag, h->tfill, h->Hval);
             } else {
-                launch_tile_gemm(t0, ng, h->tprods, h->st);
+                launch_tile_gemm(t0, ng, h->tprods, h->st, h->tfill, h->Hval);
             }
         }
     }
@@ -118,16 +118,18 @@ int refactor_issue(dotmi_handle *h, const double *x)
     // the separator panels; the (A,C) blocks and the cleared mirror panels stay zero for the handle's life
     // tile factorisation: H goes into the WORK buffer (tile_factor.hpp); the factor buffer W was zeroed once and only ever
     // receives tiles of Q
+    // DOTMI_TILE_HFILL (round 8): H goes nowhere -- the first task of every H tile builds it in LDS from the tile's entry list and
+    // Hval, so there is neither a clear nor a fill; the work buffer only ever holds R (and the eager partial sums on their way to it)
     DevParts Pf = h->P;
     if (h->tileMode) Pf.W = h->W2;
     if (h->wDirty) {
-        launch_clear_tiles(h->tclear, h->tclearLd, h->nTclear, h->st);
+        if (!h->tileHfill) launch_clear_tiles(h->tclear, h->tclearLd, h->nTclear, h->st);
     } else if (h->P.nParts > 0) {
         HIPCHECK(h, hipMemsetAsync(h->P.W, 0, h->wTotal * sizeof(double), h->st));
         if (h->tileMode) HIPCHECK(h, hipMemsetAsync(h->W2, 0, h->wTotal * sizeof(double), h->st));
         h->wDirty = true;
     }
-    launch_dense_fill(Pf, h->Hval, h->st);
+    if (!h->tileHfill) launch_dense_fill(Pf, h->Hval, h->st);
     HIPCHECK(h, hipEventRecord(h->ev1, h->st));
     if (h->P.nParts > 0) {
         HIPCHECK(h, hipMemsetAsync(h->info_dev, 0, sizeof(int) * h->P.nParts, h->st));

@@ -388,9 +388,48 @@ extern "C" int dotmi_debug_diag_prof(long long *out, int n)
 #else
 #define DPROF(k) do { } while (0)
 #endif
+// An H tile built in LDS from its entry list (TileFillEntry, tile_factor.hpp; t.init == 2): L (64 x 65 doubles, the layout
+// tile_to_lds fills) = zero, then L[pos] = Hval[src], or 1.0 for the identity padding (src < 0) -- what a cleared and filled tile
+// of the work buffer held, without the tile's round trip through memory.  Four entries per thread are in flight at a time
+// (list -> Hval is a dependent round trip): tile_fill_request asks for the first four -- behind the task's first operand
+// loads, so the two overlap -- and tile_fill_build scatters them and walks on through the longer lists.  Ends behind a barrier.
+constexpr int FILL_UNROLL = 4;
+struct TileFillReq {
+    TileFillEntry e[FILL_UNROLL];
+};
+template <int THREADS>
+__device__ __forceinline__ TileFillReq tile_fill_request(const TileFillEntry *__restrict__ fl, int first, int count, int tid)
+{
+    TileFillReq r;
+#pragma unroll
+    for (int u = 0; u < FILL_UNROLL; ++u) {
+        const int k = tid + THREADS * u;
+        r.e[u] = k < count ? fl[first + k] : TileFillEntry{-1, 0, 0};
+    }
+    return r;
+}
+template <int THREADS>
+__device__ __forceinline__ void tile_fill_build(TileFillReq r, const TileFillEntry *__restrict__ fl, int first, int count,
+                                                const double *__restrict__ Hval, double *__restrict__ L, int tid)
+{
+    for (int k = tid; k < CHOL_NB * (CHOL_NB + 1); k += THREADS) L[k] = 0.0;
+    __syncthreads();
+    for (int base = 0; base < count; base += THREADS * FILL_UNROLL) {
+        if (base > 0) r = tile_fill_request<THREADS>(fl, first + base, count - base, tid);
+        double v[FILL_UNROLL];
+#pragma unroll
+        for (int u = 0; u < FILL_UNROLL; ++u) v[u] = r.e[u].src < 0 ? 1.0 : Hval[r.e[u].src];
+#pragma unroll
+        for (int u = 0; u < FILL_UNROLL; ++u)
+            if (base + tid + THREADS * u < count) L[r.e[u].pos] = v[u];
+    }
+    __syncthreads();
+}
+
 // one tile task on the workgroup's LDS tiles (the body of both the level kernel and the dataflow kernel below)
 template <int THREADS, bool COH = false, bool FAST = false>
 __device__ __forceinline__ void tile_task_body(const TileTask &t, const TileProd *__restrict__ prods, int *__restrict__ info,
+                                               const TileFillEntry *__restrict__ fl, const double *__restrict__ Hval,
                                                double (*La)[CHOL_NB + 1], double (*Lb)[CHOL_NB + 1], double (*T32)[33],
                                                double (*T16)[17])
 {
@@ -421,8 +460,13 @@ __device__ __forceinline__ void tile_task_body(const TileTask &t, const TileProd
         rbk = TL(t.q, t.ldq, tid);
     }
     if (t.init) {
-        tile_to_lds<THREADS>(TL(t.c, t.ldc, tid), La, tid);
-        __syncthreads();
+        if (t.init == 2) {   // the tile of H from its entry list: nothing of it is in the work buffer
+            tile_fill_build<THREADS>(tile_fill_request<THREADS>(fl, t.fillFirst, t.fillCount, tid), fl, t.fillFirst, t.fillCount, Hval,
+                                     &La[0][0], tid);
+        } else {
+            tile_to_lds<THREADS>(TL(t.c, t.ldc, tid), La, tid);
+            __syncthreads();
+        }
 #pragma unroll
         for (int q = 0; q < NT; ++q)
 #pragma unroll
@@ -528,12 +572,13 @@ __device__ __forceinline__ void tile_task_body(const TileTask &t, const TileProd
 
 template <int THREADS, bool FAST = false>
 __global__ __launch_bounds__(THREADS, 2) void tile_task_kernel(const TileTask *__restrict__ tasks,
-                                                               const TileProd *__restrict__ prods, int *__restrict__ info)
+                                                               const TileProd *__restrict__ prods, int *__restrict__ info,
+                                                               const TileFillEntry *__restrict__ fl, const double *__restrict__ Hval)
 {
     constexpr int NB = CHOL_NB, LD = NB + 1;
     __shared__ double La[NB][LD], Lb[NB][LD], T32[32][33], T16[16][17];
     const TileTask t = tasks[blockIdx.x];
-    tile_task_body<THREADS, false, FAST>(t, prods, info, La, Lb, T32, T16);
+    tile_task_body<THREADS, false, FAST>(t, prods, info, fl, Hval, La, Lb, T32, T16);
 }
 
 // Dataflow form of the same factorisation (DOTMI_TILE_FLOW): ONE launch of persistent workgroups that
@@ -556,7 +601,8 @@ __global__ __launch_bounds__(THREADS, 2) void tile_flow_kernel(const TileTask *_
                                                                const TileProd *__restrict__ prods, int ntasks,
                                                                const int *__restrict__ depPtr, const int *__restrict__ depIdx,
                                                                int *__restrict__ done, int *__restrict__ next, int epoch,
-                                                               long long waitTicks, int *__restrict__ info)
+                                                               long long waitTicks, int *__restrict__ info,
+                                                               const TileFillEntry *__restrict__ fl, const double *__restrict__ Hval)
 {
     // the 256-thread form (256 VGPRs + 84 bytes of scratch) gave a wrong factor on horse7K -- the same non-SPD pivot in every
     // run -- and was not pursued: it cannot be instantiated
@@ -593,7 +639,7 @@ __global__ __launch_bounds__(THREADS, 2) void tile_flow_kernel(const TileTask *_
             if (tid == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         }
         __syncthreads();
-        tile_task_body<THREADS, true, FAST>(t, prods, info, La, Lb, T32, T16);   // (result tile stored write-through)
+        tile_task_body<THREADS, true, FAST>(t, prods, info, fl, Hval, La, Lb, T32, T16);   // (result tile stored write-through)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every storing wave: its part of the result tile has left
         __syncthreads();
         if (tid == 0) {
@@ -611,7 +657,8 @@ __global__ __launch_bounds__(THREADS, 2) void tile_flow_kernel(const TileTask *_
 //   TF_FACT  acc -= sum_k A(k, i) B(k, j):  K = the tiles' rows;  TF_INV  acc += sum_k A(i, k) B(k, j):  K = A's columns.
 // In both cases the A half is stored K-major, La[k][i], so one inner loop serves both.
 __global__ __launch_bounds__(256, 4) void tile_gemm_kernel(const TileTask *__restrict__ tasks,
-                                                           const TileProd *__restrict__ prods)
+                                                           const TileProd *__restrict__ prods,
+                                                           const TileFillEntry *__restrict__ fl, const double *__restrict__ Hval)
 {
     constexpr int KH = 32, LD = CHOL_NB + 1;
     __shared__ double Ls[2 * KH * LD];                     // La | Lb, or one whole 64 x 65 tile (4160 doubles either way)
@@ -678,7 +725,10 @@ __global__ __launch_bounds__(256, 4) void tile_gemm_kernel(const TileTask *__res
     if (nsteps > 0) fetch(0);
     else if (t.post == TP_ROW) load_rows(t.q, t.ldq, 0, ra);
     else if (t.post == TP_RMUL) load_rows(t.q, t.ldq, 0, rbk);
-    if (t.init) {
+    if (t.init == 2) {
+        // the tile of H from its entry list (tile_fill_build), in the same LDS layout as the c tile below
+        tile_fill_build<256>(tile_fill_request<256>(fl, t.fillFirst, t.fillCount, tid), fl, t.fillFirst, t.fillCount, Hval, Ls, tid);
+    } else if (t.init) {
         // the c tile through LDS into the accumulator layout (element (i, j) of acc[q][r]: i = rb + lk + 4 r, j = 16 q + lr)
         double2 c[8];
 #pragma unroll
@@ -693,6 +743,8 @@ __global__ __launch_bounds__(256, 4) void tile_gemm_kernel(const TileTask *__res
             Lf[r + 1][j] = c[u].y;
         }
         __syncthreads();
+    }
+    if (t.init) {
 #pragma unroll
         for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -767,28 +819,31 @@ __global__ __launch_bounds__(256, 4) void tile_gemm_kernel(const TileTask *__res
     }
 }
 
-void launch_tile_level(const TileTask *tasks, int ntasks, const TileProd *prods, int *info, hipStream_t st, bool fastDiag)
+void launch_tile_level(const TileTask *tasks, int ntasks, const TileProd *prods, int *info, hipStream_t st, bool fastDiag,
+                       const TileFillEntry *fill, const double *Hval)
 {
     if (ntasks <= 0) return;
-    if (fastDiag) hipLaunchKernelGGL((tile_task_kernel<512, true>), dim3(ntasks), dim3(512), 0, st, tasks, prods, info);
-    else hipLaunchKernelGGL((tile_task_kernel<512, false>), dim3(ntasks), dim3(512), 0, st, tasks, prods, info);
+    if (fastDiag) hipLaunchKernelGGL((tile_task_kernel<512, true>), dim3(ntasks), dim3(512), 0, st, tasks, prods, info, fill, Hval);
+    else hipLaunchKernelGGL((tile_task_kernel<512, false>), dim3(ntasks), dim3(512), 0, st, tasks, prods, info, fill, Hval);
 }
 void launch_tile_flow(const TileTask *tasks, int ntasks, const TileProd *prods, const int *depPtr, const int *depIdx, int *done,
-                      int *next, int epoch, int *info, int nwg, hipStream_t st, double waitMs, bool fastDiag)
+                      int *next, int epoch, int *info, int nwg, hipStream_t st, double waitMs, bool fastDiag, const TileFillEntry *fill,
+                      const double *Hval)
 {
     if (ntasks <= 0) return;
     const int grid = std::min(ntasks, nwg);
     const long long waitTicks = (long long)(waitMs * 1e5);
     if (fastDiag)
         hipLaunchKernelGGL((tile_flow_kernel<512, true>), dim3(grid), dim3(512), 0, st, tasks, prods, ntasks, depPtr, depIdx, done,
-                           next, epoch, waitTicks, info);
+                           next, epoch, waitTicks, info, fill, Hval);
     else
         hipLaunchKernelGGL((tile_flow_kernel<512, false>), dim3(grid), dim3(512), 0, st, tasks, prods, ntasks, depPtr, depIdx, done,
-                           next, epoch, waitTicks, info);
+                           next, epoch, waitTicks, info, fill, Hval);
 }
-void launch_tile_gemm(const TileTask *tasks, int ntasks, const TileProd *prods, hipStream_t st)
+void launch_tile_gemm(const TileTask *tasks, int ntasks, const TileProd *prods, hipStream_t st, const TileFillEntry *fill,
+                      const double *Hval)
 {
-    if (ntasks > 0) hipLaunchKernelGGL(tile_gemm_kernel, dim3(ntasks), dim3(256), 0, st, tasks, prods);
+    if (ntasks > 0) hipLaunchKernelGGL(tile_gemm_kernel, dim3(ntasks), dim3(256), 0, st, tasks, prods, fill, Hval);
 }
 
 // zero a list of 64 x 64 tiles (the tiles a factorisation leaves non-zero, before the refill)

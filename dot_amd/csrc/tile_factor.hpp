@@ -8,7 +8,8 @@
 //   DIAG(j)    G = H_jj - sum_m R_mj^T R_mj ;  Q_jj = chol(G)^-1
 //   ROW(k,j)   G = H_kj - sum_m R_mk^T R_mj ;  R_kj = Q_kk^T G                       (k < j)
 //   INV(i,j)   Q_ij = -(sum_{i <= m < j} Q_im R_mj) Q_jj                              (i < j)
-// Round 5: TWO buffers of the same compact layout.  H is filled into the WORK buffer, whose tiles R overwrites in place; the
+// Round 5: TWO buffers of the same compact layout.  H is filled into the WORK buffer, whose tiles R overwrites in place (round 8:
+// H is filled nowhere -- the first task of an H tile builds it in LDS from the tile's entry list, TileFillEntry below); the
 // tiles of Q go to the FACTOR buffer the back-solve streams and are never anything else.  Until round 4 Q overwrote R in
 // one buffer: the sum T_ij of INV went to a scratch tile and a task of its own (QFIN) multiplied it with -Q_jj once every
 // reader of R_ij had finished -- a third of all tasks, a fifth of the tile traffic (scratch written and read back) and two
@@ -36,7 +37,7 @@ namespace dotmi {
 
 constexpr int TILE = 64;
 
-// a task:  acc = (init ? tile c : 0);  acc (-)+= products;  post
+// a task:  acc = (init == 1 ? tile c : init == 2 ? the tile's entries of H : 0);  acc (-)+= products;  post
 enum TileForm { TF_FACT = 0 /* acc -= A^T B */, TF_INV = 1 /* acc += A B */ };
 enum TilePost {
     TP_STORE = 0,   // c = acc                       (eager partial update of an H tile / of a scratch T tile)
@@ -51,16 +52,27 @@ struct TileProd {
     int lda, ldb;    // their leading dimensions (a tile's rows live in one row block of the factor storage; scratch: 64)
 };
 struct TileTask {
-    int form, init, post, nprod;   // TileForm, read c first?, TilePost, number of products
+    int form, init, post, nprod;   // TileForm, start from (0: zero, 1: the c tile, 2: the tile's fill entries), TilePost, number of products
     int first, sub;                // products [first, first + nprod) of the level-ordered product array; owned subdomain
     int ldc, ldq;                  // leading dimensions of the c tile and of the q tile
-    int pivotBase, pad;            // TP_DIAG: scalar offset of the tile's first row (for the non-SPD report)
+    int pivotBase, fillFirst;      // TP_DIAG: scalar offset of the tile's first row (for the non-SPD report);  init == 2: the tile's
+                                   // entries are [fillFirst, fillFirst + fillCount) of the fill entry array (TileSchedule::fill)
     double *c;                     // the tile read (init)
     double *q;                     // TP_ROW: tile of Q_kk;  TP_RMUL: tile of Q_jj
     double *o;                     // the tile written (== c except for TP_DIAG: reads the work buffer's H_jj, writes the factor buffer's Q_jj)
     TileProd p0;                   // copy of the first product: its tiles are requested straight from the descriptor, one
                                    // dependent round trip earlier than through the product array
+    int fillCount, pad;
 };
+// Round 8: H reaches the factorisation through per-tile entry lists instead of a cleared and filled work buffer.  One entry = one
+// scalar of an H-pattern tile: where it goes in the 64 x 65 LDS tile of the task kernels (element (row k, column j) of the
+// column-major global tile -> k * 65 + j, the index tile_to_lds gives it) and where it comes from (the scalar's index in Hval,
+// hval_idx; -1: the 1.0 of the identity padding).  The FIRST task of the tile (init == 2) builds the tile in LDS from its list.
+struct alignas(8) TileFillEntry {
+    int src;
+    unsigned short pos, pad;
+};
+constexpr int TILE_LDS_LD = TILE + 1;
 
 struct TileSchedule {
     std::vector<TileTask> tasks;      // level after level
@@ -75,6 +87,10 @@ struct TileSchedule {
     std::vector<int> groupOf;         // owned subdomain -> group
     std::vector<int> groupLevel;      // the levels of group g are entries [groupLevel[g], groupLevel[g + 1]) of levelStart / levelDiag
     std::vector<int> clearStart;      // its clear tiles are [clearStart[g], clearStart[g + 1])
+    // build_tile_fill (block_plan.hpp): the entries of clear tile k are fill[fillPtr[k] .. fillPtr[k + 1]) -- in group order like the
+    // clear tiles; empty unless the tasks were planned with hfill
+    std::vector<int> fillPtr;
+    std::vector<TileFillEntry> fill;
     size_t scratchTiles = 0;          // 64 x 64 scratch tiles needed (none since round 5)
     double flops = 0;                 // FP64 flop of one factorisation as executed
     long long liveTiles = 0, qTiles = 0;
@@ -98,8 +114,10 @@ inline void plan_subdomain_tiles(int sub, int nt, double *W, const long long *rt
                                  std::vector<double *> &clearTiles, std::vector<int> &clearLd, double &flops, long long &qTiles,
                                  int eagerMin = 2, int eagerChunk = 1, int eagerMinDiag = 0, bool balance = true,
                                  int eagerMinRmul = -1, const long long *rtOffM = nullptr, const int *rtLdM = nullptr,
-                                 const int *rtC0M = nullptr, const uint8_t *leafTile = nullptr)
+                                 const int *rtC0M = nullptr, const uint8_t *leafTile = nullptr, bool hfill = false)
 {
+    // hfill: the first task of an H-pattern tile builds the tile from its entry list (init == 2, build_tile_fill sets the range)
+    // instead of reading what a clear and a fill pass left in the work buffer (init == 1)
     // Two-level form (leafTile != nullptr; leaves-first layout, nd_layout.hpp): tile rows of the LEAVES against the separator
     // complement.  A separator's row block j stores its separator columns in the main table (rtC0[j] = the first separator column
     // of its sub-tree) and the leaf columns of its sub-tree in a second one (rtOffM / rtLdM / rtC0M).  The factorisation proper is
@@ -185,23 +203,23 @@ inline void plan_subdomain_tiles(int sub, int nt, double *W, const long long *rt
         // DIAG(j), where the launch lasts ~26 us anyway, and leaves the multiplication with -Q_jj for the level after it)
         const int keep = post == TP_DIAG ? eagerMinDiag : (post == TP_RMUL && eagerMinRmul >= 0) ? eagerMinRmul : EAGER_MIN;
         if (nEarly <= (size_t)keep && !(post == TP_RMUL && eagerMinRmul == 0 && nEarly > 0)) nEarly = 0;
-        bool have = initFromC;
+        int init = initFromC ? (hfill ? 2 : 1) : 0;   // of the tile's next task: only the first one starts from H
         size_t k0 = 0;
         while (k0 < nEarly) {
             size_t k1 = (post == TP_RMUL && eagerMinRmul == 0 && nEarly <= (size_t)EAGER_MIN) ? nEarly : std::min(nEarly, k0 + CHUNK);
             while (k1 < nEarly && pa[k1].avail == pa[k1 - 1].avail) ++k1;
             TileTaskL E;
-            E.t = TileTask{form, have ? 1 : 0, TP_STORE, 0, 0, sub, ldc, 0, 0, 0, c, nullptr, c};
+            E.t = TileTask{form, init, TP_STORE, 0, 0, sub, ldc, 0, 0, 0, c, nullptr, c};
             for (size_t k = k0; k < k1; ++k) E.prods.push_back(pa[k].p);
             E.level = pa[k1 - 1].avail + 1;
             E.row = row;
             flops += 2.0 * TILE * TILE * TILE * E.prods.size();
             out.push_back(std::move(E));
-            have = true;
+            init = 1;
             k0 = k1;
         }
         TileTaskL F;
-        F.t = TileTask{form, have ? 1 : 0, post, 0, 0, sub, ldc, ldq, pivotBase, 0, c, q, dst};
+        F.t = TileTask{form, init, post, 0, 0, sub, ldc, ldq, pivotBase, 0, c, q, dst};
         for (size_t k = nEarly; k < pa.size(); ++k) F.prods.push_back(pa[k].p);
         F.level = lf;
         F.row = row;

@@ -308,6 +308,23 @@ int dotmi_plan_grouped_tile_schedule(int32_t n_blocks, int32_t nt, const uint8_t
                                      int32_t eager_chunk, int32_t groups, int64_t *tasks, int64_t *n_tasks, int32_t *group_of,
                                      int32_t *group_level, int64_t *clear, int64_t *n_clear, int32_t n_fill, const int32_t *fill_sub,
                                      int32_t *fill_perm, int32_t *fill_start);
+/* (host only, round 8) the H tiles' entry lists (DOTMI_TILE_HFILL): with them the first task of an H tile (init = 2) builds the tile
+ * in LDS and the refresh neither clears nor fills the work buffer.  For n_blocks blocks in the layout of
+ * dotmi_plan_grouped_tile_schedule and the caller's fill lists (fill_dst[9 n_fill]: offsets in the work buffer or -1,
+ * fill_src[n_fill]: blocks of Hval, pad_dst[n_pad]: the identity padding).  counts[8] = {tasks, clear tiles, entries, n_fill, n_pad,
+ * groups, doubles of one buffer, two-level}; tasks, 10 int64 each {group, level, block, offset of the c tile and of the tile written
+ * (each in its own buffer), init, post, first entry, entries, form}; clear, 5 int64 each {group, offset, leading dimension,
+ * first entry, entries}; entry_pos / entry_src per entry: k * 65 + j for element (row k, column j) of the column-major tile, and the
+ * scalar's index in Hval (-1: 1.0).  tasks == NULL: counts only.  Returns the groups used or an error.  tests/test_tile_fill.py */
+int dotmi_plan_tile_fill(int32_t n_blocks, int32_t nt, const uint8_t *live, const uint8_t *pattern, int32_t eager_min,
+                         int32_t eager_chunk, int32_t groups, int64_t n_fill, const int64_t *fill_dst, const int32_t *fill_src,
+                         int64_t n_pad, const int64_t *pad_dst, int64_t *counts, int64_t *tasks, int64_t *clear, int32_t *entry_pos,
+                         int32_t *entry_src);
+/* (host only) the same for all parts of a mesh through dotmi_create's own planning stages (two_level: the leaves-first form); also
+ * returns the fill lists the entry lists come from: fill_dst[9 counts[3]], fill_src[counts[3]], pad_dst[counts[4]] */
+int dotmi_plan_tile_fill_mesh(int32_t nV, int32_t nT, const int32_t *T, const double *Xrest, const int32_t *epart, int32_t nParts,
+                              int32_t groups, int32_t two_level, int64_t *counts, int64_t *tasks, int64_t *clear, int32_t *entry_pos,
+                              int32_t *entry_src, int64_t *fill_dst, int32_t *fill_src, int64_t *pad_dst);
 /* (host only) the job table of the back-solve launches dotmi_create builds for parts [p0, p1) of this mesh: how the rows of every
  * tree region are cut into tiles, which launch / kernel form takes them and which workgroup runs them (dot_amd/csrc/bs_tiles.hpp;
  * the reference has no counterpart: CHOLMODSolver::solve, CHOLMODSolver.cpp:149-163, walks CHOLMOD's supernodes).  tiles: up to cap
