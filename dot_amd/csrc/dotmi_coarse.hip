@@ -1,0 +1,267 @@
+// dotmi_coarse.hip -- the rigid-mode coarse space of Newton-PCG's preconditioner (dotmi_set_pcg_coarse; kernels k_coarse.hip, lists
+// coarse_plan.hpp).  One-level additive Schwarz carries information across one subdomain per CG iteration; the
+// additive coarse term  M = M_sym + Z A0^-1 Z^T,  A0 = Z^T H Z  with the subdomains' six rigid-body modes as Z's columns carries the
+// smooth part across all of them at once.  Off by default and then absent: no list, no buffer, no launch.  With the mode on, every
+// refresh of H (refactor_issue) marks A0 stale and the next solve rebuilds it from the handle's current iterate: centroids, the pairs'
+// 6 x 6 blocks, the dense fill, and X = chol(A0)^-1 by the tile kernels of the block solve on a schedule of their own for this one
+// dense block (as LBFGS-PD factors its Laplacian); the host reads back the pivot flag and nothing else.  A factorisation that meets a
+// non-positive pivot (rank-deficient Z) switches the term off until the next successful build -- the solves run on M_sym alone and
+// the handle is not poisoned.  The reference has no counterpart.
+#include "coarse_plan.hpp"
+#include "dotmi_handle.hpp"
+
+namespace dotmi {
+
+// lists, buffers and the tile schedule, at the first switch-on; kept
+static int coarse_setup(dotmi_handle *h)
+{
+    dotmi_handle::Coarse &K = h->coarse;
+    if (K.planned) return 0;
+    DevCoarse &D = K.D;
+    const int nP = h->nPartsAll, nV = h->nV;
+    std::vector<int> adj_ptr, adj_idx;
+    build_adjacency(nV, h->nT, h->T.data(), adj_ptr, adj_idx);
+    CoarsePlan P;
+    coarse_plan(nV, h->nT, h->T.data(), h->epart.data(), nP, adj_ptr, adj_idx, P);
+    for (int s = 0; s < nP; ++s)   // the plan's subdomains are the handle's (both from epart)
+        if (!std::equal(P.svIdx.begin() + P.svPtr[s], P.svIdx.begin() + P.svPtr[s + 1], h->partVerts[s].begin(), h->partVerts[s].end())) {
+            h->err = "dotmi_set_pcg_coarse: the coarse plan's subdomains differ from the handle's";
+            return DOTMI_E_INVALID;
+        }
+    D.nParts = nP;
+    D.nc = 6 * nP;
+    D.ncp = (D.nc + TILE - 1) / TILE * TILE;
+    D.nPairs = (int)P.pairS.size();
+    std::vector<int2> pair(D.nPairs);
+    K.pairAt.assign((size_t)nP * nP, -1);
+    for (int p = 0; p < D.nPairs; ++p) {
+        pair[p] = make_int2(P.pairS[p], P.pairT[p]);
+        K.pairAt[(size_t)P.pairS[p] * nP + P.pairT[p]] = p;
+    }
+    if (P.pairBlk.empty()) P.pairBlk.push_back(0);
+    if (int rc = upload(h, &D.vsPtr, P.vsPtr)) return rc;
+    if (int rc = upload(h, &D.vsIdx, P.vsIdx)) return rc;
+    if (int rc = upload(h, &D.svPtr, P.svPtr)) return rc;
+    if (int rc = upload(h, &D.svIdx, P.svIdx)) return rc;
+    if (int rc = upload(h, &D.pair, pair)) return rc;
+    if (int rc = upload(h, &D.pairPtr, P.pairPtr)) return rc;
+    if (int rc = upload(h, &D.pairBlk, P.pairBlk)) return rc;
+    if (int rc = upload(h, &D.pairAt, K.pairAt)) return rc;
+    if (int rc = dalloc(h, &D.live, (size_t)nP)) return rc;
+    if (int rc = dalloc(h, &D.wgt, (size_t)nV)) return rc;
+    if (int rc = dalloc(h, &D.xf, (size_t)h->n)) return rc;
+    if (int rc = dalloc(h, &D.cen, (size_t)3 * nP)) return rc;
+    if (int rc = dalloc(h, &D.pairA, (size_t)36 * D.nPairs)) return rc;
+    const size_t wn = (size_t)D.ncp * D.ncp;
+    if (int rc = dalloc(h, &D.W, wn)) return rc;
+    if (int rc = dalloc(h, &D.W2, wn)) return rc;
+    if (int rc = dalloc(h, &D.c, (size_t)D.ncp)) return rc;
+    if (int rc = dalloc(h, &D.y, (size_t)(D.ncp / TILE) * D.ncp)) return rc;
+    if (int rc = dalloc(h, &D.info, 1)) return rc;
+    HIPCHECK(h, hipMemset(D.W, 0, sizeof(double) * wn));   // (the factorisation writes the tiles of X and nothing else, ever)
+    HIPCHECK(h, hipMemset(D.c, 0, sizeof(double) * D.ncp));
+    HIPCHECK(h, hipMemset(D.y, 0, sizeof(double) * (size_t)(D.ncp / TILE) * D.ncp));
+    // the tile schedule of one dense block of nt x nt tiles in plain row-major storage: row block J at 64 J ncp, all columns
+    const int nt = D.ncp / TILE;
+    std::vector<long long> rtOff(nt);
+    std::vector<int> rtLd(nt, D.ncp), rtC0(nt, 0);
+    for (int J = 0; J < nt; ++J) rtOff[J] = (long long)J * TILE * D.ncp;
+    std::vector<uint8_t> live(nt, 1), pat((size_t)nt * nt, 0);
+    for (int I = 0; I < nt; ++I)
+        for (int J = I; J < nt; ++J) pat[(size_t)I * nt + J] = 1;
+    TileSchedule S;
+    {
+        std::vector<TileTaskL> all;
+        size_t sn = 0;
+        plan_subdomain_tiles(0, nt, D.W, rtOff.data(), rtLd.data(), rtC0.data(), live, pat, D.W2, sn, all, S.clearTiles, S.clearLd, S.flops,
+                             S.qTiles, 2, 2, 0, true, 1);
+        finish_tile_schedule(all, S);
+    }
+    if (int rc = upload(h, &K.tasks, S.tasks)) return rc;
+    if (S.prods.empty()) S.prods.push_back(TileProd{nullptr, nullptr, 0, 0});
+    if (int rc = upload(h, &K.prods, S.prods)) return rc;
+    K.levelStart = S.levelStart;
+    HIPCHECK(h, hipHostMalloc((void **)&K.h_info, sizeof(int)));
+    HIPCHECK(h, hipEventCreate(&K.ev0));
+    HIPCHECK(h, hipEventCreate(&K.ev1));
+    if (h->tune.fuseLog)
+        fprintf(stderr, "dotmi: PCG coarse space: %d subdomains, dimension %d (padded %d), %d coupled pairs with %d entries, %zu tile tasks "
+                "in %zu levels\n", nP, D.nc, D.ncp, D.nPairs, P.pairPtr.back(), S.tasks.size(), S.levelStart.size() - 1);
+    K.planned = true;
+    return 0;
+}
+
+int coarse_refresh(dotmi_handle *h)
+{
+    dotmi_handle::Coarse &K = h->coarse;
+    if (K.mode == 0 || !K.stale) return 0;
+    if (int rc = coarse_setup(h)) return rc;
+    DevCoarse &D = K.D;
+    // weights and dropped subdomains from the handle's current fixed set (dotmi_refix changes it)
+    K.wgt.resize(h->nV);
+    K.live.assign(D.nParts, 0);
+    for (int v = 0; v < h->nV; ++v) K.wgt[v] = h->fixed[v] ? 0.0 : 1.0 / (double)std::max(h->dup[v], 1);
+    K.dropped = 0;
+    for (int s = 0; s < D.nParts; ++s) {
+        int nfree = 0;
+        for (int v : h->partVerts[s]) nfree += h->fixed[v] ? 0 : 1;
+        K.live[s] = nfree >= 3;
+        K.dropped += nfree < 3;
+    }
+    HIPCHECK(h, hipMemcpyAsync(D.wgt, K.wgt.data(), sizeof(double) * h->nV, hipMemcpyHostToDevice, h->st));
+    HIPCHECK(h, hipMemcpyAsync(D.live, K.live.data(), sizeof(int) * D.nParts, hipMemcpyHostToDevice, h->st));
+    HIPCHECK(h, hipEventRecord(K.ev0, h->st));
+    HIPCHECK(h, hipMemcpyAsync(D.xf, h->x, sizeof(double) * h->n, hipMemcpyDeviceToDevice, h->st));   // frozen with this build
+    launch_coarse_centroid(D, h->st);
+    launch_coarse_assemble(D, h->M, h->Hval, h->st);
+    launch_coarse_fill(D, h->st);
+    HIPCHECK(h, hipMemsetAsync(D.info, 0, sizeof(int), h->st));
+    for (size_t l = 0; l + 1 < K.levelStart.size(); ++l)   // one launch per level of the block's own schedule
+        launch_tile_level(K.tasks + K.levelStart[l], K.levelStart[l + 1] - K.levelStart[l], K.prods, D.info, h->st, h->fastDiag);
+    HIPCHECK(h, hipEventRecord(K.ev1, h->st));
+    HIPCHECK(h, hipMemcpyAsync(K.h_info, D.info, sizeof(int), hipMemcpyDeviceToHost, h->st));
+    HIPCHECK(h, hipStreamSynchronize(h->st));
+    HIPCHECK(h, hipGetLastError());
+    float ms = 0.f;
+    hipEventElapsedTime(&ms, K.ev0, K.ev1);
+    K.lastBuildMs = ms;
+    K.stale = false;
+    K.builds++;
+    K.active = K.h_info[0] == 0;   // a non-positive pivot: Z is rank deficient -- the solves go on with M_sym alone
+    if (h->tune.fuseLog)
+        fprintf(stderr, "dotmi: PCG coarse build %lld: %.3f ms, %d dropped, %s\n", K.builds, K.lastBuildMs, K.dropped,
+                K.active ? "active" : "inactive (pivot)");
+    return 0;
+}
+
+void coarse_restrict_solve(dotmi_handle *h, const double *r)
+{
+    launch_coarse_restrict(h->coarse.D, r, h->st);
+    launch_coarse_solve(h->coarse.D, h->st);
+}
+
+void coarse_prolong(dotmi_handle *h, double *zsum) { launch_coarse_prolong(h->coarse.D, h->nV, h->pcg.isd, zsum, h->st); }
+
+}  // namespace dotmi
+
+extern "C" {
+
+int dotmi_set_pcg_coarse(dotmi_handle *h, int32_t mode)
+{
+    if (!h) return DOTMI_E_INVALID;
+    const char *why = pcg_refusal(h);
+    if (!why && !h->vpart.empty()) why = "the subdomains of this handle are vertex sets (vpart), the coarse plan works on an element partition";
+    if (why) {
+        h->err = std::string("dotmi_set_pcg_coarse: ") + why;
+        return DOTMI_E_INVALID;
+    }
+    if (mode != 0 && mode != 1) {
+        h->err = "dotmi_set_pcg_coarse: mode must be 0 (off) or 1 (rigid modes)";
+        return DOTMI_E_INVALID;
+    }
+    if (mode == 1 && h->nPartsAll > COARSE_MAX_PARTS) {
+        h->err = "dotmi_set_pcg_coarse: at most " + std::to_string(COARSE_MAX_PARTS) + " subdomains (the coarse matrix is applied through a dense "
+                 "inverse factor); this handle has " + std::to_string(h->nPartsAll);
+        return DOTMI_E_INVALID;
+    }
+    if (mode == 1 && h->coarse.mode == 0) h->coarse.stale = true;   // (whatever happened to H while the mode was off)
+    h->coarse.mode = mode;
+    return 0;
+}
+
+int dotmi_pcg_coarse_info(const dotmi_handle *h, int32_t *dim, int32_t *dropped_subdomains, int32_t *active, int64_t *builds)
+{
+    if (!h) return DOTMI_E_INVALID;
+    const dotmi_handle::Coarse &K = h->coarse;
+    if (dim) *dim = K.mode ? 6 * h->nPartsAll : 0;
+    if (dropped_subdomains) *dropped_subdomains = K.dropped;
+    if (active) *active = K.mode != 0 && K.active;
+    if (builds) *builds = K.builds;
+    return 0;
+}
+
+int dotmi_pcg_coarse_matrix(dotmi_handle *h, int32_t cap, double *A0)
+{
+    if (!h) return DOTMI_E_INVALID;
+    dotmi_handle::Coarse &K = h->coarse;
+    if (K.builds == 0) {
+        h->err = "dotmi_pcg_coarse_matrix: no coarse matrix has been assembled on this handle";
+        return DOTMI_E_INVALID;
+    }
+    const int nc = K.D.nc;
+    if (!A0) return nc;
+    if ((long long)cap < (long long)nc * nc) {
+        h->err = "dotmi_pcg_coarse_matrix: room for " + std::to_string((long long)nc * nc) + " doubles is needed";
+        return DOTMI_E_INVALID;
+    }
+    HIPCHECK(h, hipSetDevice(h->device));
+    std::vector<double> pairA((size_t)36 * K.D.nPairs);
+    HIPCHECK(h, hipMemcpyAsync(pairA.data(), K.D.pairA, sizeof(double) * pairA.size(), hipMemcpyDeviceToHost, h->st));
+    HIPCHECK(h, hipStreamSynchronize(h->st));
+    coarse_dense_host(nc, K.D.nParts, K.pairAt.data(), K.live.data(), pairA.data(), A0);
+    return nc;
+}
+
+int dotmi_pcg_apply_precond(dotmi_handle *h, const double *r, double *w)
+{
+    if (!h) return DOTMI_E_INVALID;
+    if (!r || !w) {
+        h->err = "dotmi_pcg_apply_precond: r and w must be given";
+        return DOTMI_E_INVALID;
+    }
+    if (const char *why = pcg_refusal(h)) {
+        h->err = std::string("dotmi_pcg_apply_precond: ") + why;
+        return DOTMI_E_INVALID;
+    }
+    HIPCHECK(h, hipSetDevice(h->device));
+    if (int rc = enter_with_factors(h)) return rc;
+    if (int rc = coarse_refresh(h)) return rc;
+    const bool coarse = h->coarse.mode != 0 && h->coarse.active;
+    LbfgsArgs L0;
+    memset(&L0, 0, sizeof(L0));
+    HIPCHECK(h, hipMemcpyAsync(h->tmpn, r, sizeof(double) * h->n, hipMemcpyHostToDevice, h->st));
+    launch_coarse_scale(h->n, h->tmpn, h->pcg.isd, h->q, h->st);          // q = r (.) isd
+    const Bracket br = backsolve_bracket(h);
+    if (coarse) coarse_restrict_solve(h, h->tmpn);
+    launch_gemv(h->P, h->q, h->st, nullptr, br.ev0, br.ev1);
+    launch_merge(h->M, h->P, L0, h->z, h->partC, 0, h->st);               // zsum = S q
+    if (coarse) coarse_prolong(h, h->z);
+    launch_coarse_scale(h->n, h->z, h->pcg.isd, h->tmpn, h->st);          // w = zsum (.) isd, as pcg_spmv_kernel forms it
+    HIPCHECK(h, hipMemcpyAsync(w, h->tmpn, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->st));
+    HIPCHECK(h, hipStreamSynchronize(h->st));
+    HIPCHECK(h, hipGetLastError());
+    return 0;
+}
+
+// host-only: the lists of the coarse assembly and of the per-iteration kernels.  sizes[3] = {pairs, entries, (vertex, subdomain)
+// incidences} always; the arrays (any may be NULL) as in coarse_plan.hpp
+int dotmi_plan_coarse(int32_t nV, int32_t nT, const int32_t *T, const int32_t *epart, int32_t nParts, int32_t *sizes, int32_t *pairS,
+                      int32_t *pairT, int32_t *pairPtr, int32_t *pairBlk, int32_t *vsPtr, int32_t *vsIdx, int32_t *svPtr, int32_t *svIdx)
+{
+    if (nV < 1 || nT < 1 || !T || !epart || !sizes || nParts < 1 || nParts > COARSE_MAX_PARTS) return DOTMI_E_INVALID;
+    for (int e = 0; e < 4 * nT; ++e)
+        if (T[e] < 0 || T[e] >= nV) return DOTMI_E_INVALID;
+    for (int e = 0; e < nT; ++e)
+        if (epart[e] < 0 || epart[e] >= nParts) return DOTMI_E_INVALID;
+    std::vector<int> adj_ptr, adj_idx;
+    build_adjacency(nV, nT, T, adj_ptr, adj_idx);
+    CoarsePlan P;
+    coarse_plan(nV, nT, T, epart, nParts, adj_ptr, adj_idx, P);
+    sizes[0] = (int32_t)P.pairS.size();
+    sizes[1] = (int32_t)P.pairBlk.size();
+    sizes[2] = (int32_t)P.vsIdx.size();
+    auto out = [](int32_t *dst, const std::vector<int> &src) {
+        if (dst) std::copy(src.begin(), src.end(), dst);
+    };
+    out(pairS, P.pairS);
+    out(pairT, P.pairT);
+    out(pairPtr, P.pairPtr);
+    out(pairBlk, P.pairBlk);
+    out(vsPtr, P.vsPtr);
+    out(vsIdx, P.vsIdx);
+    out(svPtr, P.svPtr);
+    out(svIdx, P.svIdx);
+    return 0;
+}
+
+}  // extern "C"

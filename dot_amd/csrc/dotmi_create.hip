@@ -1391,6 +1391,9 @@ void dotmi_destroy(dotmi_handle *h)
     if (h->h_alpha) hipHostFree(h->h_alpha);
     if (h->h_ctl) hipHostFree(h->h_ctl);
     if (h->h_pcg) hipHostFree(h->h_pcg);
+    if (h->coarse.h_info) hipHostFree(h->coarse.h_info);
+    if (h->coarse.ev0) hipEventDestroy(h->coarse.ev0);
+    if (h->coarse.ev1) hipEventDestroy(h->coarse.ev1);
     if (h->dposPinned) hipHostFree(h->dposPinned);
     if (h->evDir) hipEventDestroy(h->evDir);
     if (h->h_info) hipHostFree(h->h_info);

@@ -7,6 +7,7 @@
 //   dotmi_reconfig.hip    tolerance, time step and materials changed on a live handle (dotmi_set_rel_tol / _time_step / _lame)
 //   dotmi_pd.hip / dotmi_ic.hip   the preconditioners of LBFGS-PD (scalar Laplacian) and LBFGS-HI (block incomplete Cholesky of H)
 //   dotmi_pcg.hip         Newton-PCG: conjugate gradients on the global H with the block solve (dotmi_solve_hessian, DOTMI_FLAG_NEWTON_PCG)
+//   dotmi_coarse.hip      the rigid-mode coarse space of that PCG's preconditioner (dotmi_set_pcg_coarse; lists: coarse_plan.hpp)
 //   dotmi_api.hip         the remaining ABI entry points (state, kernel-level calls, probes, measurement)
 //
 // Control flow mirrors (paths relative to /root/reference/src)
@@ -341,6 +342,25 @@ struct dotmi_handle {
     long long pcgSolves = 0, pcgItersTotal = 0;   // dotmi_pcg_info
     int pcgLastIters = 0;
     double pcgLastRes = 0.0;
+    // dotmi_set_pcg_coarse: the rigid-mode coarse term of the PCG's preconditioner (dotmi_coarse.hip).  Nothing of it exists until the
+    // mode is switched on; every refresh of H marks the coarse matrix stale and the next solve with the mode on rebuilds it
+    struct Coarse {
+        int mode = 0;                 // 0 off, 1 rigid modes
+        bool planned = false;         // lists, buffers and the tile schedule exist
+        bool stale = true;            // H has been refreshed since the last build
+        bool active = false;          // the last build's factorisation succeeded: the solves add the coarse term
+        int dropped = 0;              // subdomains with fewer than 3 free vertices at the last build
+        long long builds = 0;
+        double lastBuildMs = 0.0;
+        DevCoarse D;
+        TileTask *tasks = nullptr;    // a tile schedule of its own for the one dense block (tile_factor.hpp)
+        TileProd *prods = nullptr;
+        std::vector<int> levelStart;
+        std::vector<int> pairAt, live;   // host copies (dotmi_pcg_coarse_matrix)
+        std::vector<double> wgt;
+        int *h_info = nullptr;        // pinned: the pivot flag, all a refresh reads back
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    } coarse;
     bool devLoop = false;
     DevLoop *ctl = nullptr, *h_ctl = nullptr;  // device / pinned staging
     int *h_flags = nullptr;                    // pinned: {status, slots done}, written by the controller
@@ -453,6 +473,11 @@ int ic_apply(dotmi_handle *h, const double *q, double *z, const LbfgsArgs &L);
 // dotmi_pcg.hip (Newton-PCG)
 int pcg_build_scaling(dotmi_handle *h);
 int pcg_solve(dotmi_handle *h, const double *b, double rel_tol, int max_iter, int check_every, int *iters, double *rel_res);
+const char *pcg_refusal(const dotmi_handle *h);   // why this handle has no global solve (nullptr: it has)
+// dotmi_coarse.hip (the coarse term of the PCG's preconditioner)
+int coarse_refresh(dotmi_handle *h);              // mode on and stale: rebuild A0 and its inverse factor from the current H and x
+void coarse_restrict_solve(dotmi_handle *h, const double *r);   // c = Z^T r, y = A0^-1 c
+void coarse_prolong(dotmi_handle *h, double *zsum);             // zsum += (Z y) / isd
 // dotmi_collectives.hip
 int allreduce_sum(dotmi_handle *h, double *dev, size_t n);
 int adopt_rank0(dotmi_handle *h, double *vals, int n);

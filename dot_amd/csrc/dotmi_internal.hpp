@@ -567,4 +567,33 @@ void launch_pcg_init(const DevPcg &C, int n, const double *b, double *u, double 
 void launch_pcg_spmv(const DevMesh &M, const DevPcg &C, const double *Hval, const double *zsum, int it, hipStream_t st);
 void launch_pcg_update(const DevPcg &C, int n, double *u, double *q, int it, double rel_tol, hipStream_t st);
 
+// ---- the rigid-mode coarse space of Newton-PCG's preconditioner (dotmi_set_pcg_coarse; dotmi_coarse.hip / k_coarse.hip; lists:
+// coarse_plan.hpp): M = M_sym + Z A0^-1 Z^T, A0 = Z^T H Z, six columns of Z per subdomain -------------------------------------------
+constexpr int COARSE_MAX_PARTS = 256;   // A0^-1 is kept as a dense inverse factor: nc = 6 nParts <= 1536 (a storage choice)
+struct DevCoarse {
+    int nParts = 0, nc = 0, ncp = 0, nPairs = 0;   // subdomains; 6 nParts; nc padded to a multiple of 64; coupled pairs (s <= t)
+    int *vsPtr = nullptr, *vsIdx = nullptr;        // per vertex: its subdomains, ascending
+    int *svPtr = nullptr, *svIdx = nullptr;        // per subdomain: its vertices, ascending
+    int2 *pair = nullptr;                          // (s, t) of every pair
+    int *pairPtr = nullptr, *pairBlk = nullptr;    // per pair: the H blocks of its sum, ascending
+    int *pairAt = nullptr;                         // nParts x nParts: the pair of (s, t), s <= t, or -1
+    int *live = nullptr;                           // per subdomain: 0 = dropped (fewer than 3 free vertices): zero columns, identity block
+    double *wgt = nullptr;                         // nV: 1 / dup on free vertices, 0 on fixed ones
+    double *xf = nullptr, *cen = nullptr;          // the positions (3 nV) and centroids (3 nParts) frozen with the last build
+    double *pairA = nullptr;                       // 36 per pair: A0_st, row-major
+    double *W = nullptr, *W2 = nullptr;            // ncp x ncp, row-major: X = chol(A0)^-1 (lower triangular) / the work buffer (A0, then R)
+    double *c = nullptr, *y = nullptr;             // the running application: Z^T r (ncp) and A0^-1 Z^T r as the parts of the ncp / 64 row
+                                                   // blocks of X ((ncp / 64) x ncp; the prolongation adds them)
+    int *info = nullptr;                           // the factorisation's pivot report
+};
+void launch_coarse_centroid(const DevCoarse &C, hipStream_t st);
+void launch_coarse_assemble(const DevCoarse &C, const DevMesh &M, const double *Hval, hipStream_t st);
+void launch_coarse_fill(const DevCoarse &C, hipStream_t st);
+void launch_coarse_restrict(const DevCoarse &C, const double *r, hipStream_t st);                       // c = Z^T r
+void launch_coarse_solve(const DevCoarse &C, hipStream_t st);                                           // y = X^T (X c)
+void launch_coarse_prolong(const DevCoarse &C, int nV, const double *isd, double *zsum, hipStream_t st);   // zsum += (Z y) / isd
+void launch_coarse_scale(int n, const double *a, const double *isd, double *out, hipStream_t st);       // out = a (.) isd per vertex
+// host: the dense nc x nc matrix from the pairs' blocks, entry by entry as the fill kernel writes it
+void coarse_dense_host(int nc, int nParts, const int *pairAt, const int *live, const double *pairA, double *A0);
+
 }  // namespace dotmi

@@ -46,6 +46,8 @@ static int pcg_alloc(dotmi_handle *h)
 int pcg_solve(dotmi_handle *h, const double *b, double rel_tol, int max_iter, int check_every, int *iters, double *rel_res)
 {
     if (int rc = pcg_alloc(h)) return rc;
+    if (int rc = coarse_refresh(h)) return rc;   // (dotmi_set_pcg_coarse; nothing unless the mode is on and H has been refreshed)
+    const bool coarse = h->coarse.mode != 0 && h->coarse.active;
     const DevPcg &C = h->pcg;
     const int n = h->n;
     LbfgsArgs L0;
@@ -58,8 +60,10 @@ int pcg_solve(dotmi_handle *h, const double *b, double rel_tol, int max_iter, in
         for (int j = 0; j < nb; ++j) {
             ++k;
             const Bracket br = backsolve_bracket(h);
+            if (coarse) coarse_restrict_solve(h, C.r);                          // y = A0^-1 Z^T r (needs nothing of the block solve)
             launch_gemv(h->P, h->q, h->st, nullptr, br.ev0, br.ev1);           // the block solves of q = r (.) isd
             launch_merge(h->M, h->P, L0, h->z, h->partC, 0, h->st);             // zsum = S q: no division, no dots
+            if (coarse) coarse_prolong(h, h->z);                                // zsum += (Z y) / isd: w = M_sym r + Z y
             launch_pcg_spmv(h->M, C, h->Hval, h->z, k, h->st);
             launch_pcg_update(C, n, h->p, h->q, k, rel_tol, h->st);
         }
@@ -90,6 +94,16 @@ int pcg_solve(dotmi_handle *h, const double *b, double rel_tol, int max_iter, in
     return state == PCG_CONVERGED ? 0 : 2;
 }
 
+const char *pcg_refusal(const dotmi_handle *h)
+{
+    return h->pd      ? "an LBFGS-PD handle has no Hessian block solve"
+           : h->hi    ? "an LBFGS-HI handle has no Hessian block solve"
+           : h->dist  ? "single-rank handles only (the subdomains of this one are sharded)"
+           : h->shardHess ? "the rows of the global Hessian are sharded over the ranks on this handle"
+           : h->gsdd  ? "a GSDD handle solves one subdomain at a time"
+                      : nullptr;
+}
+
 static bool pcg_settings_ok(double rel_tol, int max_iter) { return std::isfinite(rel_tol) && rel_tol > 0.0 && max_iter >= 1; }
 
 }  // namespace dotmi
@@ -107,13 +121,7 @@ int dotmi_solve_hessian(dotmi_handle *h, const double *b, double *u, double rel_
         h->err = "dotmi_solve_hessian: rel_tol must be finite and positive, max_iter at least 1";
         return DOTMI_E_INVALID;
     }
-    const char *why = h->pd      ? "an LBFGS-PD handle has no Hessian block solve"
-                      : h->hi    ? "an LBFGS-HI handle has no Hessian block solve"
-                      : h->dist  ? "single-rank handles only (the subdomains of this one are sharded)"
-                      : h->shardHess ? "the rows of the global Hessian are sharded over the ranks on this handle"
-                      : h->gsdd  ? "a GSDD handle solves one subdomain at a time"
-                                 : nullptr;
-    if (why) {
+    if (const char *why = pcg_refusal(h)) {
         h->err = std::string("dotmi_solve_hessian: ") + why;
         return DOTMI_E_INVALID;
     }

@@ -101,6 +101,7 @@ int run_factor(dotmi_handle *h)
 
 int refactor_issue(dotmi_handle *h, const double *x)
 {
+    h->coarse.stale = true;   // (dotmi_set_pcg_coarse: the next solve with the mode on rebuilds A0 = Z^T H Z)
     HIPCHECK(h, hipEventRecord(h->ev0, h->st));
     if (h->shardHess) {
         launch_elem_hessians(h->M, h->mat, h->dtSq, x, h->He, h->st, h->hessElems, h->nHessElems);

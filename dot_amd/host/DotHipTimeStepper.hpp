@@ -59,6 +59,8 @@ struct Options {  // the Config fields the DOT stepper reads (src/Config.hpp)
     bool newtonPCG = false;
     double pcgRelTol = 1e-3;
     int pcgMaxIter = 500, pcgCheckEvery = 8;
+    // the rigid-mode coarse term of those solves' preconditioner (dotmi_set_pcg_coarse): off by default
+    bool pcgCoarse = false;
 };
 
 class DotHipTimeStepper {
@@ -131,6 +133,14 @@ public:
             throw std::runtime_error(std::string("dotmi_create: ") + dotmi_last_error(nullptr) + " (" +
                                      std::to_string(rc) + ")");
         if (opt_.newtonPCG) check(dotmi_set_pcg(h_, opt_.pcgRelTol, opt_.pcgMaxIter, opt_.pcgCheckEvery), "set_pcg");
+        if (opt_.pcgCoarse) check(dotmi_set_pcg_coarse(h_, 1), "set_pcg_coarse");
+    }
+    // the coarse term of the PCG's preconditioner on a built stepper: 0 off, 1 rigid modes (dotmi_set_pcg_coarse)
+    void setPCGCoarse(int mode)
+    {
+        require_built("setPCGCoarse");
+        check(dotmi_set_pcg_coarse(h_, mode), "set_pcg_coarse");
+        opt_.pcgCoarse = mode != 0;
     }
 
     // 0 stepped, 1 all frames done, 2 stepped but iteration cap / line-search failure (Optimizer.cpp:327-368)

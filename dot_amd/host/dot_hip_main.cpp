@@ -15,7 +15,7 @@
 //
 // usage: dot_hip 100 <script.txt> [--mesh-root DIR] [--parts N] [--energy FCR|SNH] [--epart raw.i32]
 //                [--frames K] [--out DIR] [--device D] [--no-files] [--dump-scene K] [--dump-config] [--dump-formats DIR]
-//                [--echo-config FILE] [--fast] [--newton-pcg N]
+//                [--echo-config FILE] [--fast] [--newton-pcg N [--pcg-coarse]]
 //        dot_hip --write-info FILE nV nT steps iters t0..t21
 #include <algorithm>
 #include <chrono>
@@ -48,7 +48,7 @@ int main(int argc, char **argv)
     }
     if (argc < 3) {
         std::fprintf(stderr, "usage: %s 100 <script.txt> [--mesh-root DIR] [--parts N] [--energy FCR|SNH] "
-                             "[--epart raw.i32] [--frames K] [--out DIR] [--device D] [--no-files] [--dump-scene K] [--dump-config] [--dump-formats DIR] [--fast] [--newton-pcg N]\n", argv[0]);
+                             "[--epart raw.i32] [--frames K] [--out DIR] [--device D] [--no-files] [--dump-scene K] [--dump-config] [--dump-formats DIR] [--fast] [--newton-pcg N [--pcg-coarse]]\n", argv[0]);
         return 2;
     }
     if (std::string(argv[1]) != "100") {
@@ -58,7 +58,7 @@ int main(int argc, char **argv)
     const std::string scriptPath = argv[2];
     std::string meshRoot = ".", outDir, epartFile, energyOverride;
     int partsOverride = -1, frames = -1, device = 0, dumpScene = -1, newtonPcgParts = 0;
-    bool files = true, dumpConfig = false, fast = false;
+    bool files = true, dumpConfig = false, fast = false, pcgCoarse = false;
     std::string dumpFormats, echoConfig;
     for (int i = 3; i < argc; ++i) {
         const std::string a = argv[i];
@@ -79,6 +79,8 @@ int main(int argc, char **argv)
         // `timeStepper Newton` scripts: the mesh in N subdomains of the built-in partitioner under DOTMI_FLAG_NEWTON_PCG (H p = -g by
         // conjugate gradients on the subdomain factors) instead of one subdomain under DOTMI_FLAG_NEWTON; the output files are Newton's
         else if (a == "--newton-pcg") newtonPcgParts = std::stoi(next());
+        // ... with the rigid-mode coarse term in the solves' preconditioner (dotmi_set_pcg_coarse; at most 256 subdomains)
+        else if (a == "--pcg-coarse") pcgCoarse = true;
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     try {
@@ -117,6 +119,7 @@ int main(int argc, char **argv)
         if (newtonPcgParts != 0 && (cfg.timeStepper != "Newton" || newtonPcgParts < 1))
             throw std::runtime_error("--newton-pcg <N> takes N >= 1 and a script with `timeStepper Newton`");
         const bool newtonPcg = newtonPcgParts > 0;
+        if (pcgCoarse && !newtonPcg) throw std::runtime_error("--pcg-coarse belongs to --newton-pcg <N>");
         const bool newton = cfg.timeStepper == "Newton" && !newtonPcg;   // projected Newton: one subdomain, DOTMI_FLAG_NEWTON
         const bool lbfgsH = cfg.timeStepper == "LBFGSH" || newton;
         // `timeStepper LBFGS` (LBFGSTimeStepper with D0T_PD): LBFGS-PD on the whole mesh -- no partition, and none of the partition
@@ -209,6 +212,7 @@ int main(int argc, char **argv)
         if (newton) opt.flags |= DOTMI_FLAG_NEWTON;
         if (newtonPcg) {
             opt.newtonPCG = true;
+            opt.pcgCoarse = pcgCoarse;
             opt.alphaMin = 1.0;
         }
         opt.lbfgsPD = lbfgsPD;
@@ -295,6 +299,15 @@ int main(int argc, char **argv)
                 if (rc == 2) std::fprintf(fLog, "!!! maxIter reached for timeStep%d\n", n);
             }
             std::printf("FRAME %d ms %.3f iters %d halvings %d E %.17g status %d\n", n, st.ms_total, st.iters, st.ls_halvings, st.E, rc);
+        }
+        if (pcgCoarse) {
+            int32_t dim = 0, dropped = 0, active = 0;
+            int64_t builds = 0, solves = 0, cgIters = 0;
+            if (dotmi_pcg_coarse_info(ts.handle(), &dim, &dropped, &active, &builds) != 0 ||
+                dotmi_pcg_info(ts.handle(), &solves, &cgIters, nullptr, nullptr) != 0)
+                throw std::runtime_error("dotmi_pcg_coarse_info failed");
+            std::printf("PCG coarse space: dimension %d, %d dropped, active %d, %lld builds, %lld CG iterations in %lld solves\n", dim,
+                        dropped, active, (long long)builds, (long long)cgIters, (long long)solves);
         }
         if (files) {
             timers.descent = tStep;

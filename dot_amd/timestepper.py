@@ -306,6 +306,33 @@ class DOTTimeStepper:
                                            C.cast(C.byref(lr), _lib.c_dp)), "pcg_info")
         return ns.value, ni.value, li.value, lr.value
 
+    def setPCGCoarse(self, mode: int = 1):
+        """the rigid-mode coarse term of the PCG's preconditioner, M = M_sym + Z A0^-1 Z^T: 0 off (the default), 1 on
+        (dotmi_set_pcg_coarse).  A0 is rebuilt by the first solve after every refresh of H."""
+        self._check(self._L.dotmi_set_pcg_coarse(self._h, mode), "set_pcg_coarse")
+
+    def pcgCoarseInfo(self):
+        """(dimension 6 nParts, subdomains the last build dropped, active, builds since create) (dotmi_pcg_coarse_info)"""
+        dim, dr, ac, nb = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+        self._check(self._L.dotmi_pcg_coarse_info(self._h, C.cast(C.byref(dim), _lib.c_ip), C.cast(C.byref(dr), _lib.c_ip),
+                                                  C.cast(C.byref(ac), _lib.c_ip), C.byref(nb)), "pcg_coarse_info")
+        return dim.value, dr.value, ac.value, nb.value
+
+    def pcgCoarseMatrix(self) -> np.ndarray:
+        """the last assembled coarse matrix A0 = Z^T H Z, dense (6 nParts, 6 nParts) (dotmi_pcg_coarse_matrix)"""
+        nc = self._check(self._L.dotmi_pcg_coarse_matrix(self._h, 0, None), "pcg_coarse_matrix")
+        A0 = np.empty((nc, nc))
+        self._check(self._L.dotmi_pcg_coarse_matrix(self._h, nc * nc, dp(A0)), "pcg_coarse_matrix")
+        return A0
+
+    def pcgApplyPrecond(self, r) -> np.ndarray:
+        """one application of the PCG's preconditioner as the solve uses it: M_sym r, plus the coarse term when it is active
+        (dotmi_pcg_apply_precond)"""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        w = np.empty((self.nV, 3))
+        self._check(self._L.dotmi_pcg_apply_precond(self._h, dp(r), dp(w)), "pcg_apply_precond")
+        return w
+
     def multiply(self, p) -> np.ndarray:
         p = np.ascontiguousarray(p, dtype=np.float64)
         out = np.empty((self.nV, 3))

@@ -468,6 +468,36 @@ int dotmi_solve_hessian(dotmi_handle *h, const double *b, double *u, double rel_
 int dotmi_set_pcg(dotmi_handle *h, double rel_tol, int32_t max_iter, int32_t check_every);
 /* counters of the handle's PCG solves since create (steps and dotmi_solve_hessian alike); any pointer may be NULL */
 int dotmi_pcg_info(const dotmi_handle *h, int64_t *solves, int64_t *iters_total, int32_t *last_iters, double *last_rel_res);
+/* The rigid-mode coarse space of the PCG's preconditioner (dot_amd/csrc/dotmi_coarse.hip, k_coarse.hip; DESIGN.md section 9 -- the
+ * reference has no counterpart).  mode 0 = off (the default: the solves run exactly the launches they run without this entry),
+ * 1 = M = M_sym + Z A0^-1 Z^T with A0 = Z^T H Z and six columns of Z per subdomain s: on a vertex v of s the block
+ * w_v [I | -[x_v - c_s]x], w_v = 1 / dup_v on free vertices and 0 on fixed ones, c_s the w-weighted centroid of s.  Every refresh of H
+ * (a Newton iteration, dotmi_refactor, dotmi_refix, dotmi_set_time_step, dotmi_set_lame) marks A0 stale; the next solve with the mode
+ * on rebuilds it with x = the handle's current iterate, frozen together with the centroids until the next build.  A subdomain with
+ * fewer than 3 free vertices gets zero columns and an identity block.  If A0 still meets a non-positive pivot (collinear free
+ * vertices) the coarse term is off until the next successful build: the solves run on M_sym alone, the handle is not poisoned.
+ * DOTMI_E_INVALID on the handles dotmi_solve_hessian refuses and on a vpart handle, for any other mode, and above 256 subdomains
+ * (A0^-1 is applied through a dense inverse factor of dimension 6 nParts <= 1536: a storage choice).  No device work. */
+int dotmi_set_pcg_coarse(dotmi_handle *h, int32_t mode);
+/* *dim = 6 nParts with the mode on, else 0; the subdomains the last build dropped; *active = 1 when the solves add the coarse term
+ * (0 with the mode off, before the first build and after a failed factorisation); the builds since create.  Any pointer may be NULL. */
+int dotmi_pcg_coarse_info(const dotmi_handle *h, int32_t *dim, int32_t *dropped_subdomains, int32_t *active, int64_t *builds);
+/* the last assembled A0, dense dim x dim, row-major (identity blocks on dropped subdomains) -- for tests, like dotmi_ic_factor.
+ * Returns dim (A0 == NULL: only that); cap: room in A0, in doubles; DOTMI_E_INVALID before the first build. */
+int dotmi_pcg_coarse_matrix(dotmi_handle *h, int32_t cap, double *A0);
+/* one application of the preconditioner exactly as the PCG uses it: w = M_sym r, plus Z A0^-1 Z^T r when the coarse term is active
+ * (a stale A0 is rebuilt first).  r, w: nV*3.  Refused like dotmi_solve_hessian. */
+int dotmi_pcg_apply_precond(dotmi_handle *h, const double *r, double *w);
+/* (host only) the lists of the coarse space (dot_amd/csrc/coarse_plan.hpp) for an element partition epart[nT] into nParts <= 256
+ * subdomains.  sizes[3] = {coupled pairs nP, entries nE, (vertex, subdomain) incidences nI}; call with NULL arrays first.
+ * pairS[nP], pairT[nP]: every unordered pair of subdomains some H block couples once, s <= t, diagonals included, ordered by (s, t);
+ * pairPtr[nP + 1] / pairBlk[nE]: per pair the H blocks (i, j) with i in s and j in t as indices into the global block-CSR (vertex
+ * adjacency incl. self, ascending), ascending -- one entry per (H block, s containing i, t containing j, s <= t); vsPtr[nV + 1] /
+ * vsIdx[nI]: per vertex its subdomains, ascending; svPtr[nParts + 1] / svIdx[nI]: per subdomain its vertices, ascending.  Any array
+ * may be NULL. */
+int dotmi_plan_coarse(int32_t nV, int32_t nT, const int32_t *T, const int32_t *epart, int32_t nParts, int32_t *sizes, int32_t *pairS,
+                      int32_t *pairT, int32_t *pairPtr, int32_t *pairBlk, int32_t *vsPtr, int32_t *vsIdx, int32_t *svPtr,
+                      int32_t *svIdx);
 
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* Launch the subdomain back-solve kernel `reps` times on the handle's stream between two HIP events
