@@ -79,9 +79,15 @@ int dotmi_refix(dotmi_handle *h, const uint8_t *fixed)
     if (resolve_refresh(h) == DOTMI_E_DEVICE) return DOTMI_E_DEVICE;   // (asynchronous refresh of the last step)
     h->fixed.assign(fixed, fixed + h->nV);
     HIPCHECK(h, hipMemcpy(h->M.fixed, fixed, h->nV, hipMemcpyHostToDevice));
+    if (h->VP.orec) {   // the patch-order copy of the flags (VpOwnRec; mass and the copies' positions never change on a live handle)
+        refix_vpatch_records(h->vpRecGid, fixed, h->vpRec);
+        HIPCHECK(h, hipMemcpy(const_cast<VpOwnRec *>(h->VP.orec), h->vpRec.data(), sizeof(VpOwnRec) * h->vpRec.size(), hipMemcpyHostToDevice));
+    }
     if (h->pd) return pd_factor(h);   // L for the new fixed set (LBFGSTimeStepper::updatePrecondMtrAndFactorize, :266-270)
     return refactor(h, h->x, nullptr, nullptr);
 }
+
+int dotmi_operand_records(const dotmi_handle *h) { return h && h->vpFits ? (h->VP.orec ? 1 : 0) : -1; }
 
 double dotmi_target_gres(const dotmi_handle *h) { return h ? h->targetGRes : 0.0; }
 

@@ -838,6 +838,34 @@ int dotmi_plan_vpatches(int32_t nV, int32_t nT, const int32_t *T, const double *
     return 0;
 }
 
+// host-only: the owned vertices' static operands in patch order (vpatches.hpp: build_vpatch_records, what dotmi_create uploads as
+// DevVPatches::orec) from the caller's flat arrays; see include/dotmi.h
+int dotmi_plan_vpatch_records(int32_t nV, int32_t nT, const int32_t *T, const double *X, int32_t PE, int32_t max_own, const double *mass,
+                              const uint8_t *fixed, const int32_t *vp_ptr, const int32_t *vp_off, const uint8_t *fixed2, int32_t *hdr,
+                              int32_t *pv_gid, int32_t *po_cnt, double *rec_mass, int32_t *rec_fixed, int32_t *rec_cnt, int32_t *rec_off)
+{
+    if (nV < 1 || nT < 1 || !T || !X || PE < 1 || max_own < 1 || !mass || !fixed || !vp_ptr || !vp_off || !hdr) return DOTMI_E_INVALID;
+    const HostVPatches H = build_vpatches(nV, nT, T, X, PE, max_own);
+    hdr[0] = H.nPatches;
+    hdr[1] = H.PE;
+    hdr[2] = H.PV;
+    hdr[3] = H.PO;
+    hdr[4] = H.RUN;
+    if (!pv_gid || H.nPatches == 0) return 0;
+    if (!po_cnt || !rec_mass || !rec_fixed || !rec_cnt || !rec_off) return DOTMI_E_INVALID;
+    std::vector<VpOwnRec> R = build_vpatch_records(H, mass, fixed, vp_ptr, vp_off);
+    if (fixed2) refix_vpatch_records(vpatch_own_gid(H), fixed2, R);   // (what dotmi_refix does to the handle's copy)
+    std::copy(H.pv_gid.begin(), H.pv_gid.end(), pv_gid);
+    std::copy(H.po_cnt.begin(), H.po_cnt.end(), po_cnt);
+    for (size_t i = 0; i < R.size(); ++i) {
+        rec_mass[i] = R[i].mass;
+        rec_fixed[i] = R[i].fixed;
+        rec_cnt[i] = R[i].cnt;
+        for (int c = 0; c < 4; ++c) rec_off[4 * i + c] = R[i].off[c];
+    }
+    return 0;
+}
+
 // host-only: the level schedule of tile_factor.hpp for ONE block of nt x nt tiles with the given upper tile pattern, in the
 // compact row-block layout (c0[j] = first tile column stored for tile row j, c0[j] <= every pattern entry of column j).
 // Offsets are in doubles into one array: the factor storage first, the scratch tiles after it (*scratch_base).
@@ -1541,13 +1569,30 @@ static int choose_loop_form(dotmi_handle *h)
         (h->mat == DOTMI_ENERGY_SNH || h->tune.vertexPatches > 0) &&
         h->P.ntiles - h->P.ntilesWide + h->P.nquad > 0 && !(h->flags & (DOTMI_FLAG_GSDD | DOTMI_FLAG_NEWTON | DOTMI_FLAG_NEWTON_PCG | DOTMI_FLAG_HOST_LOOP))) {
         const HostVPatches HV = build_vpatches(h->nV, h->nT, h->T.data(), h->Xrest.data(), 512, 85);
-        const size_t shm = sizeof(double) * ((size_t)3 * HV.PV + (size_t)3 * HV.RUN) + 2 * (size_t)((HV.PO + 1 + 3) & ~3);
+        // (the kernel's static LDS counts against the 64 KB of a workgroup too)
+        // the records are chosen per handle, only where their 6 PO doubles still fit: a mesh whose patches fit without them keeps
+        // the one-launch form on the flat arrays (orec stays null)
+        const bool rec = h->tune.operandRecords != 0 && HV.nPatches > 0 &&
+                         elem_vertex_dyn_lds(HV.PV, HV.RUN, HV.PO, true) + ELEM_VERTEX_STATIC_LDS <= 64 * 1024;
+        const size_t shm = HV.nPatches > 0 ? elem_vertex_dyn_lds(HV.PV, HV.RUN, HV.PO, rec) + ELEM_VERTEX_STATIC_LDS : 0;
         if (HV.nPatches > 0 && HV.nPatches <= 512 && HV.nPatches <= ELEM_NB_MAX && shm <= 64 * 1024 && HV.PO + 1 <= 256) {
             if (int rc = upload_vpatches(h, HV, h->VP, h->smVP)) return rc;
+            if (rec) {
+                // the owned vertices' static operands in patch order, from the flat arrays as they are on the device
+                std::vector<int> vpp((size_t)h->nV + 1), vpo;
+                HIPCHECK(h, hipMemcpy(vpp.data(), h->P.vp_ptr, sizeof(int) * vpp.size(), hipMemcpyDeviceToHost));
+                vpo.resize((size_t)std::max(vpp[h->nV], 1));
+                HIPCHECK(h, hipMemcpy(vpo.data(), h->P.vp_off, sizeof(int) * (size_t)vpp[h->nV], hipMemcpyDeviceToHost));
+                h->vpRec = build_vpatch_records(HV, h->mass.data(), h->fixed.data(), vpp.data(), vpo.data());
+                h->vpRecGid = vpatch_own_gid(HV);
+                VpOwnRec *d = nullptr;
+                if (int rc = upload(h, &d, h->vpRec)) return rc;
+                h->VP.orec = d;
+            }
             h->vpFits = true;
             if (h->tune.fuseLog)
-                fprintf(stderr, "dotmi: vertex patches: %d patches, %.2f x the elements, up to %d owned / %d touched vertices, runs %d, %zu B LDS\n",
-                        HV.nPatches, (double)h->VP.nSlotsUsed / std::max(1, h->nT), HV.PO, HV.PV, HV.RUN, shm);
+                fprintf(stderr, "dotmi: vertex patches: %d patches, %.2f x the elements, up to %d owned / %d touched vertices, runs %d, %zu B LDS, operand records %s\n",
+                        HV.nPatches, (double)h->VP.nSlotsUsed / std::max(1, h->nT), HV.PO, HV.PV, HV.RUN, shm, rec ? "on" : "off");
         }
     }
     return 0;
@@ -1559,6 +1604,11 @@ static int alloc_loop_state(dotmi_handle *h)
     if (h->dist) {
         if (int rc = dalloc(h, &h->zstage, (size_t)h->n)) return rc;
         HIPCHECK(h, hipMemsetAsync(h->zstage, 0, sizeof(double) * h->n, h->st));   // (owner exchange: stays zero off the held set)
+    }
+    if (h->vpFits && h->VP.orec) {   // the pairs as records (DevLoop::hrec): zeroed once, every step starts with an empty history
+        const size_t nrec = (size_t)2 * (HIST_MAX + 1) * h->n;
+        if (int rc = dalloc(h, &h->hrec, nrec)) return rc;
+        HIPCHECK(h, hipMemsetAsync(h->hrec, 0, sizeof(double) * nrec, h->st));
     }
     if (h->earlyBs) {
         if (int rc = dalloc(h, &h->u_old, (size_t)h->n)) return rc;

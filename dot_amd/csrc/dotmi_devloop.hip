@@ -292,6 +292,7 @@ static int init_devloop(dotmi_handle *h, int *notifyFrom)
         C.HS[s] = h->HS[s];
     }
     C.u_old = h->u_old;
+    C.hrec = h->hrec;
     devloop_resolve(C);   // (slot 0, no pair yet)
     C.holdEnable = h->tune.earlyHold ? 1 : 0;
     // the forecast carries over from the last step (a function of the handle's own history)

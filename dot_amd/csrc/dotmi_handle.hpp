@@ -116,6 +116,10 @@ struct Tuning {
                               //                      gradient with the controller inside its launch, in the steps where
                               //                      the last step's counts say it pays (choose_step_forms); 2 (default): in
                               //                      every step
+    int operandRecords = 1;   // DOTMI_OPERAND_RECORDS bit 0 (default on): elem_vertex_kernel's per-owned-vertex operands as records --
+                              //                      the static ones in patch order (VpOwnRec), the stored pairs as (s, y) entries
+                              //                      (DevLoop::hrec), p and x~ of the owned dofs through LDS; 0: the flat arrays behind
+                              //                      the vertex id (until round 8).  Bit-identical either way
     static int geti(const char *name, int dflt)
     {
         const char *ev = getenv(name);
@@ -157,6 +161,7 @@ struct Tuning {
         t.vertexPatches = geti("DOTMI_VERTEX_PATCHES", -1);
         t.fuseStep = geti("DOTMI_FUSE_STEP", 1) != 0;
         t.fuseDir = geti("DOTMI_FUSE_DIR", 1) != 0;
+        t.operandRecords = geti("DOTMI_OPERAND_RECORDS", 1) & 1;
         return t;
     }
 };
@@ -252,6 +257,11 @@ struct dotmi_handle {
     // pairs or speculates keeps the element patches -- one patch set per step, so its energies are grouped alike)
     DevVPatches VP;
     bool vpFits = false, vpNow = false;
+    // DOTMI_OPERAND_RECORDS: the host copy of VP.orec with its vertex ids (dotmi_refix rewrites the fixed flags and uploads it again)
+    // and the history records DevLoop::hrec (3 nV x (HIST_MAX + 1) pairs); empty / null without the records
+    std::vector<VpOwnRec> vpRec;
+    std::vector<int> vpRecGid;
+    double *hrec = nullptr;
     // dotmi_set_lame: per family of patches the slot -> element table (-1: padding) that upload_patches / upload_vpatches fill the
     // per-slot Lame parameters through, kept on the device, and the family's slot arrays (null until a field that is not one
     // material needs them; then kept).  PT and PTspec are entered only where they are patch sets of their own.

@@ -62,6 +62,7 @@ struct DevPatches {
 };
 
 // ---- vertex patches (vpatches.hpp): element pass + vertex gather in one launch (k_elemvert.hip) -------------------------------------
+struct VpOwnRec;   // vpatches.hpp
 struct DevVPatches {
     int nPatches = 0, PE = 0, PV = 0, PO = 0, RUN = 0, nSlotsUsed = 0;
     ushort4 *tl = nullptr, *epos = nullptr;   // nPatches*PE: corners' patch-local vertex indices / positions in their vertices' runs (0xFFFF: not owned)
@@ -71,7 +72,16 @@ struct DevVPatches {
     double mu0 = 0.0, lam0 = 0.0;
     int *pv_gid = nullptr, *pv_cnt = nullptr, *po_cnt = nullptr;   // touched vertices (owned first) / their number / the owned ones
     unsigned short *c_ptr = nullptr;          // per patch (PO+1): offsets of the owned vertices' runs
+    // round 9 (DOTMI_OPERAND_RECORDS bit 0; nullptr: the flat arrays behind the vertex id): per (patch, owned vertex) one VpOwnRec
+    // (vpatches.hpp) -- mass, fixed, the vertex' copy count and its first four padded right-hand-side positions; nPatches * PO
+    const VpOwnRec *orec = nullptr;
 };
+// LDS of one elem_vertex_kernel workgroup: xs[3 PV] | gs[3][RUN] | (records: p and x~ of the owned dofs, 3 PO each) | cptr (u16)
+inline size_t elem_vertex_dyn_lds(int PV, int RUN, int PO, bool rec)
+{
+    return sizeof(double) * ((size_t)3 * PV + (size_t)3 * RUN + (rec ? (size_t)6 * PO : 0)) + 2 * (size_t)((PO + 1 + 3) & ~3);
+}
+constexpr size_t ELEM_VERTEX_STATIC_LDS = sizeof(double) * (4 * RED_K + 8 + 1);   // sm, sme, sh_alpha
 struct ElemVertArgs {
     const double *mass, *xt, *p, *hp;
     const double *spmv_partials;   // p.g / p.Hp partials, COLUMN-major [2][NB_RED] (launch_spmv_zp's partialsT)
@@ -306,6 +316,13 @@ struct DevLoop {
     // pointers resolved and all of a kernel's loop-state loads issued in front of its first branch that is ONE round trip
     // instead of three (tools/prof_loopkern.sh: 2.9 us of the gather's 6.2 and of merge_early's 9.6 were this prologue).
     double *s_new, *y_new, *hs_new;          // S[slot], Y[slot], HS[slot]: the pair of the running trial
+    // Round 9 (DOTMI_OPERAND_RECORDS bit 0, vertex patches): the pairs once more as RECORDS -- hrec[vertex][slot 0 .. HIST_MAX]
+    // [component] = (s, y), 16 bytes an entry, so that elem_vertex_kernel's lane (vertex, component) reads a stored pair with one
+    // 16-byte load instead of two 8-byte gathers from two arrays.  Written by that kernel beside S[slot] / Y[slot] (the flat arrays
+    // stay: every other kernel reads them); nothing crosses steps (the history starts empty).  hrec == nullptr: no records.
+    // rec_new = hrec + 6 slot, Lrec[i] = hrec + 6 order[i]: an entry is at [(HIST_MAX + 1) * 6 * vertex + 2 * component].
+    double *hrec, *rec_new;
+    const double *Lrec[HIST_MAX];
     double *my_new;                          // MY[order[m - 1]]: where M y of the newest stored pair goes (merge_early)
     const double *Lmy[HIST_MAX], *Lhs[HIST_MAX];   // chronological views like L.s / L.y: M y_i, H s_i of the stored pairs
 };
@@ -322,6 +339,8 @@ __host__ __device__ inline void devloop_resolve(DL &C)
         C.Lhs[i] = i < m ? C.HS[C.order[i]] : nullptr;
     }
     C.my_new = m > 0 ? C.MY[C.order[m - 1]] : nullptr;
+    C.rec_new = C.hrec ? C.hrec + 6 * C.slot : nullptr;
+    for (int i = 0; i < HIST_MAX; ++i) C.Lrec[i] = (i < m && C.hrec) ? C.hrec + 6 * C.order[i] : nullptr;
 }
 // owner exchange: the vertices a rank holds -- the vector kernels of the loop then visit only these (everything else is zero
 // and stays zero); v == nullptr: every vertex

@@ -22,8 +22,12 @@
 // patches: loop_control_body<CTL_VP>).
 // ctl == nullptr: the evaluation at the start of a step (no step, no pair: x0 -> g0, |g|^2, -g into the right-hand sides).
 #include "k_device.hpp"
+#include "vpatches.hpp"   // VpOwnRec
 
 namespace dotmi {
+
+// a 16-byte (s, y) entry of DevLoop::hrec as ONE access (the native vector type: a struct of two doubles is copied member by member)
+typedef double ev_pair __attribute__((ext_vector_type(2)));
 
 constexpr int EV_EPT = 2;   // element slots per thread (vertex patches of 512 slots)
 
@@ -42,7 +46,15 @@ extern "C" int dotmi_debug_evprof(long long *out)
 // PAIR: the instantiation of a step with paired line-search trials (elem_patch_body's: when alpha_0 < 1 the first half of a launch
 // twice as wide evaluates alpha_0 / 2 in full and the second half -- workgroup nP + b mirrors patch b -- the ENERGY at alpha_0,
 // into the second half of the energy partials; otherwise the second half leaves at once)
-template <int MAT, bool PAIR>
+//
+// REC (round 9, DOTMI_OPERAND_RECORDS bit 0): phase 3's per-vertex operands arrive as records instead of 8-byte gathers behind the
+// vertex id.  (1) the static ones -- mass, fixed, the copies' positions -- from VP.orec in patch order: two 16-byte loads that depend
+// on the workgroup's index only, no second round trip for vp_off; (2) the stored pairs (s_i, y_i) from DevLoop::Lrec, one 16-byte
+// load per pair, the new pair written there too (beside the flat S / Y every other kernel reads); (3) p at an owned dof is what
+// thread `ov` loaded for phase 1 (owned vertices lead the touched list) and x~ of a vertex' other two components what its
+// neighbour lanes loaded: both through LDS (a vertex' three lanes can straddle a wave).  The same values in the same
+// operations: bit-identical to REC = false (tests/test_gpu_operand_records.py).
+template <int MAT, bool PAIR, bool REC>
 __global__ __launch_bounds__(256) void elem_vertex_kernel(DevVPatches VP, ElemVertArgs a, const DevLoop *__restrict__ ctl)
 {
     extern __shared__ double lds[];
@@ -63,6 +75,8 @@ __global__ __launch_bounds__(256) void elem_vertex_kernel(DevVPatches VP, ElemVe
     const double *__restrict__ g_old = nullptr;
     double *__restrict__ s_new = nullptr, *__restrict__ y_new = nullptr, *__restrict__ hs_new = nullptr;
     const double *hs[HIST_MAX], *hy[HIST_MAX];
+    const ev_pair *hr[HIST_MAX];
+    ev_pair *rec_new = nullptr;
     int hm = 0, lphase = 1;
     double lalpha = 0.0;
     const bool loop = ctl != nullptr;
@@ -80,9 +94,14 @@ __global__ __launch_bounds__(256) void elem_vertex_kernel(DevVPatches VP, ElemVe
         hm = ctl->L.m;
 #pragma unroll
         for (int i = 0; i < HIST_MAX; ++i) {
-            hs[i] = ctl->L.s[i];
-            hy[i] = ctl->L.y[i];
+            if constexpr (REC) {
+                hr[i] = reinterpret_cast<const ev_pair *>(ctl->Lrec[i]);
+            } else {
+                hs[i] = ctl->L.s[i];
+                hy[i] = ctl->L.y[i];
+            }
         }
+        if constexpr (REC) rec_new = reinterpret_cast<ev_pair *>(ctl->rec_new);
         if (status != 0) return;
     }
 #ifdef K_PROFILE
@@ -99,10 +118,11 @@ __global__ __launch_bounds__(256) void elem_vertex_kernel(DevVPatches VP, ElemVe
             pHpv[u] = a.spmv_partials[NB_RED + tid + 64 * u];
         }
     }
-    // ---- LDS: xs[3 PV] | gs[3][RUN] | cptr[PO + 1 .. padded to 4] (u16) ---------------------------------------------------------
+    // ---- LDS: xs[3 PV] | gs[3][RUN] | REC: po[3 PO] | xo[3 PO] | cptr[PO + 1 .. padded to 4] (u16) ------------------------------
     constexpr int PE = 256 * EV_EPT;
     double *xs = lds, *gs = lds + 3 * VP.PV;
-    unsigned short *cptr = reinterpret_cast<unsigned short *>(gs + 3 * VP.RUN);
+    double *po = gs + 3 * VP.RUN, *xo = po + 3 * VP.PO;   // (REC) p and x~ at the owned dofs, indexed by phase 3's lane
+    unsigned short *cptr = reinterpret_cast<unsigned short *>(REC ? xo + 3 * VP.PO : po);
     // (the vertex ids do not wait for the patch's counts: the touched list is padded with -1, and a lane of phase 3 beyond the owned
     // vertices reads a touched vertex it then ignores -- one dependent round trip less in front of the positions)
     const int nv = VP.pv_cnt[p], no = VP.po_cnt[p];
@@ -116,6 +136,16 @@ __global__ __launch_bounds__(256) void elem_vertex_kernel(DevVPatches VP, ElemVe
     const int ogid_raw = ov < VP.PV ? VP.pv_gid[vb + ov] : -1;
     const bool vlane = tid < 3 * no;
     const int ogid = vlane ? ogid_raw : -1;
+    // (REC) the owned vertex' static record: its address needs neither the vertex id nor the patch's counts
+    double2 rq0 = make_double2(0.0, 0.0);
+    int4 rq1 = make_int4(0, 0, 0, 0);
+    if constexpr (REC) {
+        if (ov < VP.PO) {
+            const VpOwnRec *r = VP.orec + ((size_t)p * VP.PO + ov);
+            rq0 = *reinterpret_cast<const double2 *>(r);
+            rq1 = *reinterpret_cast<const int4 *>(&r->off[0]);
+        }
+    }
     // ---- element operands (patch order: every load of a wave is one contiguous run) ---------------------------------------------
     ushort4 tl[EV_EPT], ep[EV_EPT];
     double Ai[EV_EPT][9], mu_[EV_EPT], la_[EV_EPT], vo[EV_EPT], voE[EV_EPT];
@@ -148,7 +178,26 @@ __global__ __launch_bounds__(256) void elem_vertex_kernel(DevVPatches VP, ElemVe
     int cb = 0, ce = 0;
 #pragma unroll
     for (int i = 0; i < HIST_MAX; ++i) si[i] = yi[i] = 0.0;
-    if (vlane) {
+    if constexpr (REC) {
+        if (vlane) {
+            fx = __double2hiint(rq0.y) != 0;   // (VpOwnRec: mass | cnt, fixed | off[4])
+            ms = rq0.x;
+            ce = __double2loint(rq0.y);        // cb = 0: the copies are counted from the record's first
+            xt_own = a.xt[ok];
+            if (loop) {
+                gold = g_old[ok];
+                hpk = a.hp[ok];
+                const size_t rk = (size_t)(3 * (HIST_MAX + 1)) * ogid + od;   // the lane's entry of a slot, in (s, y) pairs
+#pragma unroll
+                for (int i = 0; i < HIST_MAX; ++i) {
+                    ev_pair sy = {0.0, 0.0};
+                    if (i < hm) sy = hr[i][rk];
+                    si[i] = sy.x;
+                    yi[i] = sy.y;
+                }
+            }
+        }
+    } else if (vlane) {
         fx = a.fixed[ogid] != 0;
         ms = a.mass[ogid];
         xt_own = a.xt[ok];
@@ -207,6 +256,12 @@ __global__ __launch_bounds__(256) void elem_vertex_kernel(DevVPatches VP, ElemVe
     if (gid >= 0) {
 #pragma unroll
         for (int d = 0; d < 3; ++d) xs[3 * tid + d] = loop ? xv[d] + alpha * pv[d] : xv[d];
+        if constexpr (REC) {
+            if (loop && tid < no) {   // an owned vertex: its direction is phase 3's p at the dofs 3 tid .. 3 tid + 2
+#pragma unroll
+                for (int d = 0; d < 3; ++d) po[3 * tid + d] = pv[d];
+            }
+        }
     }
     for (int lv = tid + 256; lv < nv; lv += 256) {   // (a patch that touches more than 256 vertices)
         const int g2 = VP.pv_gid[vb + lv];
@@ -219,8 +274,15 @@ __global__ __launch_bounds__(256) void elem_vertex_kernel(DevVPatches VP, ElemVe
     // long arrived, not in front of the barriers above; used at the end)
     constexpr int VC = 4;   // copies of a vertex (subdomains that hold it) whose positions are requested ahead of the stores
     int vof[VC];
+    if constexpr (REC) {
+        vof[0] = rq1.x;
+        vof[1] = rq1.y;
+        vof[2] = rq1.z;
+        vof[3] = rq1.w;
+    } else {
 #pragma unroll
-    for (int c = 0; c < VC; ++c) vof[c] = (cb + c < ce) ? a.vp_off[cb + c] : 0;
+        for (int c = 0; c < VC; ++c) vof[c] = (cb + c < ce) ? a.vp_off[cb + c] : 0;
+    }
     // ---- phase 2: elements ------------------------------------------------------------------------------------------------------
     double acc = 0.0;   // sum vol * Psi over the elements whose energy this patch counts
 #pragma unroll
@@ -285,8 +347,21 @@ __global__ __launch_bounds__(256) void elem_vertex_kernel(DevVPatches VP, ElemVe
                 gs[2 * VP.RUN + pkk[k]] = g[3 * k + 2];
             }
     }
+    if constexpr (REC) {
+        if (vlane) xo[tid] = xt_own;   // (published by the barrier below: the x~ a vertex' lane 0 needs of its two neighbours)
+    }
     __syncthreads();
     EVSTAMP(4);
+    if constexpr (REC) {
+        if (vlane) {
+            if (loop) pk = po[tid];
+            if (od == 0) {
+                xtv[0] = xt_own;
+                xtv[1] = xo[tid + 1];
+                xtv[2] = xo[tid + 2];
+            }
+        }
+    }
     // ---- phase 3: the owned vertices --------------------------------------------------------------------------------------------
     double st[RED_K];
 #pragma unroll
@@ -317,13 +392,21 @@ __global__ __launch_bounds__(256) void elem_vertex_kernel(DevVPatches VP, ElemVe
 #pragma unroll
         for (int c = 0; c < VC; ++c)
             if (cb + c < ce) a.rpad[vof[c] + od] = -g;
-        for (int c = cb + VC; c < ce; ++c) a.rpad[a.vp_off[c] + od] = -g;
+        if constexpr (REC) {
+            if (ce > VC) {   // (a vertex with more than four copies: the rest through the flat lists)
+                const int c0 = a.vp_ptr[ogid];
+                for (int c = c0 + VC; c < c0 + ce; ++c) a.rpad[a.vp_off[c] + od] = -g;
+            }
+        } else {
+            for (int c = cb + VC; c < ce; ++c) a.rpad[a.vp_off[c] + od] = -g;
+        }
         st[0] = g * g;
         if (loop) {
             const double sn = alpha * pk;
             const double yn = g - gold;
             s_new[ok] = sn;
             y_new[ok] = yn;
+            if constexpr (REC) rec_new[(size_t)(3 * (HIST_MAX + 1)) * ogid + od] = ev_pair{sn, yn};
             hs_new[ok] = alpha * hpk;   // H s_new = alpha H p
             st[1] = yn * sn;
             st[2] = sn * g;
@@ -360,15 +443,22 @@ __global__ __launch_bounds__(256) void elem_vertex_kernel(DevVPatches VP, ElemVe
 
 void launch_elem_vertex(const DevVPatches &VP, int mat, const ElemVertArgs &a, hipStream_t st, const DevLoop *ctl)
 {
-    const size_t shm = sizeof(double) * ((size_t)3 * VP.PV + (size_t)3 * VP.RUN) + 2 * (size_t)((VP.PO + 1 + 3) & ~3);
+    const bool rec = VP.orec != nullptr;   // (the handle then has DevLoop::hrec as well: alloc_loop_state)
+    const size_t shm = elem_vertex_dyn_lds(VP.PV, VP.RUN, VP.PO, rec);
     const bool paired = ctl && a.alpha_min < 0.0;
+#define EV_LAUNCH(MATV, PAIRV, NWG)                                                                                          \
+    do {                                                                                                                     \
+        if (rec) hipLaunchKernelGGL((elem_vertex_kernel<MATV, PAIRV, true>), dim3(NWG), dim3(256), shm, st, VP, a, ctl);     \
+        else hipLaunchKernelGGL((elem_vertex_kernel<MATV, PAIRV, false>), dim3(NWG), dim3(256), shm, st, VP, a, ctl);        \
+    } while (0)
     if (paired) {
-        if (mat == 0) hipLaunchKernelGGL((elem_vertex_kernel<0, true>), dim3(2 * VP.nPatches), dim3(256), shm, st, VP, a, ctl);
-        else hipLaunchKernelGGL((elem_vertex_kernel<1, true>), dim3(2 * VP.nPatches), dim3(256), shm, st, VP, a, ctl);
+        if (mat == 0) EV_LAUNCH(0, true, 2 * VP.nPatches);
+        else EV_LAUNCH(1, true, 2 * VP.nPatches);
     } else {
-        if (mat == 0) hipLaunchKernelGGL((elem_vertex_kernel<0, false>), dim3(VP.nPatches), dim3(256), shm, st, VP, a, ctl);
-        else hipLaunchKernelGGL((elem_vertex_kernel<1, false>), dim3(VP.nPatches), dim3(256), shm, st, VP, a, ctl);
+        if (mat == 0) EV_LAUNCH(0, false, VP.nPatches);
+        else EV_LAUNCH(1, false, VP.nPatches);
     }
+#undef EV_LAUNCH
 }
 
 }  // namespace dotmi

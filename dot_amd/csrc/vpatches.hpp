@@ -160,4 +160,50 @@ inline HostVPatches build_vpatches(int nV, int nT, const int32_t *T, const doubl
     return H;
 }
 
+// ---- round 9: what phase 3 of elem_vertex_kernel needs of an owned vertex, in PATCH order ------------------------------------------
+// One 32-byte record per (patch, owned vertex), nPatches * PO of them (zeros behind a patch's po_cnt): the lane (vertex, component)
+// reads it with two 16-byte loads that depend on nothing but the workgroup's index -- instead of fixed[gid], mass[gid],
+// vp_ptr[gid], vp_ptr[gid + 1] behind the vertex id and vp_off[cb .. cb + 3] a second round trip behind those.
+// Only `fixed` changes on a live handle (dotmi_refix: refix_vpatch_records in the same call).  mass, vp_ptr and vp_off are uploaded
+// once by dotmi_create and no entry point writes them afterwards (dotmi_set_lame / dotmi_set_time_step touch neither the lumped
+// masses nor the subdomains).
+struct VpOwnRec {
+    double mass;
+    int32_t cnt;      // copies of the vertex in the padded right-hand sides: vp_ptr[v + 1] - vp_ptr[v]
+    int32_t fixed;
+    int32_t off[4];   // vp_off[vp_ptr[v] + c], c < min(cnt, 4); 0 beyond (a vertex with more copies: the rest through vp_off)
+};
+static_assert(sizeof(VpOwnRec) == 32, "two 16-byte loads per lane");
+
+inline std::vector<VpOwnRec> build_vpatch_records(const HostVPatches &H, const double *mass, const uint8_t *fixed, const int *vp_ptr,
+                                                  const int *vp_off)
+{
+    std::vector<VpOwnRec> R((size_t)H.nPatches * H.PO, VpOwnRec{0.0, 0, 0, {0, 0, 0, 0}});
+    for (int p = 0; p < H.nPatches; ++p)
+        for (int lv = 0; lv < H.po_cnt[p]; ++lv) {
+            const int v = H.pv_gid[(size_t)p * H.PV + lv];
+            VpOwnRec &r = R[(size_t)p * H.PO + lv];
+            r.mass = mass[v];
+            r.fixed = fixed[v] != 0;
+            r.cnt = vp_ptr[v + 1] - vp_ptr[v];
+            for (int c = 0; c < 4 && c < r.cnt; ++c) r.off[c] = vp_off[vp_ptr[v] + c];
+        }
+    return R;
+}
+
+// own_gid: nPatches * PO, the owned vertices' ids in record order (-1: padding)
+inline std::vector<int> vpatch_own_gid(const HostVPatches &H)
+{
+    std::vector<int> g((size_t)H.nPatches * H.PO, -1);
+    for (int p = 0; p < H.nPatches; ++p)
+        for (int lv = 0; lv < H.po_cnt[p]; ++lv) g[(size_t)p * H.PO + lv] = H.pv_gid[(size_t)p * H.PV + lv];
+    return g;
+}
+
+inline void refix_vpatch_records(const std::vector<int> &own_gid, const uint8_t *fixed, std::vector<VpOwnRec> &R)
+{
+    for (size_t i = 0; i < own_gid.size(); ++i)
+        if (own_gid[i] >= 0) R[i].fixed = fixed[own_gid[i]] != 0;
+}
+
 }  // namespace dotmi

@@ -275,6 +275,18 @@ int dotmi_plan_patches(int32_t nV, int32_t nT, const int32_t *T, const double *X
  * vertex' gradient run in its patch).  tests/test_gpu_round6.py / test_host_logic.py */
 int dotmi_plan_vpatches(int32_t nV, int32_t nT, const int32_t *T, const double *X, int32_t PE, int32_t max_own, int32_t *hdr,
                         int32_t *owner, int32_t *elem, int32_t *eown, int32_t *runlen);
+/* (round 9) which loads the handle's one-launch element pass + gather (elem_vertex_kernel) uses: 1 = the operand records
+ * (DOTMI_OPERAND_RECORDS, default, where their LDS fits), 0 = the flat arrays, -1 = the handle has no vertex patches */
+int dotmi_operand_records(const dotmi_handle *h);
+/* (host only, round 9) the static operands of the owned vertices in PATCH order (vpatches.hpp: VpOwnRec, DOTMI_OPERAND_RECORDS), built
+ * from the caller's flat arrays as dotmi_create builds them from its own: mass[nV], fixed[nV] and the CSR vp_ptr[nV + 1] / vp_off of a
+ * vertex' copies in the padded right-hand sides.  hdr as dotmi_plan_vpatches; with pv_gid != NULL also pv_gid[patches * PV] (touched
+ * vertices, the owned ones first, -1 padding), po_cnt[patches] and per record (patches * PO, zeros behind po_cnt): rec_mass, rec_fixed,
+ * rec_cnt (copies of the vertex), rec_off[4] (its first four positions, 0 beyond the count).  fixed2 != NULL: the records after
+ * dotmi_refix's rewrite of the flags with that mask.  tests/test_operand_records.py */
+int dotmi_plan_vpatch_records(int32_t nV, int32_t nT, const int32_t *T, const double *X, int32_t PE, int32_t max_own, const double *mass,
+                              const uint8_t *fixed, const int32_t *vp_ptr, const int32_t *vp_off, const uint8_t *fixed2, int32_t *hdr,
+                              int32_t *pv_gid, int32_t *po_cnt, double *rec_mass, int32_t *rec_fixed, int32_t *rec_cnt, int32_t *rec_off);
 /* (host only) the level schedule of the tile factorisation for one nt x nt tile block with the given upper tile pattern in
  * the compact row-block layout; see dot_amd/csrc/tile_factor.hpp and tests/test_tile_schedule.py */
 int dotmi_plan_tile_schedule(int32_t nt, const uint8_t *live, const uint8_t *pattern, const int32_t *c0, int32_t eager_min,
