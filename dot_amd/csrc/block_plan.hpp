@@ -1,7 +1,7 @@
 // block_plan.hpp -- the planning of the subdomain block solve as a sequence of stages (host only): vertex sets -> dissection layout and
 // form -> padded rows -> factor storage -> fill / reduce / merge lists -> tile schedule of the factorisation -> two-level panels.
 // Plain data in, plain data out: no device call and no handle.  dotmi_create (build_device_mesh) runs the stages with the uploads of
-// each stage's arrays in between; the host-only entries dotmi_plan_layout / _backsolve_tiles / _backsolve_form / _rank run the
+// each stage's arrays in between; the host-only entries dotmi_plan_layout / _backsolve_tiles / _backsolve_form / _rank (dotmi_plan.cpp) run the
 // first ones on the caller's mesh, so that what tests/test_host_logic.py pins is the code dotmi_create runs.
 //
 // Role in the reference: the ADMMDDTimeStepper constructor (ADMMDDTimeStepper.cpp:88-262: subdomain vertex sets, local maps); the

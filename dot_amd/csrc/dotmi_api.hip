@@ -1,4 +1,4 @@
-// dotmi_api.hip -- the remaining entry points of include/dotmi.h: state, scripted handles, kernel-level calls for parity tests, probes, measurement
+// dotmi_api.hip -- the remaining entry points of include/dotmi.h: state, scripted handles, kernel-level calls for parity tests, probes, measurement, handle queries (factor kind / groups, back-solve form, communicator)
 #include "dotmi_handle.hpp"
 
 extern "C" {
@@ -691,6 +691,46 @@ int dotmi_bench_energy(dotmi_handle *h, int32_t reps, double *ms_per_launch, int
     // 112 B per tet + 56 B per vertex
     if (bytes_per_launch) *bytes_per_launch = (int64_t)112 * h->nOwnElem + (int64_t)56 * (h->v1 - h->v0);
     return 0;
+}
+
+int dotmi_comm_unique_id(void *out128)
+{
+    ncclUniqueId id;
+    if (ncclGetUniqueId(&id) != ncclSuccess) return DOTMI_E_DEVICE;
+    static_assert(sizeof(ncclUniqueId) == 128, "ncclUniqueId size");
+    memcpy(out128, &id, 128);
+    return 0;
+}
+
+int32_t dotmi_factor_kind(const dotmi_handle *h)
+{
+    if (!h) return DOTMI_E_INVALID;
+    return h->tileFlow ? 2 : h->tileSplit ? 3 : 1;
+}
+
+// the independent launch chains of the factorisation: the subdomain groups of the level launches (1: one chain, the dataflow
+// launch and the split levels included)
+int32_t dotmi_factor_groups(const dotmi_handle *h)
+{
+    if (!h) return DOTMI_E_INVALID;
+    return h->tgroupLevel.size() > 2 ? (int32_t)h->tgroupLevel.size() - 1 : 1;
+}
+
+int32_t dotmi_backsolve_form(const dotmi_handle *h)
+{
+    if (!h) return DOTMI_E_INVALID;
+    return h->twoLevel ? 1 : 0;
+}
+
+int32_t dotmi_comm_ranks(const dotmi_handle *h)
+{
+    if (!h) return DOTMI_E_INVALID;
+    if (h->comm) {
+        int n = 0;
+        if (ncclCommCount(h->comm, &n) != ncclSuccess) return DOTMI_E_DEVICE;
+        return n;
+    }
+    return h->arCb ? -h->world : 1;
 }
 
 }  // extern "C"

@@ -233,35 +233,4 @@ int dotmi_pcg_apply_precond(dotmi_handle *h, const double *r, double *w)
     return 0;
 }
 
-// host-only: the lists of the coarse assembly and of the per-iteration kernels.  sizes[3] = {pairs, entries, (vertex, subdomain)
-// incidences} always; the arrays (any may be NULL) as in coarse_plan.hpp
-int dotmi_plan_coarse(int32_t nV, int32_t nT, const int32_t *T, const int32_t *epart, int32_t nParts, int32_t *sizes, int32_t *pairS,
-                      int32_t *pairT, int32_t *pairPtr, int32_t *pairBlk, int32_t *vsPtr, int32_t *vsIdx, int32_t *svPtr, int32_t *svIdx)
-{
-    if (nV < 1 || nT < 1 || !T || !epart || !sizes || nParts < 1 || nParts > COARSE_MAX_PARTS) return DOTMI_E_INVALID;
-    for (int e = 0; e < 4 * nT; ++e)
-        if (T[e] < 0 || T[e] >= nV) return DOTMI_E_INVALID;
-    for (int e = 0; e < nT; ++e)
-        if (epart[e] < 0 || epart[e] >= nParts) return DOTMI_E_INVALID;
-    std::vector<int> adj_ptr, adj_idx;
-    build_adjacency(nV, nT, T, adj_ptr, adj_idx);
-    CoarsePlan P;
-    coarse_plan(nV, nT, T, epart, nParts, adj_ptr, adj_idx, P);
-    sizes[0] = (int32_t)P.pairS.size();
-    sizes[1] = (int32_t)P.pairBlk.size();
-    sizes[2] = (int32_t)P.vsIdx.size();
-    auto out = [](int32_t *dst, const std::vector<int> &src) {
-        if (dst) std::copy(src.begin(), src.end(), dst);
-    };
-    out(pairS, P.pairS);
-    out(pairT, P.pairT);
-    out(pairPtr, P.pairPtr);
-    out(pairBlk, P.pairBlk);
-    out(vsPtr, P.vsPtr);
-    out(vsIdx, P.vsIdx);
-    out(svPtr, P.svPtr);
-    out(svIdx, P.svIdx);
-    return 0;
-}
-
 }  // extern "C"

@@ -112,36 +112,6 @@ int ic_apply(dotmi_handle *h, const double *q, double *z, const LbfgsArgs &L)
 
 extern "C" {
 
-// host-only: the multicolour ordering and the lists of the block IC(0).  sizes[3] = {colours, lower blocks, products} always; the
-// arrays (any may be NULL) as in ic_plan.hpp
-int dotmi_plan_ic(int32_t nV, int32_t nT, const int32_t *T, int32_t *sizes, int32_t *colour, int32_t *pos, int32_t *lptr,
-                  int32_t *lidx, int32_t *lsrc, int32_t *dsrc, int32_t *pptr, int32_t *pa, int32_t *pb)
-{
-    if (nV < 1 || nT < 1 || !T || !sizes) return DOTMI_E_INVALID;
-    for (int e = 0; e < 4 * nT; ++e)
-        if (T[e] < 0 || T[e] >= nV) return DOTMI_E_INVALID;
-    std::vector<int> adj_ptr, adj_idx;
-    build_adjacency(nV, nT, T, adj_ptr, adj_idx);
-    IcPlan P;
-    ic_plan(nV, adj_ptr, adj_idx, P);
-    sizes[0] = P.nColours;
-    sizes[1] = (int32_t)P.lidx.size();
-    sizes[2] = (int32_t)P.pa.size();
-    auto out = [](int32_t *dst, const std::vector<int> &src) {
-        if (dst) std::copy(src.begin(), src.end(), dst);
-    };
-    out(colour, P.colour);
-    out(pos, P.pos);
-    out(lptr, P.lptr);
-    out(lidx, P.lidx);
-    out(lsrc, P.lsrc);
-    out(dsrc, P.dsrc);
-    out(pptr, P.pptr);
-    out(pa, P.pa);
-    out(pb, P.pb);
-    return 0;
-}
-
 int dotmi_ic_info(dotmi_handle *h, int32_t *colours, double *shift, int32_t *attempts)
 {
     if (!h) return DOTMI_E_INVALID;
