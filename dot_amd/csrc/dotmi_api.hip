@@ -208,6 +208,7 @@ int dotmi_apply_precond(dotmi_handle *h, const double *r, double *p)
     if (!h || !r || !p) return DOTMI_E_INVALID;
     HIPCHECK(h, hipSetDevice(h->device));
     if (int rc = enter_with_factors(h)) return rc;
+    if (int rc = dot_coarse_refresh(h)) return rc;   // (dotmi_set_dot_coarse: nothing unless the mode is on and A0 is stale)
     if (int rc = upload_tmp(h, r, h->q)) return rc;
     LbfgsArgs L;
     memset(&L, 0, sizeof(L));
@@ -243,6 +244,7 @@ int dotmi_probe_direction(dotmi_handle *h, const double *x, int32_t m, const dou
     }
     HIPCHECK(h, hipSetDevice(h->device));
     if (int rc = enter_with_factors(h)) return rc;
+    if (int rc = dot_coarse_refresh(h)) return rc;
     const int n = h->n;
     const size_t bytes = sizeof(double) * n;
     // the probe works on tmpn (iterate), g_trial (gradient), x_trial (trial point): the handle's own x, g stay

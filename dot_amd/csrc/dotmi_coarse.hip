@@ -7,6 +7,10 @@
 // dense block (as LBFGS-PD factors its Laplacian); the host reads back the pivot flag and nothing else.  A factorisation that meets a
 // non-positive pivot (rank-deficient Z) switches the term off until the next successful build -- the solves run on M_sym alone and
 // the handle is not poisoned.  The reference has no counterpart.
+// dotmi_set_dot_coarse puts the same term into DOT's own preconditioner, M' = M + Z A0^-1 Z^T with M = D^-1 sum_s R_s^T H_s^-1 R_s: the
+// same lists, Z, A0 and factor (one build serves both modes).  There the build is enqueued behind every refresh of H, at the positions
+// the refresh was made at, and its pivot flag is read after the synchronisation the refresh ends in anyway -- no read-back of its own
+// in a step.  The restriction reads the padded right-hand sides (coarse_restrict_pad_kernel), the prolongation is part of the merges.
 #include "coarse_plan.hpp"
 #include "dotmi_handle.hpp"
 
@@ -28,6 +32,23 @@ static int coarse_setup(dotmi_handle *h)
             h->err = "dotmi_set_pcg_coarse: the coarse plan's subdomains differ from the handle's";
             return DOTMI_E_INVALID;
         }
+    // the padded restriction (dotmi_set_dot_coarse) finds a subdomain's vertices in its padded range: every vertex of every subdomain has
+    // its three consecutive positions there (place_rows), the same subdomains in the same order (one rank: all of them are owned)
+    if (h->P.nParts != nP || (int)h->partPos.size() != nP) {
+        h->err = "dotmi_set_pcg_coarse / dotmi_set_dot_coarse: the handle does not own every subdomain";
+        return DOTMI_E_INVALID;
+    }
+    for (int s = 0; s < nP; ++s) {
+        bool ok = h->partPos[s].size() == h->partVerts[s].size();
+        for (size_t i = 0; ok && i < h->partPos[s].size(); ++i) ok = h->partPos[s][i] >= 0 && h->partPos[s][i] + 3 <= h->P.nmax;
+        if (!ok) {
+            h->err = "dotmi_set_dot_coarse: a vertex of subdomain " + std::to_string(s) + " has no place in the padded right-hand sides";
+            return DOTMI_E_INVALID;
+        }
+    }
+    D.nmax = h->P.nmax;
+    D.dofmap = h->P.dofmap;
+    if (int rc = dalloc(h, &D.rtab, (size_t)nP * D.nmax)) return rc;
     D.nParts = nP;
     D.nc = 6 * nP;
     D.ncp = (D.nc + TILE - 1) / TILE * TILE;
@@ -87,32 +108,38 @@ static int coarse_setup(dotmi_handle *h)
     if (h->tune.fuseLog)
         fprintf(stderr, "dotmi: PCG coarse space: %d subdomains, dimension %d (padded %d), %d coupled pairs with %d entries, %zu tile tasks "
                 "in %zu levels\n", nP, D.nc, D.ncp, D.nPairs, P.pairPtr.back(), S.tasks.size(), S.levelStart.size() - 1);
+    K.cm = CoarseMerge{D.vsPtr, D.vsIdx, D.wgt, D.xf, D.cen, D.y, D.nc, D.ncp};
     K.planned = true;
     return 0;
 }
 
-int coarse_refresh(dotmi_handle *h)
+int coarse_issue(dotmi_handle *h, const double *x)
 {
     dotmi_handle::Coarse &K = h->coarse;
-    if (K.mode == 0 || !K.stale) return 0;
     if (int rc = coarse_setup(h)) return rc;
     DevCoarse &D = K.D;
-    // weights and dropped subdomains from the handle's current fixed set (dotmi_refix changes it)
-    K.wgt.resize(h->nV);
-    K.live.assign(D.nParts, 0);
-    for (int v = 0; v < h->nV; ++v) K.wgt[v] = h->fixed[v] ? 0.0 : 1.0 / (double)std::max(h->dup[v], 1);
+    // weights and dropped subdomains from the handle's current fixed set (dotmi_refix changes it); uploaded when they change
+    std::vector<double> wgt(h->nV);
+    std::vector<int> live(D.nParts, 0);
+    for (int v = 0; v < h->nV; ++v) wgt[v] = h->fixed[v] ? 0.0 : 1.0 / (double)std::max(h->dup[v], 1);
     K.dropped = 0;
     for (int s = 0; s < D.nParts; ++s) {
         int nfree = 0;
         for (int v : h->partVerts[s]) nfree += h->fixed[v] ? 0 : 1;
-        K.live[s] = nfree >= 3;
+        live[s] = nfree >= 3;
         K.dropped += nfree < 3;
     }
-    HIPCHECK(h, hipMemcpyAsync(D.wgt, K.wgt.data(), sizeof(double) * h->nV, hipMemcpyHostToDevice, h->st));
-    HIPCHECK(h, hipMemcpyAsync(D.live, K.live.data(), sizeof(int) * D.nParts, hipMemcpyHostToDevice, h->st));
+    if (!K.uploaded || wgt != K.wgt || live != K.live) {
+        K.wgt.swap(wgt);
+        K.live.swap(live);
+        HIPCHECK(h, hipMemcpyAsync(D.wgt, K.wgt.data(), sizeof(double) * h->nV, hipMemcpyHostToDevice, h->st));
+        HIPCHECK(h, hipMemcpyAsync(D.live, K.live.data(), sizeof(int) * D.nParts, hipMemcpyHostToDevice, h->st));
+        K.uploaded = true;
+    }
     HIPCHECK(h, hipEventRecord(K.ev0, h->st));
-    HIPCHECK(h, hipMemcpyAsync(D.xf, h->x, sizeof(double) * h->n, hipMemcpyDeviceToDevice, h->st));   // frozen with this build
+    HIPCHECK(h, hipMemcpyAsync(D.xf, x, sizeof(double) * h->n, hipMemcpyDeviceToDevice, h->st));   // frozen with this build
     launch_coarse_centroid(D, h->st);
+    launch_coarse_rtab(D, h->st);
     launch_coarse_assemble(D, h->M, h->Hval, h->st);
     launch_coarse_fill(D, h->st);
     HIPCHECK(h, hipMemsetAsync(D.info, 0, sizeof(int), h->st));
@@ -120,18 +147,43 @@ int coarse_refresh(dotmi_handle *h)
         launch_tile_level(K.tasks + K.levelStart[l], K.levelStart[l + 1] - K.levelStart[l], K.prods, D.info, h->st, h->fastDiag);
     HIPCHECK(h, hipEventRecord(K.ev1, h->st));
     HIPCHECK(h, hipMemcpyAsync(K.h_info, D.info, sizeof(int), hipMemcpyDeviceToHost, h->st));
-    HIPCHECK(h, hipStreamSynchronize(h->st));
-    HIPCHECK(h, hipGetLastError());
+    K.pending = true;
+    return 0;
+}
+
+void coarse_finish(dotmi_handle *h)
+{
+    dotmi_handle::Coarse &K = h->coarse;
+    if (!K.pending) return;
+    K.pending = false;
     float ms = 0.f;
     hipEventElapsedTime(&ms, K.ev0, K.ev1);
     K.lastBuildMs = ms;
     K.stale = false;
     K.builds++;
-    K.active = K.h_info[0] == 0;   // a non-positive pivot: Z is rank deficient -- the solves go on with M_sym alone
+    K.active = K.h_info[0] == 0;   // a non-positive pivot: Z is rank deficient -- the applications go on without the coarse term
     if (h->tune.fuseLog)
-        fprintf(stderr, "dotmi: PCG coarse build %lld: %.3f ms, %d dropped, %s\n", K.builds, K.lastBuildMs, K.dropped,
+        fprintf(stderr, "dotmi: coarse build %lld: %.3f ms, %d dropped, %s\n", K.builds, K.lastBuildMs, K.dropped,
                 K.active ? "active" : "inactive (pivot)");
+}
+
+int coarse_refresh(dotmi_handle *h)
+{
+    dotmi_handle::Coarse &K = h->coarse;
+    if ((K.mode == 0 && K.dotMode == 0) || !K.stale) return 0;
+    if (int rc = coarse_issue(h, h->x)) return rc;
+    HIPCHECK(h, hipStreamSynchronize(h->st));
+    HIPCHECK(h, hipGetLastError());
+    coarse_finish(h);
     return 0;
+}
+
+void dot_coarse_restrict_solve(dotmi_handle *h, const DevLoop *ctl, int spec)
+{
+    const DevCoarse &D = h->coarse.D;
+    launch_coarse_restrict_pad(D, h->P.rpad, h->st, ctl, spec);
+    if (ctl) launch_coarse_solve_loop(D, h->st, ctl, spec);
+    else launch_coarse_solve(D, h->st);
 }
 
 void coarse_restrict_solve(dotmi_handle *h, const double *r)
@@ -164,8 +216,63 @@ int dotmi_set_pcg_coarse(dotmi_handle *h, int32_t mode)
                  "inverse factor); this handle has " + std::to_string(h->nPartsAll);
         return DOTMI_E_INVALID;
     }
-    if (mode == 1 && h->coarse.mode == 0) h->coarse.stale = true;   // (whatever happened to H while the mode was off)
+    if (mode == 1 && h->coarse.mode == 0 && h->coarse.dotMode == 0) h->coarse.stale = true;   // (whatever happened to H while the mode was off)
     h->coarse.mode = mode;
+    return 0;
+}
+
+int dotmi_set_dot_coarse(dotmi_handle *h, int32_t mode)
+{
+    if (!h) return DOTMI_E_INVALID;
+    const char *why = (h->world > 1 || h->dist) ? "single-rank handles only (the subdomains of this one are sharded)"
+                      : h->owner                ? "not with the owner exchange"
+                      : h->gsdd                 ? "a GSDD handle solves one subdomain at a time"
+                      : h->newtonPcg            ? "a Newton-PCG handle takes its coarse term through dotmi_set_pcg_coarse"
+                      : h->newton               ? "a Newton handle factorises H as one subdomain"
+                      : h->pd                   ? "an LBFGS-PD handle has no Hessian block solve"
+                      : h->hi                   ? "an LBFGS-HI handle has no Hessian block solve"
+                      : (h->flags & DOTMI_FLAG_ASYNC_REFRESH) ? "not with DOTMI_FLAG_ASYNC_REFRESH (the build is judged with the refresh)"
+                      : !h->vpart.empty() ? "the subdomains of this handle are vertex sets (vpart), the coarse plan works on an element partition"
+                                          : nullptr;
+    if (why) {
+        h->err = std::string("dotmi_set_dot_coarse: ") + why;
+        return DOTMI_E_INVALID;
+    }
+    if (mode != 0 && mode != 1) {
+        h->err = "dotmi_set_dot_coarse: mode must be 0 (off) or 1 (rigid modes)";
+        return DOTMI_E_INVALID;
+    }
+    if (mode == 1 && h->nPartsAll > COARSE_MAX_PARTS) {
+        h->err = "dotmi_set_dot_coarse: at most " + std::to_string(COARSE_MAX_PARTS) + " subdomains (the coarse matrix is applied through a dense "
+                 "inverse factor); this handle has " + std::to_string(h->nPartsAll);
+        return DOTMI_E_INVALID;
+    }
+    if (mode == h->coarse.dotMode) return 0;
+    h->coarse.dotMode = mode;
+    if (mode == 0) return 0;
+    // the refreshes of H that ran while the mode was off built nothing: build now, from the H and the positions of the last one
+    HIPCHECK(h, hipSetDevice(h->device));
+    if (int rc = enter_with_factors(h)) {
+        h->coarse.dotMode = 0;
+        return rc;
+    }
+    if (int rc = coarse_refresh(h)) {
+        h->coarse.dotMode = 0;
+        return rc;
+    }
+    return 0;
+}
+
+int dotmi_dot_coarse_info(const dotmi_handle *h, int32_t *dim, int32_t *dropped_subdomains, int32_t *active, int64_t *builds,
+                          double *last_build_ms)
+{
+    if (!h) return DOTMI_E_INVALID;
+    const dotmi_handle::Coarse &K = h->coarse;
+    if (dim) *dim = K.dotMode ? 6 * h->nPartsAll : 0;
+    if (dropped_subdomains) *dropped_subdomains = K.dotMode ? K.dropped : 0;
+    if (active) *active = dot_coarse(h) != nullptr;
+    if (builds) *builds = K.builds;
+    if (last_build_ms) *last_build_ms = K.lastBuildMs;
     return 0;
 }
 

@@ -128,6 +128,15 @@ static int slot_gradient(dotmi_handle *h, Slot &s)
     return 0;
 }
 
+// stage 3b (dotmi_set_dot_coarse with an active term), coarse: c = Z^T (-g_trial) from the padded right-hand sides the gradient stage has
+// just written, y = A0^-1 c.  Like the back-solve behind them the two kernels run whatever the controller will say about the trial --
+// in a retry slot too, whose trial may be the accepted one --, and return at once past the end of the loop.  They write c and the
+// parts of y only; a merge that is gated off never reads them, so held, stopped, paired and two-level slots need nothing else
+static void slot_coarse(dotmi_handle *h)
+{
+    if (dot_coarse(h)) dot_coarse_restrict_solve(h, h->ctl, 1);
+}
+
 // stage 4, back-solve on -g_trial with the controller as one workgroup of its launch
 static void slot_backsolve(dotmi_handle *h, const Slot &s)
 {
@@ -140,11 +149,13 @@ static void slot_backsolve(dotmi_handle *h, const Slot &s)
         (int)h->slotTimed.size() /* the slot's epoch, 1-based */);
 }
 
-// stage 5, merge: z = u - sum_j xi_j (M y_j) from the tile partials and the cached M y_j
+// stage 5, merge: z = u - sum_j xi_j (M y_j) from the tile partials and the cached M y_j (dotmi_set_dot_coarse: u with + Z y, so the
+// cached vectors are M' y_j)
 static int slot_merge(dotmi_handle *h)
 {
     if (!h->dist) {
-        launch_merge_early(h->M, h->P, h->z, h->partC, 0, h->st, h->ctl, nullptr, nullptr, VList(), nullptr, 0, nullptr, h->partCT);
+        launch_merge_early(h->M, h->P, h->z, h->partC, 0, h->st, h->ctl, nullptr, nullptr, VList(), nullptr, 0, nullptr, h->partCT,
+                           dot_coarse(h));
     } else if (!h->owner) {
         // sharded subdomains: this rank's part of the sum, the one collective of the iteration (issued in every slot,
         // whatever the controller decided: every rank enqueues the same sequence), then the division and the history terms
@@ -182,6 +193,7 @@ static int enqueue_loop_slot_early(dotmi_handle *h)
     if (int rc = slot_direction(h, s)) return rc;
     slot_trial(h, s);
     if (int rc = slot_gradient(h, s)) return rc;
+    slot_coarse(h);
     slot_backsolve(h, s);
     return slot_merge(h);
 }
@@ -196,11 +208,13 @@ static int enqueue_loop_slot(dotmi_handle *h)
     LbfgsArgs L0;
     memset(&L0, 0, sizeof(L0));
     launch_build_qpad(h->P, h->g, L0, nullptr, h->st, h->ctl);   // q, straight into the padded right-hand sides
+    const CoarseMerge *co = dot_coarse(h);
+    if (co) dot_coarse_restrict_solve(h, h->ctl, 0);             // dotmi_set_dot_coarse: y = A0^-1 Z^T q, gated like the back-solve
     const Bracket br = backsolve_bracket(h);
     h->slotTimed.push_back(br.at);
     launch_gemv(h->P, nullptr, h->st, h->ctl, br.ev0, br.ev1);
     if (!h->dist) {
-        launch_merge(h->M, h->P, L0, h->z, h->partC, 1 | 2, h->st, h->ctl);
+        launch_merge(h->M, h->P, L0, h->z, h->partC, 1 | 2, h->st, h->ctl, VList(), co);
     } else {
         // sharded subdomains: the one collective of an iteration, enqueued like a kernel.  It runs in every slot (also
         // in retries and past the end, where the kernels around it return at once), so every rank issues the same
@@ -257,8 +271,9 @@ static void choose_step_forms(dotmi_handle *h)
     // the unit step speculatively beside the direction kernel: one rank, the fused kernels, every patch a workgroup, no pairing
     // in this step (a step whose predecessor halved often); -1: only after a step whose first trials took the unit estimate at
     // least nine times in ten (a slot whose estimate is below 1 is redone: ~45 us lost against ~10 saved)
+    // (not on a handle with dotmi_set_dot_coarse on: the coarse stage has not been run under the speculative slots)
     h->specNow = h->earlyNow && !h->dist && !h->pairNow && h->tune.fuseStep && h->tune.fuseDir &&
-                 h->specFits &&
+                 h->specFits && h->coarse.dotMode == 0 &&
                  (h->tune.specStep > 0 || (h->tune.specStep < 0 && h->prevFirst > 0 && 10 * h->prevUnit >= 9 * h->prevFirst));
     // the trial's element pass + gather as one launch on vertex patches (paired steps too: elem_vertex_kernel<MAT, true>); a step that
     // speculates keeps the element patches (one patch set per step: the start-of-step evaluation and the trials group their
@@ -401,10 +416,12 @@ static int enqueue_step_start(dotmi_handle *h)
         return 0;
     }
     // the first direction's solve, u = -M g_0 and z = u, with the start-of-step controller inside its launch
+    if (dot_coarse(h)) dot_coarse_restrict_solve(h);   // (dotmi_set_dot_coarse: y = A0^-1 Z^T (-g_0) for the merge below)
     CtlArgs ca{h->ctl, h->partE, h->partR, h->alpha_dev, h->h_flags, nb, 1};
     (h->vpNow ? launch_gemv_vp : launch_gemv)(h->P, nullptr, h->st, h->ctl, nullptr, nullptr, &ca, 1 << 30);
     if (!h->dist) {
-        launch_merge_early(h->M, h->P, h->z, h->partC, 1, h->st, h->ctl, nullptr, nullptr, VList(), nullptr, 0, nullptr, h->partCT);
+        launch_merge_early(h->M, h->P, h->z, h->partC, 1, h->st, h->ctl, nullptr, nullptr, VList(), nullptr, 0, nullptr, h->partCT,
+                           dot_coarse(h));
     } else {
         launch_merge(h->M, h->P, L0, h->zstage, h->partC, 0, h->st, h->ctl);
         if (int rc = allreduce_sum(h, h->zstage, h->n)) return rc;

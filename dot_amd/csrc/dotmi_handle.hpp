@@ -8,7 +8,8 @@
 //   dotmi_reconfig.hip    tolerance, time step and materials changed on a live handle (dotmi_set_rel_tol / _time_step / _lame)
 //   dotmi_pd.hip / dotmi_ic.hip   the preconditioners of LBFGS-PD (scalar Laplacian) and LBFGS-HI (block incomplete Cholesky of H)
 //   dotmi_pcg.hip         Newton-PCG: conjugate gradients on the global H with the block solve (dotmi_solve_hessian, DOTMI_FLAG_NEWTON_PCG)
-//   dotmi_coarse.hip      the rigid-mode coarse space of that PCG's preconditioner (dotmi_set_pcg_coarse; lists: coarse_plan.hpp)
+//   dotmi_coarse.hip      the rigid-mode coarse space of that PCG's preconditioner (dotmi_set_pcg_coarse; lists: coarse_plan.hpp) and of
+//                         DOT's own block preconditioner (dotmi_set_dot_coarse)
 //   dotmi_api.hip         the remaining ABI entry points (state, kernel-level calls, probes, measurement, handle queries)
 //
 // Control flow mirrors (paths relative to /root/reference/src)
@@ -249,8 +250,15 @@ struct dotmi_handle {
     double pcgLastRes = 0.0;
     // dotmi_set_pcg_coarse: the rigid-mode coarse term of the PCG's preconditioner (dotmi_coarse.hip).  Nothing of it exists until the
     // mode is switched on; every refresh of H marks the coarse matrix stale and the next solve with the mode on rebuilds it
+    // dotmi_set_dot_coarse: the same term in DOT's own loop, M' = M + Z A0^-1 Z^T -- one build serves both modes.  With dotMode on the
+    // build is enqueued behind every refresh of H (refactor_issue) and judged with it (refactor_finish): the pivot flag comes back
+    // with the stream synchronisation the refresh takes anyway
     struct Coarse {
-        int mode = 0;                 // 0 off, 1 rigid modes
+        int mode = 0;                 // dotmi_set_pcg_coarse: 0 off, 1 rigid modes
+        int dotMode = 0;              // dotmi_set_dot_coarse: 0 off, 1 rigid modes
+        bool pending = false;         // a build is enqueued, its pivot flag not yet read (coarse_issue -> coarse_finish)
+        bool uploaded = false;        // the device's weights and live flags are those of wgt / live below
+        CoarseMerge cm{};             // the merge kernels' view of the last build (launch_merge / launch_merge_early)
         bool planned = false;         // lists, buffers and the tile schedule exist
         bool stale = true;            // H has been refreshed since the last build
         bool active = false;          // the last build's factorisation succeeded: the solves add the coarse term
@@ -380,7 +388,19 @@ int pcg_build_scaling(dotmi_handle *h);
 int pcg_solve(dotmi_handle *h, const double *b, double rel_tol, int max_iter, int check_every, int *iters, double *rel_res);
 const char *pcg_refusal(const dotmi_handle *h);   // why this handle has no global solve (nullptr: it has)
 // dotmi_coarse.hip (the coarse term of the PCG's preconditioner)
-int coarse_refresh(dotmi_handle *h);              // mode on and stale: rebuild A0 and its inverse factor from the current H and x
+int coarse_refresh(dotmi_handle *h);              // a mode on and stale: rebuild A0 and its inverse factor from the current H and x
+int coarse_issue(dotmi_handle *h, const double *x);   // enqueue that build at the positions x (no synchronisation) ...
+void coarse_finish(dotmi_handle *h);                  // ... and, after one, take its pivot flag and its time
+// dotmi_set_dot_coarse: what the merges of a preconditioner application add (nullptr: mode off, or the last build met a bad pivot)
+inline const CoarseMerge *dot_coarse(const dotmi_handle *h)
+{
+    const dotmi_handle::Coarse &K = h->coarse;
+    return (K.dotMode != 0 && K.active && !K.stale) ? &K.cm : nullptr;
+}
+// the build that a refresh with the mode off has left undone (dotmi_set_dot_coarse only: the PCG builds in its solves)
+inline int dot_coarse_refresh(dotmi_handle *h) { return h->coarse.dotMode != 0 ? coarse_refresh(h) : 0; }
+// c = Z^T r from the padded right-hand sides, y = A0^-1 c (ctl: as kernels of the device-resident loop; spec: the early order)
+void dot_coarse_restrict_solve(dotmi_handle *h, const DevLoop *ctl = nullptr, int spec = 0);
 void coarse_restrict_solve(dotmi_handle *h, const double *r);   // c = Z^T r, y = A0^-1 c
 void coarse_prolong(dotmi_handle *h, double *zsum);             // zsum += (Z y) / isd
 // dotmi_collectives.hip

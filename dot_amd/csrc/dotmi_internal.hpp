@@ -221,6 +221,7 @@ struct DevIC {
 
 constexpr int MT_PAD = -2147483647 - 1;   // end of a dof's interleaved list (no offset, plain or complemented, has this value)
 
+struct CoarseMerge;   // (below, with DevCoarse)
 struct LbfgsArgs {
     int m;
     const double *s[HIST_MAX];  // chronological, oldest first
@@ -464,7 +465,8 @@ void launch_twolevel_pack(const DevParts &P, hipStream_t st);   // after a facto
 // sums, partials = nullptr)
 void launch_merge_early(const DevMesh &M, const DevParts &P, double *z, double *partials, int first, hipStream_t st,
                         const DevLoop *ctl, const double *zsum = nullptr, const uint8_t *ownMask = nullptr, VList vl = VList(),
-                        const uint8_t *kind = nullptr, int pre = 0, double *zshare = nullptr, double *partialsT = nullptr);
+                        const uint8_t *kind = nullptr, int pre = 0, double *zshare = nullptr, double *partialsT = nullptr,
+                        const CoarseMerge *co = nullptr);   // co (dotmi_set_dot_coarse): u += Z y behind the division, the COARSE instantiation
 // owner exchange: the entries of the vertices held by more than one rank, packed / unpacked (idx: their vertex ids);
 // tail: `ntail` further scalars copied from / to tailp behind the packed entries
 // red0 / red1: partial arrays whose rows workgroup 0 of the pack sums into the packet's tail (pack[dst ...]): `cols` columns of
@@ -487,9 +489,9 @@ void launch_mask_owned(int n, double *v, const uint8_t *ownMask, hipStream_t st)
 // tiles are job[0..njobs); then p = 0 except p[dofs of part ls] = psub_s  (ADMMDDTimeStepper::fill, :1646-1665)
 void launch_gemv_part(const DevParts &P, int ls, const int4 *job, int njobs, const int2 *lwork, int nlwork, const double *q,
                       int n, double *p, hipStream_t st);
-// z = merge(psub) / dup  (+ partial dots y_i . z)
+// z = merge(psub) / dup  (+ partial dots y_i . z);  co (dotmi_set_dot_coarse): z += Z y behind the division, the COARSE instantiations
 void launch_merge(const DevMesh &M, const DevParts &P, const LbfgsArgs &L, double *z, double *partials,
-                  int with_dots, hipStream_t st, const DevLoop *ctl = nullptr, VList vl = VList());
+                  int with_dots, hipStream_t st, const DevLoop *ctl = nullptr, VList vl = VList(), const CoarseMerge *co = nullptr);
 // partial dots y_i . z only (multi-GPU path after all-reduce)
 // p = z + sum_j delta_j s_j, delta from c partials, xi and SY
 void launch_build_p(int n, const double *z, const LbfgsArgs &L, const double *c_partials,
@@ -589,6 +591,7 @@ void launch_pcg_update(const DevPcg &C, int n, double *u, double *q, int it, dou
 // ---- the rigid-mode coarse space of Newton-PCG's preconditioner (dotmi_set_pcg_coarse; dotmi_coarse.hip / k_coarse.hip; lists:
 // coarse_plan.hpp): M = M_sym + Z A0^-1 Z^T, A0 = Z^T H Z, six columns of Z per subdomain -------------------------------------------
 constexpr int COARSE_MAX_PARTS = 256;   // A0^-1 is kept as a dense inverse factor: nc = 6 nParts <= 1536 (a storage choice)
+constexpr int COARSE_NC_MAX = 6 * COARSE_MAX_PARTS;
 struct DevCoarse {
     int nParts = 0, nc = 0, ncp = 0, nPairs = 0;   // subdomains; 6 nParts; nc padded to a multiple of 64; coupled pairs (s <= t)
     int *vsPtr = nullptr, *vsIdx = nullptr;        // per vertex: its subdomains, ascending
@@ -604,6 +607,16 @@ struct DevCoarse {
     double *c = nullptr, *y = nullptr;             // the running application: Z^T r (ncp) and A0^-1 Z^T r as the parts of the ncp / 64 row
                                                    // blocks of X ((ncp / 64) x ncp; the prolongation adds them)
     int *info = nullptr;                           // the factorisation's pivot report
+    // dotmi_set_dot_coarse: the restriction from the padded right-hand sides (DevParts::rpad / dofmap / nmax of the same handle)
+    int nmax = 0;
+    const int *dofmap = nullptr;
+    double4 *rtab = nullptr;                       // nParts * nmax: (w_v, k_0, k_1, k_2) per padded position (coarse_rtab_kernel)
+};
+// what a merge kernel's COARSE instantiation needs for the prolongation  u_v += w_v sum_{s holds v} (t_s + omega_s x (x_v - c_s))
+struct CoarseMerge {
+    const int *vsPtr, *vsIdx;
+    const double *wgt, *xf, *cen, *ypart;
+    int nc, ld;
 };
 void launch_coarse_centroid(const DevCoarse &C, hipStream_t st);
 void launch_coarse_assemble(const DevCoarse &C, const DevMesh &M, const double *Hval, hipStream_t st);
@@ -612,6 +625,11 @@ void launch_coarse_restrict(const DevCoarse &C, const double *r, hipStream_t st)
 void launch_coarse_solve(const DevCoarse &C, hipStream_t st);                                           // y = X^T (X c)
 void launch_coarse_prolong(const DevCoarse &C, int nV, const double *isd, double *zsum, hipStream_t st);   // zsum += (Z y) / isd
 void launch_coarse_scale(int n, const double *a, const double *isd, double *out, hipStream_t st);       // out = a (.) isd per vertex
+// dotmi_set_dot_coarse: the table of the padded restriction (once per build); c = Z^T r from the padded right-hand sides and the
+// solve as kernels of the loop (ctl != nullptr: gated by its status, and by its retry phase unless spec)
+void launch_coarse_rtab(const DevCoarse &C, hipStream_t st);
+void launch_coarse_restrict_pad(const DevCoarse &C, const double *rpad, hipStream_t st, const DevLoop *ctl = nullptr, int spec = 0);
+void launch_coarse_solve_loop(const DevCoarse &C, hipStream_t st, const DevLoop *ctl, int spec);
 // host: the dense nc x nc matrix from the pairs' blocks, entry by entry as the fill kernel writes it
 void coarse_dense_host(int nc, int nParts, const int *pairAt, const int *live, const double *pairA, double *A0);
 

@@ -76,12 +76,16 @@ void two_loop_xi(int m, const double *b, const double (*sy)[HIST_MAX], const dou
 }
 
 // p = D^-1 sum_s R_s^T W_s R_s q   (DOTTimeStepper.cpp:406-450); leaves y_i.z partials in partC
+// dotmi_set_dot_coarse with an active term: + Z A0^-1 Z^T q -- the restriction from the padded right-hand sides (where launch_gemv has
+// put q, or build_qpad before it) and the coarse solve behind the back-solve, the prolongation inside the merge
 int apply_precond(dotmi_handle *h, const double *q, double *z, const LbfgsArgs &L)
 {
     const Bracket br = backsolve_bracket(h);
     launch_gemv(h->P, q, h->st, nullptr, br.ev0, br.ev1);
     if (!h->dist) {
-        launch_merge(h->M, h->P, L, z, h->partC, 1 | 2, h->st);
+        const CoarseMerge *co = dot_coarse(h);
+        if (co) dot_coarse_restrict_solve(h);
+        launch_merge(h->M, h->P, L, z, h->partC, 1 | 2, h->st, nullptr, VList(), co);
     } else {
         launch_merge(h->M, h->P, L, z, h->partC, 0, h->st);
         if (int rc = allreduce_sum(h, z, h->n)) return rc;
@@ -440,6 +444,7 @@ int dotmi_step(dotmi_handle *h, dotmi_step_stats *st)
     // a refresh still running from the last step is judged BEFORE anything of this step is enqueued: a step never runs on
     // factors whose factorisation failed (what the caller did between the two steps has already overlapped the refresh)
     if (int rc = enter_with_factors(h)) return rc;
+    if (int rc = dot_coarse_refresh(h)) return rc;   // (nothing in a step that follows a refresh: dotmi_set_dot_coarse builds behind it)
     const double T0 = now_ms();
     h->m = 0;
     h->energy_evals = 0;

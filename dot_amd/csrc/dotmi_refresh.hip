@@ -101,7 +101,7 @@ int run_factor(dotmi_handle *h)
 
 int refactor_issue(dotmi_handle *h, const double *x)
 {
-    h->coarse.stale = true;   // (dotmi_set_pcg_coarse: the next solve with the mode on rebuilds A0 = Z^T H Z)
+    h->coarse.stale = true;   // (dotmi_set_pcg_coarse: the next solve with the mode on rebuilds A0 = Z^T H Z; dotmi_set_dot_coarse: below)
     HIPCHECK(h, hipEventRecord(h->ev0, h->st));
     if (h->shardHess) {
         launch_elem_hessians(h->M, h->mat, h->dtSq, x, h->He, h->st, h->hessElems, h->nHessElems);
@@ -139,12 +139,17 @@ int refactor_issue(dotmi_handle *h, const double *x)
         HIPCHECK(h, hipMemcpyAsync(h->h_info, h->info_dev, sizeof(int) * h->P.nParts, hipMemcpyDeviceToHost, h->st));
     }
     HIPCHECK(h, hipEventRecord(h->ev2, h->st));
+    // dotmi_set_dot_coarse: A0 = Z^T H Z of this H at these positions and its factor, behind the subdomains' (outside ms_factor's
+    // bracket; dotmi_dot_coarse_info has its time); refactor_finish reads its pivot flag after the same synchronisation
+    if (h->coarse.dotMode != 0)
+        if (int rc = coarse_issue(h, x)) return rc;
     return 0;
 }
 
 // after the stream has been synchronised: SPD check of every owned subdomain and the two timings
 int refactor_finish(dotmi_handle *h, double *ms_hess, double *ms_fact)
 {
+    coarse_finish(h);   // (a coarse build enqueued behind this refresh: judged whatever the subdomains' verdict is)
     int bad = -1;
 #ifdef DOTMI_TEST_HOOKS
     if (h->testFailRefresh > 0 && ++h->testRefreshCount == h->testFailRefresh && h->P.nParts > 0) h->h_info[0] = 7;

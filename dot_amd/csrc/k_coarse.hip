@@ -9,6 +9,9 @@
 //   per CG iteration:   coarse_restrict_kernel (c = Z^T r, one workgroup per subdomain), coarse_solve_kernel (y = X^T (X c), one
 //                       workgroup per 64 rows of X), coarse_prolong_kernel (zsum += (Z y) / isd, a gather per vertex over its
 //                       subdomains ascending)
+//   DOT's own loop (dotmi_set_dot_coarse): the same Z, A0 and coarse_solve_kernel in M' = M + Z A0^-1 Z^T; the restriction reads the
+//                       subdomains' padded right-hand sides through a table per padded position (coarse_rtab_kernel at the build,
+//                       coarse_restrict_pad_kernel per application), the prolongation is inside the merge kernels (k_loopvec.hip, COARSE)
 // Every sum has a fixed shape -- a thread's entries in list order, the lanes by wave_sum's tree, the four waves pairwise -- and
 // nothing is added atomically: two builds and two applications are bit-identical.  The reference has no counterpart.
 #include "k_device.hpp"
@@ -170,11 +173,9 @@ __global__ __launch_bounds__(256) void coarse_restrict_kernel(const int *__restr
 // convention of every reduction here.  (A first form did both phases in ONE workgroup: 34 us at nc = 192, 81 us at nc = 384,
 // more than the block solve itself -- profiles/newton_pcg_coarse.txt.)  The strictly upper part of a diagonal tile holds zeros
 // (tile_task_body stores them), the padding rows are the identity on zeros of c.
-constexpr int COARSE_NC_MAX = 6 * COARSE_MAX_PARTS;
-__global__ __launch_bounds__(256) void coarse_solve_kernel(int nc, int ld, const double *__restrict__ X, const double *__restrict__ c,
-                                                           double *__restrict__ ypart)
+__device__ __forceinline__ void coarse_solve_body(int nc, int ld, const double *__restrict__ X, const double *__restrict__ c,
+                                                  double *__restrict__ ypart, double *sc, double *tv)
 {
-    __shared__ double sc[COARSE_NC_MAX], tv[64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = blockIdx.x, r0 = 64 * g, ncol = min(64 * (g + 1), nc);
     for (int k = tid; k < ncol; k += 256) sc[k] = c[k];
@@ -201,6 +202,84 @@ __global__ __launch_bounds__(256) void coarse_solve_kernel(int nc, int ld, const
         for (int r = 0; r < 64; ++r) a += col[(size_t)r * ld] * tv[r];
         ypart[(size_t)g * ld + k] = a;
     }
+}
+__global__ __launch_bounds__(256) void coarse_solve_kernel(int nc, int ld, const double *__restrict__ X, const double *__restrict__ c,
+                                                           double *__restrict__ ypart)
+{
+    __shared__ double sc[COARSE_NC_MAX], tv[64];
+    coarse_solve_body(nc, ld, X, c, ypart, sc, tv);
+}
+// the same solve as a kernel of the device-resident loop (dotmi_set_dot_coarse): gated like the back-solve it stands in front of --
+// past the end of the loop it returns at once, and in the q-based order (spec == 0) in a line-search retry too; in the early order a
+// retry slot solves for its trial's gradient like the back-solve does
+__global__ __launch_bounds__(256) void coarse_solve_loop_kernel(int nc, int ld, const double *__restrict__ X, const double *__restrict__ c,
+                                                                double *__restrict__ ypart, const DevLoop *__restrict__ ctl, int spec)
+{
+    __shared__ double sc[COARSE_NC_MAX], tv[64];
+    if (ctl->status != 0 || (ctl->phase != 0 && !spec)) return;
+    coarse_solve_body(nc, ld, X, c, ypart, sc, tv);
+}
+
+// The restriction of DOT's loop reads the right-hand sides where the back-solve reads them: DevParts::rpad, subdomain s in the padded
+// positions [s nmax, (s + 1) nmax), every vertex of s in three consecutive ones (block_plan.hpp: place_rows).  Per padded position the
+// table holds what its scalar r_a (component a of vertex v) contributes to c_s = Z_s^T r:  w_v r_a to translation a and
+// w_v ((x_v - c_s) x r)_b = w_v (k_b r_a) to the rotations, k = (0, d2, -d1), (-d2, 0, d0), (d1, -d0, 0) for a = 0, 1, 2 and
+// d = x_v - c_s.  An entry is (w_v, k_0, k_1, k_2); all zero on the padding, on fixed vertices and in a dropped subdomain.  Written
+// once per build, behind the centroids
+__global__ __launch_bounds__(256) void coarse_rtab_kernel(int total, int nmax, const int *__restrict__ dofmap,
+                                                          const double *__restrict__ wgt, const double *__restrict__ x,
+                                                          const double *__restrict__ cen, const int *__restrict__ live,
+                                                          double4 *__restrict__ rtab)
+{
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= total) return;
+    const int dof = dofmap[k], s = k / nmax;
+    double4 t = make_double4(0.0, 0.0, 0.0, 0.0);
+    if (dof >= 0 && live[s]) {
+        const int v = dof / 3, a = dof - 3 * v;
+        const double w = wgt[v];
+        if (w != 0.0) {
+            const double d0 = x[3 * v] - cen[3 * s], d1 = x[3 * v + 1] - cen[3 * s + 1], d2 = x[3 * v + 2] - cen[3 * s + 2];
+            t.x = w;
+            t.y = a == 0 ? 0.0 : (a == 1 ? -d2 : d1);
+            t.z = a == 0 ? d2 : (a == 1 ? 0.0 : -d0);
+            t.w = a == 0 ? -d1 : (a == 1 ? d0 : 0.0);
+        }
+    }
+    rtab[k] = t;
+}
+
+// c_s = Z_s^T r from the padded right-hand sides: one workgroup per subdomain over its own contiguous range, the table, the
+// right-hand side and the position's component (dofmap) side by side.  DEV: a kernel of the device-resident loop, gated like
+// coarse_solve_loop_kernel
+template <bool DEV>
+__global__ __launch_bounds__(256) void coarse_restrict_pad_kernel(int nmax, const int *__restrict__ dofmap,
+                                                                  const double4 *__restrict__ rtab, const double *__restrict__ rpad,
+                                                                  double *__restrict__ c, const DevLoop *__restrict__ ctl, int spec)
+{
+    __shared__ double sm[5 * 6];
+    if constexpr (DEV) {
+        if (ctl->status != 0 || (ctl->phase != 0 && !spec)) return;
+    }
+    const int s = blockIdx.x;
+    const size_t base = (size_t)s * nmax;
+    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int k = threadIdx.x; k < nmax; k += 256) {
+        const double4 t = rtab[base + k];
+        const double r = rpad[base + k];
+        const int dof = dofmap[base + k];
+        if (t.x == 0.0) continue;
+        const int a = dof % 3;
+        const double wr = t.x * r;
+        acc[0] += a == 0 ? wr : 0.0;
+        acc[1] += a == 1 ? wr : 0.0;
+        acc[2] += a == 2 ? wr : 0.0;
+        acc[3] += t.x * (t.y * r);
+        acc[4] += t.x * (t.z * r);
+        acc[5] += t.x * (t.w * r);
+    }
+    coarse_block_sum<6>(acc, sm);
+    if (threadIdx.x < 6) c[6 * s + threadIdx.x] = sm[4 * 6 + threadIdx.x];
 }
 
 // zsum_v += (Z y)_v / isd_v with (Z y)_v = w_v sum over the subdomains s of v, ascending, of t_s + omega_s x (x_v - c_s): behind the
@@ -278,6 +357,26 @@ void launch_coarse_prolong(const DevCoarse &C, int nV, const double *isd, double
 {
     hipLaunchKernelGGL(coarse_prolong_kernel, dim3((nV + 255) / 256), dim3(256), 0, st, nV, C.nc, C.ncp, (const int *)C.vsPtr,
                        (const int *)C.vsIdx, (const double *)C.wgt, (const double *)C.xf, (const double *)C.cen, (const double *)C.y, isd, zsum);
+}
+void launch_coarse_rtab(const DevCoarse &C, hipStream_t st)
+{
+    const int total = C.nParts * C.nmax;
+    hipLaunchKernelGGL(coarse_rtab_kernel, dim3((total + 255) / 256), dim3(256), 0, st, total, C.nmax, C.dofmap, (const double *)C.wgt,
+                       (const double *)C.xf, (const double *)C.cen, (const int *)C.live, C.rtab);
+}
+void launch_coarse_restrict_pad(const DevCoarse &C, const double *rpad, hipStream_t st, const DevLoop *ctl, int spec)
+{
+    if (ctl)
+        hipLaunchKernelGGL(coarse_restrict_pad_kernel<true>, dim3(C.nParts), dim3(256), 0, st, C.nmax, C.dofmap, (const double4 *)C.rtab, rpad,
+                           C.c, ctl, spec);
+    else
+        hipLaunchKernelGGL(coarse_restrict_pad_kernel<false>, dim3(C.nParts), dim3(256), 0, st, C.nmax, C.dofmap, (const double4 *)C.rtab, rpad,
+                           C.c, ctl, spec);
+}
+void launch_coarse_solve_loop(const DevCoarse &C, hipStream_t st, const DevLoop *ctl, int spec)
+{
+    hipLaunchKernelGGL(coarse_solve_loop_kernel, dim3((C.nc + 63) / 64), dim3(256), 0, st, C.nc, C.ncp, (const double *)C.W,
+                       (const double *)C.c, C.y, ctl, spec);
 }
 void launch_coarse_scale(int n, const double *a, const double *isd, double *out, hipStream_t st)
 {

@@ -491,19 +491,60 @@ void launch_multidot(int n, const double *v, const double *const *vecs, int m, d
     hipLaunchKernelGGL(multidot_kernel, dim3(NB_RED), dim3(256), 0, st, n, v, W, m, partials);
 }
 
+// ---- the prolongation of DOT's rigid-mode coarse term inside the merges (dotmi_set_dot_coarse; k_coarse.hip) ----
+// The COARSE instantiations of the three merge kernels add  (Z y)_v = w_v sum over the subdomains s of v, ascending, of
+// t_s + omega_s x (x_v - c_s)  behind the division by the multiplicity: M' r = M r + Z A0^-1 Z^T r.  The last kernel parameter is
+// MergeCoarse<COARSE>: empty without the term, so the plain instantiations keep their arguments and their code.
+template <bool COARSE>
+struct MergeCoarse {};
+template <>
+struct MergeCoarse<true> : CoarseMerge {};
+// y = A0^-1 Z^T r from the row blocks' parts in ascending block order (coarse_prolong_kernel's prologue) into LDS, by every workgroup
+__device__ __forceinline__ void coarse_load_y(const CoarseMerge &co, double *y)
+{
+    const int G = (co.nc + 63) / 64;
+    for (int k = threadIdx.x; k < co.nc; k += blockDim.x) {
+        double a = 0.0;
+        for (int g = k >> 6; g < G; ++g) a += co.ypart[(size_t)g * co.ld + k];
+        y[k] = a;
+    }
+    __syncthreads();
+}
+// component dd of (Z y)_v: coarse_prolong_kernel's expression in its order
+__device__ __forceinline__ double coarse_term(const CoarseMerge &co, const double *y, int v, int dd)
+{
+    const double w = co.wgt[v];
+    if (w == 0.0) return 0.0;
+    const double x0 = co.xf[3 * v], x1 = co.xf[3 * v + 1], x2 = co.xf[3 * v + 2];
+    double a = 0.0;
+    for (int k = co.vsPtr[v]; k < co.vsPtr[v + 1]; ++k) {
+        const int s = co.vsIdx[k];
+        const double *ys = y + 6 * s;
+        const double d0 = x0 - co.cen[3 * s], d1 = x1 - co.cen[3 * s + 1], d2 = x2 - co.cen[3 * s + 2];
+        a += dd == 0 ? ys[0] + (ys[4] * d2 - ys[5] * d1) : dd == 1 ? ys[1] + (ys[5] * d0 - ys[3] * d2) : ys[2] + (ys[3] * d1 - ys[4] * d0);
+    }
+    return w * a;
+}
+
 // z_v = (sum over parts containing v of p_s[local v]) / dup_v ; partial dots c_i = y_i . z
-template <bool DEV>
+template <bool DEV, bool COARSE = false>
 __global__ __launch_bounds__(256) void merge_kernel(int nV, const int *__restrict__ vp_ptr,
                                                     const int *__restrict__ vp_off,
                                                     const int *__restrict__ dup,
                                                     const double *__restrict__ psub, LbfgsArgs L,
                                                     int with_dots, int divide, double *__restrict__ z,
                                                     double *__restrict__ partials,
-                                                    const DevLoop *__restrict__ ctl, VList vl)
+                                                    const DevLoop *__restrict__ ctl, VList vl, MergeCoarse<COARSE> co)
 {
     __shared__ double sm[4 * RED_K];
     if constexpr (DEV) {
         if (ctl->status != 0 || ctl->phase != 0) return;
+    }
+    double *ysh = nullptr;
+    if constexpr (COARSE) {
+        __shared__ double ybuf[COARSE_NC_MAX];
+        ysh = ybuf;
+        coarse_load_y(co, ysh);
     }
     const LbfgsArgs &Lr = [&]() -> const LbfgsArgs & {
         if constexpr (DEV) return ctl->L;
@@ -558,6 +599,11 @@ __global__ __launch_bounds__(256) void merge_kernel(int nV, const int *__restric
             z1 /= d;
             z2 /= d;
         }
+        if constexpr (COARSE) {
+            z0 += coarse_term(co, ysh, v, 0);
+            z1 += coarse_term(co, ysh, v, 1);
+            z2 += coarse_term(co, ysh, v, 2);
+        }
         z[3 * v] = z0;
         z[3 * v + 1] = z1;
         z[3 * v + 2] = z2;
@@ -606,17 +652,24 @@ __device__ __forceinline__ double merge_walk_interleaved(int k, const int2 *__re
     }
     return u + ps;
 }
-template <bool DEV>
+template <bool DEV, bool COARSE = false>
 __global__ __launch_bounds__(256) void merge_tiles_kernel(int n3, const int *__restrict__ mt_ptr,
                                                           const int *__restrict__ mt_ent, const int *__restrict__ dup,
                                                           const double *__restrict__ ppart, LbfgsArgs L, int with_dots,
                                                           int divide, double *__restrict__ z,
                                                           double *__restrict__ partials, const DevLoop *__restrict__ ctl, VList vl,
-                                                          const int2 *__restrict__ mt_wave, const int *__restrict__ mt_il)
+                                                          const int2 *__restrict__ mt_wave, const int *__restrict__ mt_il,
+                                                          MergeCoarse<COARSE> co)
 {
     __shared__ double sm[4 * RED_K];
     if constexpr (DEV) {
         if (ctl->status != 0 || ctl->phase != 0) return;
+    }
+    double *ysh = nullptr;
+    if constexpr (COARSE) {
+        __shared__ double ybuf[COARSE_NC_MAX];
+        ysh = ybuf;
+        coarse_load_y(co, ysh);
     }
     const bool il = mt_il != nullptr && vl.v == nullptr;
     const LbfgsArgs &Lr = [&]() -> const LbfgsArgs & {
@@ -663,6 +716,7 @@ __global__ __launch_bounds__(256) void merge_tiles_kernel(int n3, const int *__r
         }
         zk += ps;
         if (d > 1) zk /= d;
+        if constexpr (COARSE) zk += coarse_term(co, ysh, k / 3, k % 3);
         z[k] = zk;
         if (with_dots) {
 #pragma unroll
@@ -679,7 +733,7 @@ __global__ __launch_bounds__(256) void merge_tiles_kernel(int n3, const int *__r
 // newest pair's M y = M (g - g_old) = u_old - u costs no solve of its own.  Same sums per dof as merge_tiles_kernel
 // (tiles of a subdomain, then subdomains, then the division by the multiplicity), then the history terms newest first
 // like build_qpad's.  first: start of the step (no pair yet; u_old is only set).
-template <int NT = 256>
+template <int NT = 256, bool COARSE = false>
 __global__ __launch_bounds__(NT) void merge_tiles_early_kernel(int n3, const int *__restrict__ mt_ptr,
                                                                 const int *__restrict__ mt_ent, const int *__restrict__ dup,
                                                                 const double *__restrict__ ppart, int first,
@@ -691,7 +745,8 @@ __global__ __launch_bounds__(NT) void merge_tiles_early_kernel(int n3, const int
                                                                 double *__restrict__ zshare,
                                                                 double *__restrict__ z, double *__restrict__ partials,
                                                                 const DevLoop *__restrict__ ctl, const int2 *__restrict__ mt_wave,
-                                                                const int *__restrict__ mt_il, double *__restrict__ partialsT)
+                                                                const int *__restrict__ mt_il, double *__restrict__ partialsT,
+                                                                MergeCoarse<COARSE> co)
 {
     __shared__ double sm[(NT / 64) * RED_K];
     KSTAMP(1, 0);
@@ -709,6 +764,12 @@ __global__ __launch_bounds__(NT) void merge_tiles_early_kernel(int n3, const int
         xi[i] = ctl->X.xi[i];
     }
     if (status != 0 || phase != 0) return;
+    double *ysh = nullptr;
+    if constexpr (COARSE) {
+        __shared__ double ybuf[COARSE_NC_MAX];
+        ysh = ybuf;
+        coarse_load_y(co, ysh);
+    }
     const bool il = mt_il != nullptr && vl.v == nullptr && !psub && !zsum;
     const int m = first ? 0 : lm;
     const bool pairNew = !first && pnew != 0 && m > 0;
@@ -808,6 +869,7 @@ __global__ __launch_bounds__(NT) void merge_tiles_early_kernel(int n3, const int
             continue;
         }
         if (d > 1) u /= d;
+        if constexpr (COARSE) u += coarse_term(co, ysh, vtx, k - 3 * vtx);   // u = -M' g: everything below follows (M' is linear and fixed)
         u_old[k] = u;
         const double myn = uo - u;   // M y of the pair the controller has just stored
         if (pairNew) my_new[k] = myn;
@@ -937,43 +999,64 @@ void launch_mask_owned(int n, double *v, const uint8_t *ownMask, hipStream_t st)
     hipLaunchKernelGGL(mask_owned_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, v, ownMask);
 }
 
+// the arguments of a COARSE instantiation from the handle's record
+static MergeCoarse<true> merge_coarse(const CoarseMerge *co)
+{
+    MergeCoarse<true> c;
+    static_cast<CoarseMerge &>(c) = *co;
+    return c;
+}
+
 void launch_merge_early(const DevMesh &M, const DevParts &P, double *z, double *partials, int first, hipStream_t st,
                         const DevLoop *ctl, const double *zsum, const uint8_t *ownMask, VList vl, const uint8_t *kind, int pre,
-                        double *zshare, double *partialsT)
+                        double *zshare, double *partialsT, const CoarseMerge *co)
 {
     const bool split = !P.mt_ptr;
     // (a thread of the 256-thread form takes a dof per trip: beyond two trips -- 1 M tets: eight -- workgroups of 1024 threads)
     const long long ndof = vl.v ? 3ll * vl.n : 3ll * M.nV;
-    if (ndof > 2ll * NB_RED * 256)
-        hipLaunchKernelGGL(merge_tiles_early_kernel<512>, dim3(NB_RED), dim3(512), 0, st, 3 * M.nV, P.mt_ptr, P.mt_ent, P.dup, P.ppart,
-                           first, zsum, split ? P.vp_ptr : nullptr, split ? P.vp_off : nullptr,
-                           split ? (const double *)P.psub : nullptr, ownMask, vl, kind, pre, zshare, z, partials, ctl, P.mt_wave, P.mt_il,
-                           partialsT);
-    else
-    hipLaunchKernelGGL(merge_tiles_early_kernel<256>, dim3(NB_RED), dim3(256), 0, st, 3 * M.nV, P.mt_ptr, P.mt_ent, P.dup, P.ppart,
-                       first, zsum, split ? P.vp_ptr : nullptr, split ? P.vp_off : nullptr,
-                       split ? (const double *)P.psub : nullptr, ownMask, vl, kind, pre, zshare, z, partials, ctl, P.mt_wave, P.mt_il, partialsT);
+#define DOTMI_MERGE_EARLY(NT, COARSE, ...)                                                                                              \
+    hipLaunchKernelGGL((merge_tiles_early_kernel<NT, COARSE>), dim3(NB_RED), dim3(NT), 0, st, 3 * M.nV, P.mt_ptr, P.mt_ent, P.dup, P.ppart, \
+                       first, zsum, split ? P.vp_ptr : nullptr, split ? P.vp_off : nullptr, split ? (const double *)P.psub : nullptr,  \
+                       ownMask, vl, kind, pre, zshare, z, partials, ctl, P.mt_wave, P.mt_il, partialsT, __VA_ARGS__)
+    if (ndof > 2ll * NB_RED * 256) {
+        if (co) DOTMI_MERGE_EARLY(512, true, merge_coarse(co));
+        else DOTMI_MERGE_EARLY(512, false, MergeCoarse<false>());
+    } else {
+        if (co) DOTMI_MERGE_EARLY(256, true, merge_coarse(co));
+        else DOTMI_MERGE_EARLY(256, false, MergeCoarse<false>());
+    }
+#undef DOTMI_MERGE_EARLY
 }
 
 void launch_merge(const DevMesh &M, const DevParts &P, const LbfgsArgs &L, double *z, double *partials,
-                  int with_dots, hipStream_t st, const DevLoop *ctl, VList vl)
+                  int with_dots, hipStream_t st, const DevLoop *ctl, VList vl, const CoarseMerge *co)
 {
+    // with_dots: bit0 = accumulate y_i.z partials, bit1 = divide by dup
+#define DOTMI_MERGE_TILES(DEV, COARSE, ...)                                                                                             \
+    hipLaunchKernelGGL((merge_tiles_kernel<DEV, COARSE>), dim3(NB_RED), dim3(256), 0, st, 3 * M.nV, P.mt_ptr, P.mt_ent, P.dup, P.ppart, L, \
+                       with_dots & 1, (with_dots >> 1) & 1, z, partials, ctl, vl, P.mt_wave, P.mt_il, __VA_ARGS__)
+#define DOTMI_MERGE_PSUB(DEV, COARSE, ...)                                                                                              \
+    hipLaunchKernelGGL((merge_kernel<DEV, COARSE>), dim3(NB_RED), dim3(256), 0, st, M.nV, P.vp_ptr, P.vp_off, P.dup, P.psub, L,          \
+                       with_dots & 1, (with_dots >> 1) & 1, z, partials, ctl, vl, __VA_ARGS__)
     if (P.mt_ptr) {   // (launch_gemv left the tile partials in ppart and skipped the reduce)
-        if (ctl)
-            hipLaunchKernelGGL(merge_tiles_kernel<true>, dim3(NB_RED), dim3(256), 0, st, 3 * M.nV, P.mt_ptr, P.mt_ent, P.dup,
-                               P.ppart, L, with_dots & 1, (with_dots >> 1) & 1, z, partials, ctl, vl, P.mt_wave, P.mt_il);
-        else
-            hipLaunchKernelGGL(merge_tiles_kernel<false>, dim3(NB_RED), dim3(256), 0, st, 3 * M.nV, P.mt_ptr, P.mt_ent, P.dup,
-                               P.ppart, L, with_dots & 1, (with_dots >> 1) & 1, z, partials, ctl, vl, P.mt_wave, P.mt_il);
+        if (ctl) {
+            if (co) DOTMI_MERGE_TILES(true, true, merge_coarse(co));
+            else DOTMI_MERGE_TILES(true, false, MergeCoarse<false>());
+        } else {
+            if (co) DOTMI_MERGE_TILES(false, true, merge_coarse(co));
+            else DOTMI_MERGE_TILES(false, false, MergeCoarse<false>());
+        }
         return;
     }
-    // with_dots: bit0 = accumulate y_i.z partials, bit1 = divide by dup
-    if (ctl)
-        hipLaunchKernelGGL(merge_kernel<true>, dim3(NB_RED), dim3(256), 0, st, M.nV, P.vp_ptr, P.vp_off, P.dup, P.psub,
-                           L, with_dots & 1, (with_dots >> 1) & 1, z, partials, ctl, vl);
-    else
-        hipLaunchKernelGGL(merge_kernel<false>, dim3(NB_RED), dim3(256), 0, st, M.nV, P.vp_ptr, P.vp_off, P.dup, P.psub,
-                           L, with_dots & 1, (with_dots >> 1) & 1, z, partials, ctl, vl);
+    if (ctl) {
+        if (co) DOTMI_MERGE_PSUB(true, true, merge_coarse(co));
+        else DOTMI_MERGE_PSUB(true, false, MergeCoarse<false>());
+    } else {
+        if (co) DOTMI_MERGE_PSUB(false, true, merge_coarse(co));
+        else DOTMI_MERGE_PSUB(false, false, MergeCoarse<false>());
+    }
+#undef DOTMI_MERGE_TILES
+#undef DOTMI_MERGE_PSUB
 }
 
 // Sharded subdomains: z holds the all-reduced SUM over every subdomain; z_v /= dup_v and the partial dots c_i = y_i . z,

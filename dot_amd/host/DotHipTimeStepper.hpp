@@ -61,6 +61,8 @@ struct Options {  // the Config fields the DOT stepper reads (src/Config.hpp)
     int pcgMaxIter = 500, pcgCheckEvery = 8;
     // the rigid-mode coarse term of those solves' preconditioner (dotmi_set_pcg_coarse): off by default
     bool pcgCoarse = false;
+    // the same term in DOT's own block preconditioner, M' = M + Z A0^-1 Z^T (dotmi_set_dot_coarse): off by default
+    bool dotCoarse = false;
 };
 
 class DotHipTimeStepper {
@@ -134,6 +136,14 @@ public:
                                      std::to_string(rc) + ")");
         if (opt_.newtonPCG) check(dotmi_set_pcg(h_, opt_.pcgRelTol, opt_.pcgMaxIter, opt_.pcgCheckEvery), "set_pcg");
         if (opt_.pcgCoarse) check(dotmi_set_pcg_coarse(h_, 1), "set_pcg_coarse");
+        if (opt_.dotCoarse) check(dotmi_set_dot_coarse(h_, 1), "set_dot_coarse");
+    }
+    // the coarse term of DOT's block preconditioner on a built stepper: 0 off, 1 rigid modes (dotmi_set_dot_coarse)
+    void setDotCoarse(int mode)
+    {
+        require_built("setDotCoarse");
+        check(dotmi_set_dot_coarse(h_, mode), "set_dot_coarse");
+        opt_.dotCoarse = mode != 0;
     }
     // the coarse term of the PCG's preconditioner on a built stepper: 0 off, 1 rigid modes (dotmi_set_pcg_coarse)
     void setPCGCoarse(int mode)

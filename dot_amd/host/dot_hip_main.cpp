@@ -15,7 +15,7 @@
 //
 // usage: dot_hip 100 <script.txt> [--mesh-root DIR] [--parts N] [--energy FCR|SNH] [--epart raw.i32]
 //                [--frames K] [--out DIR] [--device D] [--no-files] [--dump-scene K] [--dump-config] [--dump-formats DIR]
-//                [--echo-config FILE] [--fast] [--newton-pcg N [--pcg-coarse]]
+//                [--echo-config FILE] [--fast] [--newton-pcg N [--pcg-coarse]] [--dot-coarse]
 //        dot_hip --write-info FILE nV nT steps iters t0..t21
 #include <algorithm>
 #include <chrono>
@@ -48,7 +48,7 @@ int main(int argc, char **argv)
     }
     if (argc < 3) {
         std::fprintf(stderr, "usage: %s 100 <script.txt> [--mesh-root DIR] [--parts N] [--energy FCR|SNH] "
-                             "[--epart raw.i32] [--frames K] [--out DIR] [--device D] [--no-files] [--dump-scene K] [--dump-config] [--dump-formats DIR] [--fast] [--newton-pcg N [--pcg-coarse]]\n", argv[0]);
+                             "[--epart raw.i32] [--frames K] [--out DIR] [--device D] [--no-files] [--dump-scene K] [--dump-config] [--dump-formats DIR] [--fast] [--newton-pcg N [--pcg-coarse]] [--dot-coarse]\n", argv[0]);
         return 2;
     }
     if (std::string(argv[1]) != "100") {
@@ -58,7 +58,7 @@ int main(int argc, char **argv)
     const std::string scriptPath = argv[2];
     std::string meshRoot = ".", outDir, epartFile, energyOverride;
     int partsOverride = -1, frames = -1, device = 0, dumpScene = -1, newtonPcgParts = 0;
-    bool files = true, dumpConfig = false, fast = false, pcgCoarse = false;
+    bool files = true, dumpConfig = false, fast = false, pcgCoarse = false, dotCoarse = false;
     std::string dumpFormats, echoConfig;
     for (int i = 3; i < argc; ++i) {
         const std::string a = argv[i];
@@ -81,6 +81,8 @@ int main(int argc, char **argv)
         else if (a == "--newton-pcg") newtonPcgParts = std::stoi(next());
         // ... with the rigid-mode coarse term in the solves' preconditioner (dotmi_set_pcg_coarse; at most 256 subdomains)
         else if (a == "--pcg-coarse") pcgCoarse = true;
+        // `timeStepper DOT` scripts: the rigid-mode coarse term in DOT's own block preconditioner (dotmi_set_dot_coarse)
+        else if (a == "--dot-coarse") dotCoarse = true;
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     try {
@@ -116,6 +118,8 @@ int main(int argc, char **argv)
         // `timeStepper LBFGSH` (LBFGSTimeStepper with D0T_H, LBFGSTimeStepper.cpp:196-262, :338-420): L-BFGS whose initial
         // inverse Hessian is the factored GLOBAL projected Hessian and whose line search starts from step 1 -- this
         // path with the whole mesh as ONE subdomain (no averaging: dup = 1) and the alpha_0 clamp at 1
+        if (dotCoarse && newtonPcgParts != 0)
+            throw std::runtime_error("--dot-coarse is the coarse term of DOT's own preconditioner: not together with --newton-pcg");
         if (newtonPcgParts != 0 && (cfg.timeStepper != "Newton" || newtonPcgParts < 1))
             throw std::runtime_error("--newton-pcg <N> takes N >= 1 and a script with `timeStepper Newton`");
         const bool newtonPcg = newtonPcgParts > 0;
@@ -217,6 +221,7 @@ int main(int argc, char **argv)
         }
         opt.lbfgsPD = lbfgsPD;
         opt.lbfgsHI = lbfgsHI;
+        opt.dotCoarse = dotCoarse;   // (refused by the library on every stepper but DOT's own, with its message)
         // `timeStepper LBFGSJH <n>`: block-Jacobi on a vertex partition (the reference takes METIS::partMesh_nodes;
         // without METIS a vertex goes to the lowest-numbered subdomain among its elements) and a unit first step
         std::vector<int32_t> vpart;
@@ -308,6 +313,15 @@ int main(int argc, char **argv)
                 throw std::runtime_error("dotmi_pcg_coarse_info failed");
             std::printf("PCG coarse space: dimension %d, %d dropped, active %d, %lld builds, %lld CG iterations in %lld solves\n", dim,
                         dropped, active, (long long)builds, (long long)cgIters, (long long)solves);
+        }
+        if (dotCoarse) {
+            int32_t dim = 0, dropped = 0, active = 0;
+            int64_t builds = 0;
+            double ms = 0;
+            if (dotmi_dot_coarse_info(ts.handle(), &dim, &dropped, &active, &builds, &ms) != 0)
+                throw std::runtime_error("dotmi_dot_coarse_info failed");
+            std::printf("DOT coarse space: dimension %d, %d dropped, active %d, %lld builds, last build %.3f ms\n", dim, dropped, active,
+                        (long long)builds, ms);
         }
         if (files) {
             timers.descent = tStep;

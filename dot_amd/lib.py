@@ -81,6 +81,7 @@ EXPORTS = [
     "dotmi_set_rel_tol", "dotmi_set_time_step", "dotmi_set_lame",
     "dotmi_solve_hessian", "dotmi_set_pcg", "dotmi_pcg_info",
     "dotmi_set_pcg_coarse", "dotmi_pcg_coarse_info", "dotmi_pcg_coarse_matrix", "dotmi_pcg_apply_precond", "dotmi_plan_coarse",
+    "dotmi_set_dot_coarse", "dotmi_dot_coarse_info",
 ]
 
 _lib = None
@@ -170,6 +171,9 @@ def load() -> C.CDLL:
         L.dotmi_pcg_coarse_matrix.argtypes = [H, C.c_int32, c_dp]
         L.dotmi_pcg_apply_precond.argtypes = [H, c_dp, c_dp]
         L.dotmi_plan_coarse.argtypes = [C.c_int32, C.c_int32, c_ip, c_ip, C.c_int32] + [c_ip] * 9
+    if hasattr(L, "dotmi_set_dot_coarse"):
+        L.dotmi_set_dot_coarse.argtypes = [H, C.c_int32]
+        L.dotmi_dot_coarse_info.argtypes = [H, c_ip, c_ip, c_ip, C.POINTER(C.c_int64), c_dp]
     L.dotmi_plan_layout.argtypes = [C.c_int32, C.c_int32, c_ip, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32,
                                     C.c_int32, C.c_int32, C.c_int32, c_ip, c_ip, c_ip, c_ip]
     if hasattr(L, "dotmi_plan_backsolve_tiles"):   # (round 5 entry; guarded like the two above -- ADVICE r05)

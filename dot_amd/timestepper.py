@@ -333,6 +333,20 @@ class DOTTimeStepper:
         self._check(self._L.dotmi_pcg_apply_precond(self._h, dp(r), dp(w)), "pcg_apply_precond")
         return w
 
+    def setDotCoarse(self, mode: int = 1):
+        """the rigid-mode coarse term in DOT's own block preconditioner, M' = M + Z A0^-1 Z^T: 0 off (the default), 1 on
+        (dotmi_set_dot_coarse).  step(), applyPrecond() and probeDirection() then use M'; A0 is built behind every refresh of H."""
+        self._check(self._L.dotmi_set_dot_coarse(self._h, mode), "set_dot_coarse")
+
+    def dotCoarseInfo(self):
+        """(dimension 6 nParts, subdomains the last build dropped, active, coarse builds since create, ms of the last build)
+        (dotmi_dot_coarse_info)"""
+        dim, dr, ac, nb, ms = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64(), C.c_double()
+        self._check(self._L.dotmi_dot_coarse_info(self._h, C.cast(C.byref(dim), _lib.c_ip), C.cast(C.byref(dr), _lib.c_ip),
+                                                  C.cast(C.byref(ac), _lib.c_ip), C.byref(nb), C.cast(C.byref(ms), _lib.c_dp)),
+                    "dot_coarse_info")
+        return dim.value, dr.value, ac.value, nb.value, ms.value
+
     def multiply(self, p) -> np.ndarray:
         p = np.ascontiguousarray(p, dtype=np.float64)
         out = np.empty((self.nV, 3))

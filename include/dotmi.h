@@ -500,6 +500,22 @@ int dotmi_pcg_coarse_matrix(dotmi_handle *h, int32_t cap, double *A0);
 /* one application of the preconditioner exactly as the PCG uses it: w = M_sym r, plus Z A0^-1 Z^T r when the coarse term is active
  * (a stale A0 is rebuilt first).  r, w: nV*3.  Refused like dotmi_solve_hessian. */
 int dotmi_pcg_apply_precond(dotmi_handle *h, const double *r, double *w);
+/* The same rigid-mode coarse term in DOT's own loop (the reference has no counterpart, so iteration counts
+ * differ from its: opt-in).  mode 0 = off (the default: every entry runs exactly the launches it runs without this one), 1 = the
+ * two-loop recursion of dotmi_step, dotmi_apply_precond and dotmi_probe_direction use  M' = M + Z A0^-1 Z^T  with
+ * M = D^-1 sum_s R_s^T H_s^-1 R_s the block preconditioner and Z, A0, the dropped-subdomain and the pivot rule those of
+ * dotmi_set_pcg_coarse (one build serves both modes).  A0 is built behind every refresh of H (the end of a step, dotmi_refactor,
+ * dotmi_refix, dotmi_set_time_step, dotmi_set_lame) at the positions the refresh was made at, and by this entry when it switches the
+ * mode on; its pivot flag is read with the refresh's own synchronisation.  A non-positive pivot switches the term off until the next
+ * successful build: the step runs on M, the handle is not poisoned.  A step with the mode on does not take the unit step
+ * speculatively (DOTMI_SPEC_STEP).  DOTMI_E_INVALID with a message on a handle of more than one rank, with DOTMI_FLAG_FORCE_DIST,
+ * _OWNER_EXCHANGE, _GSDD, _NEWTON, _NEWTON_PCG, _LBFGS_PD, _LBFGS_HI or _ASYNC_REFRESH, on a vpart handle, for any other mode, and
+ * above 256 subdomains. */
+int dotmi_set_dot_coarse(dotmi_handle *h, int32_t mode);
+/* *dim = 6 nParts with the mode on, else 0; the subdomains the last build dropped; *active = 1 when the applications add the coarse
+ * term; the coarse builds since create (both modes); the device time of the last one in ms.  Any pointer may be NULL. */
+int dotmi_dot_coarse_info(const dotmi_handle *h, int32_t *dim, int32_t *dropped_subdomains, int32_t *active, int64_t *builds,
+                          double *last_build_ms);
 /* (host only) the lists of the coarse space (dot_amd/csrc/coarse_plan.hpp) for an element partition epart[nT] into nParts <= 256
  * subdomains.  sizes[3] = {coupled pairs nP, entries nE, (vertex, subdomain) incidences nI}; call with NULL arrays first.
  * pairS[nP], pairT[nP]: every unordered pair of subdomains some H block couples once, s <= t, diagonals included, ordered by (s, t);
