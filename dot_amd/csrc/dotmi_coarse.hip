@@ -11,6 +11,14 @@
 // same lists, Z, A0 and factor (one build serves both modes).  There the build is enqueued behind every refresh of H, at the positions
 // the refresh was made at, and its pivot flag is read after the synchronisation the refresh ends in anyway -- no read-back of its own
 // in a step.  The restriction reads the padded right-hand sides (coarse_restrict_pad_kernel), the prolongation is part of the merges.
+// DOTMI_FLAG_DOT_COARSE puts that term on a sharded handle (world > 1, DOTMI_FLAG_FORCE_DIST).  The plan, Z, the
+// weights, the dropped subdomains, the frozen x and the centroids are global and computed on every rank alike (x is replicated there);
+// the restriction table covers the rank's own subdomains.  With a replicated Hessian every rank assembles every pair as one GPU does;
+// with a sharded one a rank assembles the pairs (s, t), s <= t, whose s it owns -- the block rows of its subdomains' vertices are
+// assembled whole, so every H block such a pair names is there --, writes zeros for the others, and one all-reduce of the 36 nPairs
+// doubles per refresh makes pairA whole (disjoint contributions: the sum is exact).  Fill and factorisation of the one dense block run
+// on every rank.  Per application c = Z^T r rides in the tail of the vector the iteration all-reduces anyway and the solve runs on
+// every rank behind that collective (dot_coarse_restrict / dot_coarse_solve).
 #include "coarse_plan.hpp"
 #include "dotmi_handle.hpp"
 
@@ -32,23 +40,31 @@ static int coarse_setup(dotmi_handle *h)
             h->err = "dotmi_set_pcg_coarse: the coarse plan's subdomains differ from the handle's";
             return DOTMI_E_INVALID;
         }
-    // the padded restriction (dotmi_set_dot_coarse) finds a subdomain's vertices in its padded range: every vertex of every subdomain has
-    // its three consecutive positions there (place_rows), the same subdomains in the same order (one rank: all of them are owned)
-    if (h->P.nParts != nP || (int)h->partPos.size() != nP) {
+    // the padded restriction (dotmi_set_dot_coarse) finds a subdomain's vertices in its padded range: every vertex of every subdomain
+    // the handle owns has its three consecutive positions there (place_rows), the subdomains [p0, p1) in their order by local index
+    // (one rank: all of them; a sharded handle restricts its own and the ranks' parts of c are summed, DOTMI_FLAG_DOT_COARSE)
+    const int nOwn = h->p1 - h->p0;
+    if (h->P.nParts != nOwn || (int)h->partPos.size() != nOwn || (!h->dist && nOwn != nP)) {
         h->err = "dotmi_set_pcg_coarse / dotmi_set_dot_coarse: the handle does not own every subdomain";
         return DOTMI_E_INVALID;
     }
-    for (int s = 0; s < nP; ++s) {
-        bool ok = h->partPos[s].size() == h->partVerts[s].size();
-        for (size_t i = 0; ok && i < h->partPos[s].size(); ++i) ok = h->partPos[s][i] >= 0 && h->partPos[s][i] + 3 <= h->P.nmax;
+    for (int ls = 0; ls < nOwn; ++ls) {
+        bool ok = h->partPos[ls].size() == h->partVerts[h->p0 + ls].size();
+        for (size_t i = 0; ok && i < h->partPos[ls].size(); ++i) ok = h->partPos[ls][i] >= 0 && h->partPos[ls][i] + 3 <= h->P.nmax;
         if (!ok) {
-            h->err = "dotmi_set_dot_coarse: a vertex of subdomain " + std::to_string(s) + " has no place in the padded right-hand sides";
+            h->err = "dotmi_set_dot_coarse: a vertex of subdomain " + std::to_string(h->p0 + ls) + " has no place in the padded right-hand sides";
             return DOTMI_E_INVALID;
         }
     }
     D.nmax = h->P.nmax;
     D.dofmap = h->P.dofmap;
-    if (int rc = dalloc(h, &D.rtab, (size_t)nP * D.nmax)) return rc;
+    D.p0 = h->p0;
+    D.nOwn = nOwn;
+    // who assembles which pair: everything, unless the Hessian refresh is sharded -- then H is whole only on the block rows of the
+    // rank's own subdomains' vertices, which is what the pairs (s, t), s <= t, with s its own read
+    D.as0 = h->shardHess ? h->p0 : 0;
+    D.as1 = h->shardHess ? h->p1 : nP;
+    if (int rc = dalloc(h, &D.rtab, (size_t)nOwn * D.nmax)) return rc;
     D.nParts = nP;
     D.nc = 6 * nP;
     D.ncp = (D.nc + TILE - 1) / TILE * TILE;
@@ -141,6 +157,11 @@ int coarse_issue(dotmi_handle *h, const double *x)
     launch_coarse_centroid(D, h->st);
     launch_coarse_rtab(D, h->st);
     launch_coarse_assemble(D, h->M, h->Hval, h->st);
+    // sharded Hessian refresh: every pair's block was assembled by exactly one rank, the owner of s, and is zero elsewhere
+    if (h->shardHess)
+        if (int rc = allreduce_sum(h, D.pairA, (size_t)36 * D.nPairs)) return rc;
+    // from here on every rank holds the same pairA, live flags and padding: the fill, the factorisation and with them the pivot flag
+    // are functions of identical data, so a non-positive pivot leaves the term inactive on ALL ranks alike -- no agreement collective
     launch_coarse_fill(D, h->st);
     HIPCHECK(h, hipMemsetAsync(D.info, 0, sizeof(int), h->st));
     for (size_t l = 0; l + 1 < K.levelStart.size(); ++l)   // one launch per level of the block's own schedule
@@ -178,12 +199,22 @@ int coarse_refresh(dotmi_handle *h)
     return 0;
 }
 
-void dot_coarse_restrict_solve(dotmi_handle *h, const DevLoop *ctl, int spec)
+void dot_coarse_restrict(dotmi_handle *h, double *c, const DevLoop *ctl, int spec)
+{
+    launch_coarse_restrict_pad(h->coarse.D, h->P.rpad, h->st, ctl, spec, c);
+}
+
+void dot_coarse_solve(dotmi_handle *h, const double *c, const DevLoop *ctl, int spec)
 {
     const DevCoarse &D = h->coarse.D;
-    launch_coarse_restrict_pad(D, h->P.rpad, h->st, ctl, spec);
-    if (ctl) launch_coarse_solve_loop(D, h->st, ctl, spec);
-    else launch_coarse_solve(D, h->st);
+    if (ctl) launch_coarse_solve_loop(D, h->st, ctl, spec, c);
+    else launch_coarse_solve(D, h->st, c);
+}
+
+void dot_coarse_restrict_solve(dotmi_handle *h, const DevLoop *ctl, int spec)
+{
+    dot_coarse_restrict(h, nullptr, ctl, spec);
+    dot_coarse_solve(h, nullptr, ctl, spec);
 }
 
 void coarse_restrict_solve(dotmi_handle *h, const double *r)

@@ -885,6 +885,31 @@ static int take_arguments(dotmi_handle *h, const dotmi_mesh *mesh, const dotmi_p
         h->epart.resize(h->nT);
         partition_elements(mesh->nV, mesh->nT, mesh->T, mesh->X_rest, mesh->nParts, h->epart.data());
     }
+    if (h->flags & DOTMI_FLAG_DOT_COARSE) {
+        // the term of dotmi_set_dot_coarse from create on (the only way to it on a sharded handle: it changes the payload of a
+        // collective, so it is fixed for the life of the communicator); what the setter refuses is refused here
+        const char *why = (h->flags & DOTMI_FLAG_OWNER_EXCHANGE)
+                              ? "not with DOTMI_FLAG_OWNER_EXCHANGE (its merge in front of the exchange forms z before the coarse solution y exists)"
+                          : (h->flags & DOTMI_FLAG_GSDD)       ? "not with DOTMI_FLAG_GSDD (a GSDD handle solves one subdomain at a time)"
+                          : (h->flags & DOTMI_FLAG_NEWTON_PCG) ? "not with DOTMI_FLAG_NEWTON_PCG (its coarse term is dotmi_set_pcg_coarse)"
+                          : (h->flags & DOTMI_FLAG_NEWTON)     ? "not with DOTMI_FLAG_NEWTON (a Newton handle factorises H as one subdomain)"
+                          : (h->flags & DOTMI_FLAG_LBFGS_PD)   ? "not with DOTMI_FLAG_LBFGS_PD (no Hessian block solve)"
+                          : (h->flags & DOTMI_FLAG_LBFGS_HI)   ? "not with DOTMI_FLAG_LBFGS_HI (no Hessian block solve)"
+                          : (h->flags & DOTMI_FLAG_ASYNC_REFRESH)
+                              ? "not with DOTMI_FLAG_ASYNC_REFRESH (the build is judged with the refresh)"
+                          : mesh->vpart ? "not with a vertex partition (vpart): the coarse plan works on an element partition"
+                                        : nullptr;
+        if (why) {
+            h->err = std::string("DOTMI_FLAG_DOT_COARSE: ") + why;
+            return DOTMI_E_INVALID;
+        }
+        if (h->nPartsAll > COARSE_MAX_PARTS) {
+            h->err = "DOTMI_FLAG_DOT_COARSE: at most " + std::to_string(COARSE_MAX_PARTS) + " subdomains (the coarse matrix is applied "
+                     "through a dense inverse factor); " + std::to_string(h->nPartsAll) + " were asked for";
+            return DOTMI_E_INVALID;
+        }
+        h->coarse.dotMode = 1;   // the refresh create ends in builds A0 behind itself, as every later one
+    }
     h->fixed.assign(mesh->fixed, mesh->fixed + h->nV);
     h->Xrest.assign(mesh->X_rest, mesh->X_rest + h->n);
     h->mu.assign(mesh->mu, mesh->mu + h->nT);
@@ -962,8 +987,10 @@ static int choose_loop_form(dotmi_handle *h)
 static int alloc_loop_state(dotmi_handle *h)
 {
     if (h->dist) {
-        if (int rc = dalloc(h, &h->zstage, (size_t)h->n)) return rc;
-        HIPCHECK(h, hipMemsetAsync(h->zstage, 0, sizeof(double) * h->n, h->st));   // (owner exchange: stays zero off the held set)
+        // (DOTMI_FLAG_DOT_COARSE: the packet's tail c = Z^T r behind the n sums)
+        const size_t nz = (size_t)h->n + dot_coarse_tail(h);
+        if (int rc = dalloc(h, &h->zstage, nz)) return rc;
+        HIPCHECK(h, hipMemsetAsync(h->zstage, 0, sizeof(double) * nz, h->st));   // (owner exchange: stays zero off the held set)
     }
     if (h->vpFits && h->VP.orec) {   // the pairs as records (DevLoop::hrec): zeroed once, every step starts with an empty history
         const size_t nrec = (size_t)2 * (HIST_MAX + 1) * h->n;
@@ -1068,9 +1095,11 @@ static int create_impl(dotmi_handle *h, const dotmi_mesh *mesh, const dotmi_para
     const int n = h->n;
     double **vecs[] = {&h->x, &h->x_trial, &h->xn, &h->v, &h->xt, &h->g, &h->g_trial, &h->p, &h->q, &h->z,
                        &h->Hp, &h->tmpn};
+    // (a sharded handle with DOTMI_FLAG_DOT_COARSE: z travels with c = Z^T r in its tail, apply_precond / the q-based slot)
+    const size_t nvec = (size_t)n + 8 + dot_coarse_tail(h);
     for (double **pp : vecs) {
-        if (int rc = dalloc(h, pp, (size_t)n + 8)) return rc;
-        HIPCHECK(h, hipMemsetAsync(*pp, 0, sizeof(double) * (n + 8), h->st));
+        if (int rc = dalloc(h, pp, nvec)) return rc;
+        HIPCHECK(h, hipMemsetAsync(*pp, 0, sizeof(double) * nvec, h->st));
     }
     for (int s = 0; s <= h->hist; ++s) {
         if (int rc = dalloc(h, &h->S[s], (size_t)n)) return rc;

@@ -132,9 +132,13 @@ static int slot_gradient(dotmi_handle *h, Slot &s)
 // just written, y = A0^-1 c.  Like the back-solve behind them the two kernels run whatever the controller will say about the trial --
 // in a retry slot too, whose trial may be the accepted one --, and return at once past the end of the loop.  They write c and the
 // parts of y only; a merge that is gated off never reads them, so held, stopped, paired and two-level slots need nothing else
+// Sharded subdomains (DOTMI_FLAG_DOT_COARSE): only the restriction runs here, over the rank's own subdomains into the tail of the
+// staging buffer slot_merge all-reduces; the solve follows that collective
 static void slot_coarse(dotmi_handle *h)
 {
-    if (dot_coarse(h)) dot_coarse_restrict_solve(h, h->ctl, 1);
+    if (!dot_coarse(h)) return;
+    if (h->dist) dot_coarse_restrict(h, h->zstage + h->n, h->ctl, 1);
+    else dot_coarse_restrict_solve(h, h->ctl, 1);
 }
 
 // stage 4, back-solve on -g_trial with the controller as one workgroup of its launch
@@ -163,9 +167,14 @@ static int slot_merge(dotmi_handle *h)
         // still runs, on stale scratch, and z is left alone)
         LbfgsArgs L0;
         memset(&L0, 0, sizeof(L0));
+        // DOTMI_FLAG_DOT_COARSE: the packet is [zsum (n) ; c (nc)] -- slot_coarse has left this rank's part of c = Z^T (-g_trial) in the
+        // tail --, every rank solves A0 y = c on the summed tail behind the collective (gated like the merge that reads y: the
+        // controller has spoken by now) and the zsum branch of the merge adds Z y behind the division
+        const CoarseMerge *co = dot_coarse(h);
         launch_merge(h->M, h->P, L0, h->zstage, h->partC, 0, h->st, h->ctl, h->held());
-        if (int rc = allreduce_sum(h, h->zstage, h->n)) return rc;
-        launch_merge_early(h->M, h->P, h->z, h->partC, 0, h->st, h->ctl, h->zstage);
+        if (int rc = allreduce_sum(h, h->zstage, h->n + dot_coarse_tail(h))) return rc;
+        if (co) dot_coarse_solve(h, h->zstage + h->n, h->ctl, 0);
+        launch_merge_early(h->M, h->P, h->z, h->partC, 0, h->st, h->ctl, h->zstage, nullptr, VList(), nullptr, 0, nullptr, nullptr, co);
     } else {
         // owner exchange: merge_early merges the tiles itself.
         // zstage: this rank's subdomains' sum, zero on the vertices it does not hold; only the shared vertices' entries
@@ -209,7 +218,10 @@ static int enqueue_loop_slot(dotmi_handle *h)
     memset(&L0, 0, sizeof(L0));
     launch_build_qpad(h->P, h->g, L0, nullptr, h->st, h->ctl);   // q, straight into the padded right-hand sides
     const CoarseMerge *co = dot_coarse(h);
-    if (co) dot_coarse_restrict_solve(h, h->ctl, 0);             // dotmi_set_dot_coarse: y = A0^-1 Z^T q, gated like the back-solve
+    // dotmi_set_dot_coarse: y = A0^-1 Z^T q, gated like the back-solve (sharded subdomains: the restriction into the tail of z's
+    // packet here, the solve behind the collective below)
+    if (co && h->dist) dot_coarse_restrict(h, h->z + n, h->ctl, 0);
+    else if (co) dot_coarse_restrict_solve(h, h->ctl, 0);
     const Bracket br = backsolve_bracket(h);
     h->slotTimed.push_back(br.at);
     launch_gemv(h->P, nullptr, h->st, h->ctl, br.ev0, br.ev1);
@@ -220,8 +232,9 @@ static int enqueue_loop_slot(dotmi_handle *h)
         // in retries and past the end, where the kernels around it return at once), so every rank issues the same
         // sequence of collectives whatever the controller decides
         launch_merge(h->M, h->P, L0, h->z, h->partC, 0, h->st, h->ctl);
-        if (int rc = allreduce_sum(h, h->z, n)) return rc;
-        launch_zfinish(h->nV, h->P.dup, L0, h->z, h->partC, h->st, h->ctl);
+        if (int rc = allreduce_sum(h, h->z, n + dot_coarse_tail(h))) return rc;
+        if (co) dot_coarse_solve(h, h->z + n, h->ctl, 0);
+        launch_zfinish(h->nV, h->P.dup, L0, h->z, h->partC, h->st, h->ctl, co);
     }
     launch_build_p(n, h->z, L0, h->partC, nullptr, h->p, h->st, h->ctl);
     launch_spmv_dots(h->M, h->Hval, h->p, h->g, nullptr, h->v0, h->v1, h->partS, h->st, h->ctl);
@@ -361,12 +374,15 @@ static int step_start_sharded(dotmi_handle *h, int nb)
     // early order on the sharded element pass: -g_0 (the summed gradient) into this rank's right-hand sides, the
     // first direction's solve with the start-of-step controller inside its launch, the sum over the ranks, z = u
     launch_build_qpad(h->P, h->g, L0, nullptr, h->st, nullptr);
+    const CoarseMerge *co = dot_coarse(h);   // (DOTMI_FLAG_DOT_COARSE, never with the owner exchange: as in slot_merge)
+    if (co) dot_coarse_restrict(h, h->zstage + n);
     CtlArgs ca{h->ctl, h->gstage + n, ctlR, h->alpha_dev, h->h_flags, 1, 1};
     launch_gemv(h->P, nullptr, h->st, h->ctl, nullptr, nullptr, &ca, 1 << 30);
     launch_merge(h->M, h->P, L0, h->zstage, h->partC, 0, h->st, h->ctl, h->held());
     if (!h->owner) {
-        if (int rc = allreduce_sum(h, h->zstage, n)) return rc;
-        launch_merge_early(h->M, h->P, h->z, h->partC, 1, h->st, h->ctl, h->zstage);
+        if (int rc = allreduce_sum(h, h->zstage, n + dot_coarse_tail(h))) return rc;
+        if (co) dot_coarse_solve(h, h->zstage + n, h->ctl, 0);
+        launch_merge_early(h->M, h->P, h->z, h->partC, 1, h->st, h->ctl, h->zstage, nullptr, VList(), nullptr, 0, nullptr, nullptr, co);
     } else {
         if (int rc = exchange_iface(h, h->zstage, nullptr, 0)) return rc;
         // (no pair yet: no y_i . z to sum)
@@ -416,16 +432,19 @@ static int enqueue_step_start(dotmi_handle *h)
         return 0;
     }
     // the first direction's solve, u = -M g_0 and z = u, with the start-of-step controller inside its launch
-    if (dot_coarse(h)) dot_coarse_restrict_solve(h);   // (dotmi_set_dot_coarse: y = A0^-1 Z^T (-g_0) for the merge below)
+    // (dotmi_set_dot_coarse: y = A0^-1 Z^T (-g_0) for the merge below; sharded subdomains: the restriction into the packet's tail)
+    const CoarseMerge *co = dot_coarse(h);
+    if (co && h->dist) dot_coarse_restrict(h, h->zstage + h->n);
+    else if (co) dot_coarse_restrict_solve(h);
     CtlArgs ca{h->ctl, h->partE, h->partR, h->alpha_dev, h->h_flags, nb, 1};
     (h->vpNow ? launch_gemv_vp : launch_gemv)(h->P, nullptr, h->st, h->ctl, nullptr, nullptr, &ca, 1 << 30);
     if (!h->dist) {
-        launch_merge_early(h->M, h->P, h->z, h->partC, 1, h->st, h->ctl, nullptr, nullptr, VList(), nullptr, 0, nullptr, h->partCT,
-                           dot_coarse(h));
+        launch_merge_early(h->M, h->P, h->z, h->partC, 1, h->st, h->ctl, nullptr, nullptr, VList(), nullptr, 0, nullptr, h->partCT, co);
     } else {
         launch_merge(h->M, h->P, L0, h->zstage, h->partC, 0, h->st, h->ctl);
-        if (int rc = allreduce_sum(h, h->zstage, h->n)) return rc;
-        launch_merge_early(h->M, h->P, h->z, h->partC, 1, h->st, h->ctl, h->zstage);
+        if (int rc = allreduce_sum(h, h->zstage, h->n + dot_coarse_tail(h))) return rc;
+        if (co) dot_coarse_solve(h, h->zstage + h->n, h->ctl, 0);
+        launch_merge_early(h->M, h->P, h->z, h->partC, 1, h->st, h->ctl, h->zstage, nullptr, VList(), nullptr, 0, nullptr, nullptr, co);
     }
     return 0;
 }

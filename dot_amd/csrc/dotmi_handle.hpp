@@ -401,6 +401,14 @@ inline const CoarseMerge *dot_coarse(const dotmi_handle *h)
 inline int dot_coarse_refresh(dotmi_handle *h) { return h->coarse.dotMode != 0 ? coarse_refresh(h) : 0; }
 // c = Z^T r from the padded right-hand sides, y = A0^-1 c (ctl: as kernels of the device-resident loop; spec: the early order)
 void dot_coarse_restrict_solve(dotmi_handle *h, const DevLoop *ctl = nullptr, int spec = 0);
+// DOTMI_FLAG_DOT_COARSE on a sharded handle: the two halves around the iteration's collective.  The restriction of the rank's own
+// subdomains goes into the dot_coarse_tail doubles behind the n of the vector that travels (zeros for the others' subdomains), the
+// all-reduce of n + tail doubles makes c whole and identical on every rank, and every rank solves on it behind the collective
+void dot_coarse_restrict(dotmi_handle *h, double *c, const DevLoop *ctl = nullptr, int spec = 0);
+void dot_coarse_solve(dotmi_handle *h, const double *c, const DevLoop *ctl = nullptr, int spec = 0);
+// what the z packet of a sharded handle carries behind its n entries: nc = 6 nParts doubles with the flag, whether the last build left
+// the term active or not (the payload of a collective never depends on a rank's state), else nothing
+inline size_t dot_coarse_tail(const dotmi_handle *h) { return (h->dist && h->coarse.dotMode != 0) ? (size_t)6 * h->nPartsAll : 0; }
 void coarse_restrict_solve(dotmi_handle *h, const double *r);   // c = Z^T r, y = A0^-1 c
 void coarse_prolong(dotmi_handle *h, double *zsum);             // zsum += (Z y) / isd
 // dotmi_collectives.hip

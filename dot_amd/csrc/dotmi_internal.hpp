@@ -553,8 +553,9 @@ void launch_be_update(int nV, const uint8_t *fixed, double *x, double *xn, doubl
 void launch_scatter_rows(int n, const int *idx, const double *pos, double *x, hipStream_t st);
 void launch_copy(int n, const double *src, double *dst, hipStream_t st);
 // sharded subdomains, after the all-reduce of the merged sums: z_v /= dup_v and the y_i . z partials
+// (co: + (Z y)_v behind the division, DOTMI_FLAG_DOT_COARSE)
 void launch_zfinish(int nV, const int *dup, const LbfgsArgs &L, double *z, double *partials, hipStream_t st,
-                    const DevLoop *ctl = nullptr);
+                    const DevLoop *ctl = nullptr, const CoarseMerge *co = nullptr);
 // k_reconfig.hip (dotmi_set_lame / dotmi_set_time_step): the per-slot Lame parameters of a patch family from the global
 // per-element arrays through the family's slot -> element table (padding slots, -1, get the neutral 1.0 that create gives them)
 void launch_gather_lame(const int *slotElem, size_t nSlots, const double *mu, const double *lam, double *mu_s, double *lam_s,
@@ -610,7 +611,12 @@ struct DevCoarse {
     // dotmi_set_dot_coarse: the restriction from the padded right-hand sides (DevParts::rpad / dofmap / nmax of the same handle)
     int nmax = 0;
     const int *dofmap = nullptr;
-    double4 *rtab = nullptr;                       // nParts * nmax: (w_v, k_0, k_1, k_2) per padded position (coarse_rtab_kernel)
+    double4 *rtab = nullptr;                       // nOwn * nmax: (w_v, k_0, k_1, k_2) per padded position (coarse_rtab_kernel)
+    // the handle's own subdomains [p0, p0 + nOwn) -- all of them on one rank --: the padded ranges above are theirs, by local index
+    int p0 = 0, nOwn = 0;
+    // the pairs (s, t), s <= t, this handle assembles: those with s in [as0, as1) -- every pair, unless the Hessian refresh is sharded
+    // (then [p0, p0 + nOwn), and pairA is summed over the ranks)
+    int as0 = 0, as1 = 0;
 };
 // what a merge kernel's COARSE instantiation needs for the prolongation  u_v += w_v sum_{s holds v} (t_s + omega_s x (x_v - c_s))
 struct CoarseMerge {
@@ -622,14 +628,16 @@ void launch_coarse_centroid(const DevCoarse &C, hipStream_t st);
 void launch_coarse_assemble(const DevCoarse &C, const DevMesh &M, const double *Hval, hipStream_t st);
 void launch_coarse_fill(const DevCoarse &C, hipStream_t st);
 void launch_coarse_restrict(const DevCoarse &C, const double *r, hipStream_t st);                       // c = Z^T r
-void launch_coarse_solve(const DevCoarse &C, hipStream_t st);                                           // y = X^T (X c)
+void launch_coarse_solve(const DevCoarse &C, hipStream_t st, const double *c = nullptr);               // y = X^T (X c); c: DevCoarse::c unless given
 void launch_coarse_prolong(const DevCoarse &C, int nV, const double *isd, double *zsum, hipStream_t st);   // zsum += (Z y) / isd
 void launch_coarse_scale(int n, const double *a, const double *isd, double *out, hipStream_t st);       // out = a (.) isd per vertex
 // dotmi_set_dot_coarse: the table of the padded restriction (once per build); c = Z^T r from the padded right-hand sides and the
-// solve as kernels of the loop (ctl != nullptr: gated by its status, and by its retry phase unless spec)
+// solve as kernels of the loop (ctl != nullptr: gated by its status, and by its retry phase unless spec).  c: where Z^T r is written /
+// read, DevCoarse::c unless given (a sharded handle: the tail of the vector that is all-reduced between the two)
 void launch_coarse_rtab(const DevCoarse &C, hipStream_t st);
-void launch_coarse_restrict_pad(const DevCoarse &C, const double *rpad, hipStream_t st, const DevLoop *ctl = nullptr, int spec = 0);
-void launch_coarse_solve_loop(const DevCoarse &C, hipStream_t st, const DevLoop *ctl, int spec);
+void launch_coarse_restrict_pad(const DevCoarse &C, const double *rpad, hipStream_t st, const DevLoop *ctl = nullptr, int spec = 0,
+                                double *c = nullptr);
+void launch_coarse_solve_loop(const DevCoarse &C, hipStream_t st, const DevLoop *ctl, int spec, const double *c = nullptr);
 // host: the dense nc x nc matrix from the pairs' blocks, entry by entry as the fill kernel writes it
 void coarse_dense_host(int nc, int nParts, const int *pairAt, const int *live, const double *pairA, double *A0);
 

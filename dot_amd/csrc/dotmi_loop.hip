@@ -77,7 +77,8 @@ void two_loop_xi(int m, const double *b, const double (*sy)[HIST_MAX], const dou
 
 // p = D^-1 sum_s R_s^T W_s R_s q   (DOTTimeStepper.cpp:406-450); leaves y_i.z partials in partC
 // dotmi_set_dot_coarse with an active term: + Z A0^-1 Z^T q -- the restriction from the padded right-hand sides (where launch_gemv has
-// put q, or build_qpad before it) and the coarse solve behind the back-solve, the prolongation inside the merge
+// put q, or build_qpad before it) and the coarse solve behind the back-solve, the prolongation inside the merge (sharded subdomains,
+// DOTMI_FLAG_DOT_COARSE: the restriction in the tail of z's packet, the solve behind the collective, the prolongation in zfinish)
 int apply_precond(dotmi_handle *h, const double *q, double *z, const LbfgsArgs &L)
 {
     const Bracket br = backsolve_bracket(h);
@@ -87,9 +88,15 @@ int apply_precond(dotmi_handle *h, const double *q, double *z, const LbfgsArgs &
         if (co) dot_coarse_restrict_solve(h);
         launch_merge(h->M, h->P, L, z, h->partC, 1 | 2, h->st, nullptr, VList(), co);
     } else {
+        // DOTMI_FLAG_DOT_COARSE: c = Z^T q of this rank's subdomains in the tail of z, summed with z; the solve on every rank behind the
+        // collective; the prolongation behind the division (z: one of the handle's vectors, which have room for the tail)
+        const CoarseMerge *co = dot_coarse(h);
+        const size_t tail = dot_coarse_tail(h);
+        if (co) dot_coarse_restrict(h, z + h->n);
         launch_merge(h->M, h->P, L, z, h->partC, 0, h->st);
-        if (int rc = allreduce_sum(h, z, h->n)) return rc;
-        launch_zfinish(h->nV, h->P.dup, L, z, h->partC, h->st);
+        if (int rc = allreduce_sum(h, z, h->n + tail)) return rc;
+        if (co) dot_coarse_solve(h, z + h->n);
+        launch_zfinish(h->nV, h->P.dup, L, z, h->partC, h->st, nullptr, co);
     }
     return 0;
 }

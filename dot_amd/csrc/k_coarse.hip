@@ -12,6 +12,10 @@
 //   DOT's own loop (dotmi_set_dot_coarse): the same Z, A0 and coarse_solve_kernel in M' = M + Z A0^-1 Z^T; the restriction reads the
 //                       subdomains' padded right-hand sides through a table per padded position (coarse_rtab_kernel at the build,
 //                       coarse_restrict_pad_kernel per application), the prolongation is inside the merge kernels (k_loopvec.hip, COARSE)
+//   sharded handles (DOTMI_FLAG_DOT_COARSE): the table and the restriction over the rank's own subdomains, c in the tail of the vector
+//                       the iteration all-reduces (zeros for the others' subdomains), the solve on every rank behind that collective,
+//                       the prolongation in zfinish_kernel<DEV, true> / the zsum branch of merge_tiles_early_kernel<NT, true>; with a
+//                       sharded Hessian coarse_assemble_kernel sums the pairs whose first subdomain the rank owns, zeros elsewhere
 // Every sum has a fixed shape -- a thread's entries in list order, the lanes by wave_sum's tree, the four waves pairwise -- and
 // nothing is added atomically: two builds and two applications are bit-identical.  The reference has no counterpart.
 #include "k_device.hpp"
@@ -63,7 +67,7 @@ __global__ __launch_bounds__(256) void coarse_assemble_kernel(const int2 *__rest
                                                               const int *__restrict__ adj_idx, const double *__restrict__ Hval,
                                                               const double *__restrict__ wgt, const double *__restrict__ x,
                                                               const double *__restrict__ cen, const int *__restrict__ live,
-                                                              double *__restrict__ pairA)
+                                                              int own0, int own1, double *__restrict__ pairA)
 {
     __shared__ double sm[5 * 36];
     const int p = blockIdx.x;
@@ -71,7 +75,9 @@ __global__ __launch_bounds__(256) void coarse_assemble_kernel(const int2 *__rest
     double acc[36];
 #pragma unroll
     for (int k = 0; k < 36; ++k) acc[k] = 0.0;
-    if (live[st.x] && live[st.y]) {   // (uniform over the workgroup)
+    // [own0, own1): the subdomains whose pairs (s, t), s <= t, this rank assembles -- all of them unless the Hessian refresh is sharded
+    // (DevCoarse::as0); the other pairs' blocks are written as zeros and come with the all-reduce of pairA, H is not read for them
+    if (st.x >= own0 && st.x < own1 && live[st.x] && live[st.y]) {   // (uniform over the workgroup)
         const double cs0 = cen[3 * st.x], cs1 = cen[3 * st.x + 1], cs2 = cen[3 * st.x + 2];
         const double ct0 = cen[3 * st.y], ct1 = cen[3 * st.y + 1], ct2 = cen[3 * st.y + 2];
         for (int e = pairPtr[p] + threadIdx.x; e < pairPtr[p + 1]; e += 256) {
@@ -225,15 +231,16 @@ __global__ __launch_bounds__(256) void coarse_solve_loop_kernel(int nc, int ld, 
 // table holds what its scalar r_a (component a of vertex v) contributes to c_s = Z_s^T r:  w_v r_a to translation a and
 // w_v ((x_v - c_s) x r)_b = w_v (k_b r_a) to the rotations, k = (0, d2, -d1), (-d2, 0, d0), (d1, -d0, 0) for a = 0, 1, 2 and
 // d = x_v - c_s.  An entry is (w_v, k_0, k_1, k_2); all zero on the padding, on fixed vertices and in a dropped subdomain.  Written
-// once per build, behind the centroids
-__global__ __launch_bounds__(256) void coarse_rtab_kernel(int total, int nmax, const int *__restrict__ dofmap,
+// once per build, behind the centroids.  A sharded handle (DOTMI_FLAG_DOT_COARSE) holds the padded ranges of its own subdomains
+// [p0, p0 + nOwn) only: the table has their local index, subdomain p0 + ls in [ls nmax, (ls + 1) nmax)
+__global__ __launch_bounds__(256) void coarse_rtab_kernel(int total, int nmax, int p0, const int *__restrict__ dofmap,
                                                           const double *__restrict__ wgt, const double *__restrict__ x,
                                                           const double *__restrict__ cen, const int *__restrict__ live,
                                                           double4 *__restrict__ rtab)
 {
     const int k = blockIdx.x * 256 + threadIdx.x;
     if (k >= total) return;
-    const int dof = dofmap[k], s = k / nmax;
+    const int dof = dofmap[k], s = p0 + k / nmax;   // (the table and dofmap are indexed by the rank's own subdomains, cen and live by all)
     double4 t = make_double4(0.0, 0.0, 0.0, 0.0);
     if (dof >= 0 && live[s]) {
         const int v = dof / 3, a = dof - 3 * v;
@@ -251,9 +258,11 @@ __global__ __launch_bounds__(256) void coarse_rtab_kernel(int total, int nmax, c
 
 // c_s = Z_s^T r from the padded right-hand sides: one workgroup per subdomain over its own contiguous range, the table, the
 // right-hand side and the position's component (dofmap) side by side.  DEV: a kernel of the device-resident loop, gated like
-// coarse_solve_loop_kernel
+// coarse_solve_loop_kernel.  The grid covers every subdomain and c is indexed by the global one; a workgroup whose subdomain this rank
+// does not own (outside [p0, p0 + nOwn)) writes its six zeros -- on a sharded handle c is the tail of the vector the iteration
+// all-reduces, and the sum over the ranks of (own c_s, zeros elsewhere) is the whole Z^T r, exactly
 template <bool DEV>
-__global__ __launch_bounds__(256) void coarse_restrict_pad_kernel(int nmax, const int *__restrict__ dofmap,
+__global__ __launch_bounds__(256) void coarse_restrict_pad_kernel(int nmax, int p0, int nOwn, const int *__restrict__ dofmap,
                                                                   const double4 *__restrict__ rtab, const double *__restrict__ rpad,
                                                                   double *__restrict__ c, const DevLoop *__restrict__ ctl, int spec)
 {
@@ -261,8 +270,12 @@ __global__ __launch_bounds__(256) void coarse_restrict_pad_kernel(int nmax, cons
     if constexpr (DEV) {
         if (ctl->status != 0 || (ctl->phase != 0 && !spec)) return;
     }
-    const int s = blockIdx.x;
-    const size_t base = (size_t)s * nmax;
+    const int s = blockIdx.x, ls = s - p0;
+    if (ls < 0 || ls >= nOwn) {   // (uniform over the workgroup)
+        if (threadIdx.x < 6) c[6 * s + threadIdx.x] = 0.0;
+        return;
+    }
+    const size_t base = (size_t)ls * nmax;
     double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int k = threadIdx.x; k < nmax; k += 256) {
         const double4 t = rtab[base + k];
@@ -336,7 +349,7 @@ void launch_coarse_assemble(const DevCoarse &C, const DevMesh &M, const double *
 {
     hipLaunchKernelGGL(coarse_assemble_kernel, dim3(C.nPairs), dim3(256), 0, st, (const int2 *)C.pair, (const int *)C.pairPtr,
                        (const int *)C.pairBlk, (const int *)M.blk_row, (const int *)M.adj_idx, Hval, (const double *)C.wgt,
-                       (const double *)C.xf, (const double *)C.cen, (const int *)C.live, C.pairA);
+                       (const double *)C.xf, (const double *)C.cen, (const int *)C.live, C.as0, C.as1, C.pairA);
 }
 void launch_coarse_fill(const DevCoarse &C, hipStream_t st)
 {
@@ -348,9 +361,9 @@ void launch_coarse_restrict(const DevCoarse &C, const double *r, hipStream_t st)
     hipLaunchKernelGGL(coarse_restrict_kernel, dim3(C.nParts), dim3(256), 0, st, (const int *)C.svPtr, (const int *)C.svIdx,
                        (const double *)C.wgt, (const double *)C.xf, (const double *)C.cen, (const int *)C.live, r, C.c);
 }
-void launch_coarse_solve(const DevCoarse &C, hipStream_t st)
+void launch_coarse_solve(const DevCoarse &C, hipStream_t st, const double *c)
 {
-    hipLaunchKernelGGL(coarse_solve_kernel, dim3((C.nc + 63) / 64), dim3(256), 0, st, C.nc, C.ncp, (const double *)C.W, (const double *)C.c,
+    hipLaunchKernelGGL(coarse_solve_kernel, dim3((C.nc + 63) / 64), dim3(256), 0, st, C.nc, C.ncp, (const double *)C.W, c ? c : (const double *)C.c,
                        C.y);
 }
 void launch_coarse_prolong(const DevCoarse &C, int nV, const double *isd, double *zsum, hipStream_t st)
@@ -360,23 +373,25 @@ void launch_coarse_prolong(const DevCoarse &C, int nV, const double *isd, double
 }
 void launch_coarse_rtab(const DevCoarse &C, hipStream_t st)
 {
-    const int total = C.nParts * C.nmax;
-    hipLaunchKernelGGL(coarse_rtab_kernel, dim3((total + 255) / 256), dim3(256), 0, st, total, C.nmax, C.dofmap, (const double *)C.wgt,
+    const int total = C.nOwn * C.nmax;
+    if (total == 0) return;   // (a rank without subdomains)
+    hipLaunchKernelGGL(coarse_rtab_kernel, dim3((total + 255) / 256), dim3(256), 0, st, total, C.nmax, C.p0, C.dofmap, (const double *)C.wgt,
                        (const double *)C.xf, (const double *)C.cen, (const int *)C.live, C.rtab);
 }
-void launch_coarse_restrict_pad(const DevCoarse &C, const double *rpad, hipStream_t st, const DevLoop *ctl, int spec)
+void launch_coarse_restrict_pad(const DevCoarse &C, const double *rpad, hipStream_t st, const DevLoop *ctl, int spec, double *c)
 {
+    if (!c) c = C.c;
     if (ctl)
-        hipLaunchKernelGGL(coarse_restrict_pad_kernel<true>, dim3(C.nParts), dim3(256), 0, st, C.nmax, C.dofmap, (const double4 *)C.rtab, rpad,
-                           C.c, ctl, spec);
+        hipLaunchKernelGGL(coarse_restrict_pad_kernel<true>, dim3(C.nParts), dim3(256), 0, st, C.nmax, C.p0, C.nOwn, C.dofmap,
+                           (const double4 *)C.rtab, rpad, c, ctl, spec);
     else
-        hipLaunchKernelGGL(coarse_restrict_pad_kernel<false>, dim3(C.nParts), dim3(256), 0, st, C.nmax, C.dofmap, (const double4 *)C.rtab, rpad,
-                           C.c, ctl, spec);
+        hipLaunchKernelGGL(coarse_restrict_pad_kernel<false>, dim3(C.nParts), dim3(256), 0, st, C.nmax, C.p0, C.nOwn, C.dofmap,
+                           (const double4 *)C.rtab, rpad, c, ctl, spec);
 }
-void launch_coarse_solve_loop(const DevCoarse &C, hipStream_t st, const DevLoop *ctl, int spec)
+void launch_coarse_solve_loop(const DevCoarse &C, hipStream_t st, const DevLoop *ctl, int spec, const double *c)
 {
     hipLaunchKernelGGL(coarse_solve_loop_kernel, dim3((C.nc + 63) / 64), dim3(256), 0, st, C.nc, C.ncp, (const double *)C.W,
-                       (const double *)C.c, C.y, ctl, spec);
+                       c ? c : (const double *)C.c, C.y, ctl, spec);
 }
 void launch_coarse_scale(int n, const double *a, const double *isd, double *out, hipStream_t st)
 {

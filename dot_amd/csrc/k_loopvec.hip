@@ -1061,14 +1061,22 @@ void launch_merge(const DevMesh &M, const DevParts &P, const LbfgsArgs &L, doubl
 
 // Sharded subdomains: z holds the all-reduced SUM over every subdomain; z_v /= dup_v and the partial dots c_i = y_i . z,
 // i.e. the second half of merge_kernel after the collective (same vertex loop and partial layout).
-template <bool DEV>
+// COARSE (DOTMI_FLAG_DOT_COARSE): + (Z y)_v behind the division and in front of the dots, as merge_kernel<DEV, true> forms it -- y from
+// the solve that ran behind the collective on the summed tail of z
+template <bool DEV, bool COARSE = false>
 __global__ __launch_bounds__(256) void zfinish_kernel(int nV, const int *__restrict__ dup, LbfgsArgs L,
                                                       double *__restrict__ z, double *__restrict__ partials,
-                                                      const DevLoop *__restrict__ ctl)
+                                                      const DevLoop *__restrict__ ctl, MergeCoarse<COARSE> co)
 {
     __shared__ double sm[4 * RED_K];
     if constexpr (DEV) {
         if (ctl->status != 0 || ctl->phase != 0) return;
+    }
+    double *ysh = nullptr;
+    if constexpr (COARSE) {
+        __shared__ double ybuf[COARSE_NC_MAX];
+        ysh = ybuf;
+        coarse_load_y(co, ysh);
     }
     const LbfgsArgs &Lr = [&]() -> const LbfgsArgs & {
         if constexpr (DEV) return ctl->L;
@@ -1085,6 +1093,13 @@ __global__ __launch_bounds__(256) void zfinish_kernel(int nV, const int *__restr
             z0 /= d;
             z1 /= d;
             z2 /= d;
+        }
+        if constexpr (COARSE) {
+            z0 += coarse_term(co, ysh, v, 0);
+            z1 += coarse_term(co, ysh, v, 1);
+            z2 += coarse_term(co, ysh, v, 2);
+        }
+        if (COARSE || d > 1) {
             z[3 * v] = z0;
             z[3 * v + 1] = z1;
             z[3 * v + 2] = z2;
@@ -1100,10 +1115,18 @@ __global__ __launch_bounds__(256) void zfinish_kernel(int nV, const int *__restr
 }
 
 void launch_zfinish(int nV, const int *dup, const LbfgsArgs &L, double *z, double *partials, hipStream_t st,
-                    const DevLoop *ctl)
+                    const DevLoop *ctl, const CoarseMerge *co)
 {
-    if (ctl) hipLaunchKernelGGL(zfinish_kernel<true>, dim3(NB_RED), dim3(256), 0, st, nV, dup, L, z, partials, ctl);
-    else hipLaunchKernelGGL(zfinish_kernel<false>, dim3(NB_RED), dim3(256), 0, st, nV, dup, L, z, partials, ctl);
+#define DOTMI_ZFINISH(DEV, COARSE, ...)                                                                                                 \
+    hipLaunchKernelGGL((zfinish_kernel<DEV, COARSE>), dim3(NB_RED), dim3(256), 0, st, nV, dup, L, z, partials, ctl, __VA_ARGS__)
+    if (ctl) {
+        if (co) DOTMI_ZFINISH(true, true, merge_coarse(co));
+        else DOTMI_ZFINISH(true, false, MergeCoarse<false>());
+    } else {
+        if (co) DOTMI_ZFINISH(false, true, merge_coarse(co));
+        else DOTMI_ZFINISH(false, false, MergeCoarse<false>());
+    }
+#undef DOTMI_ZFINISH
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -30,6 +30,7 @@ FLAG_OWNER_EXCHANGE = 256
 FLAG_LBFGS_PD = 512
 FLAG_LBFGS_HI = 1024
 FLAG_NEWTON_PCG = 2048
+FLAG_DOT_COARSE = 4096   # the coarse term of setDotCoarse(1) from create on; the only way to it on a sharded handle
 
 
 class Mesh(C.Structure):

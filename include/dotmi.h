@@ -186,9 +186,21 @@ enum {
                                      * stats.backsolve_launches = block-solve applications (the CG iterations of the step's solves).
                                      * Host-driven loop, single GPU: not with world > 1, FORCE_DIST, OWNER_EXCHANGE, GSDD, NEWTON,
                                      * LBFGS_PD, LBFGS_HI, ASYNC_REFRESH or a vpart. */
+#define DOTMI_FLAG_DOT_COARSE 4096   /* the rigid-mode coarse term of dotmi_set_dot_coarse, M' = M + Z A0^-1 Z^T, from create on.  One rank
+                                     * without FORCE_DIST: dotmi_create followed by dotmi_set_dot_coarse(h, 1); the handle can be toggled
+                                     * afterwards.  world > 1 or FORCE_DIST: the only way in, and fixed for the life of the handle -- the
+                                     * term changes the payload of a collective, so every rank must pass the flag or none (the setter
+                                     * keeps refusing such handles).  There c = Z^T r of a rank's own subdomains rides in the nc = 6 nParts
+                                     * doubles behind the n of the one vector the iteration all-reduces anyway (no collective is added),
+                                     * every rank solves A0 y = c redundantly behind the collective, and A0 is built on every rank behind
+                                     * every refresh -- with a sharded Hessian refresh through one more all-reduce of 36 doubles per
+                                     * coupled pair of subdomains (DESIGN.md sections 6 and 9).  dotmi_dot_coarse_info and
+                                     * dotmi_pcg_coarse_matrix (the whole A0 on every rank) work on such a handle.  dotmi_create fails
+                                     * with DOTMI_E_INVALID and a message for the flag with OWNER_EXCHANGE, GSDD, NEWTON, NEWTON_PCG,
+                                     * LBFGS_PD, LBFGS_HI, ASYNC_REFRESH, a vpart, or more than 256 subdomains. */
 
 typedef struct {
-    int32_t iters;        /* L-BFGS iterations (innerIterAmt delta, DOTTimeStepper.cpp:338) */
+    int32_t iters;       /* L-BFGS iterations (innerIterAmt delta, DOTTimeStepper.cpp:338) */
     int32_t ls_halvings;  /* numOfLineSearch delta (Optimizer.cpp:816) */
     int32_t energy_evals;
     int32_t status;       /* 0 / 2 */
@@ -510,7 +522,7 @@ int dotmi_pcg_apply_precond(dotmi_handle *h, const double *r, double *w);
  * successful build: the step runs on M, the handle is not poisoned.  A step with the mode on does not take the unit step
  * speculatively (DOTMI_SPEC_STEP).  DOTMI_E_INVALID with a message on a handle of more than one rank, with DOTMI_FLAG_FORCE_DIST,
  * _OWNER_EXCHANGE, _GSDD, _NEWTON, _NEWTON_PCG, _LBFGS_PD, _LBFGS_HI or _ASYNC_REFRESH, on a vpart handle, for any other mode, and
- * above 256 subdomains. */
+ * above 256 subdomains.  (A sharded handle takes the term at create: DOTMI_FLAG_DOT_COARSE.) */
 int dotmi_set_dot_coarse(dotmi_handle *h, int32_t mode);
 /* *dim = 6 nParts with the mode on, else 0; the subdomains the last build dropped; *active = 1 when the applications add the coarse
  * term; the coarse builds since create (both modes); the device time of the last one in ms.  Any pointer may be NULL. */

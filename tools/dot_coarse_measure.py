@@ -6,6 +6,11 @@
                                                                           build beside ms_factor
   python tools/dot_coarse_measure.py kernels <workload> <mode> [frames]   the same steps with the mode 0 / 1, to run under
                                                                           `rocprofv3 --kernel-trace --stats`
+  python tools/dot_coarse_measure.py sharded <workload> [frames] [reps] [off]
+                                                                          `steps` on one rank under DOTMI_FLAG_FORCE_DIST, without and
+                                                                          with DOTMI_FLAG_DOT_COARSE (profiles/dot_coarse_sharded.txt);
+                                                                          `off`: the rows without the flag only (an older library
+                                                                          ignores the bit)
 A library without the entries (DOTMI_LIBRARY pointing at an older build) gives the mode-off rows only."""
 import os
 import sys
@@ -18,10 +23,11 @@ from dot_amd.timestepper import DOTTimeStepper  # noqa: E402
 from dot_amd.workloads import load_workload  # noqa: E402
 
 
-def run(name, mode, frames):
+def run(name, mode, frames, sharded=False):
     sc, ep, n = load_workload(name)
-    ts = DOTTimeStepper(sc, ep, n)
-    if mode:
+    print(f"  ... {name}: a handle with the coarse term {'on' if mode else 'off'}", file=sys.stderr, flush=True)
+    ts = DOTTimeStepper(sc, ep, n, flags=(dl.FLAG_FORCE_DIST | (dl.FLAG_DOT_COARSE if mode else 0)) if sharded else 0)
+    if mode and not sharded:
         ts.setDotCoarse(1)
     rows = []
     for _ in range(frames):
@@ -46,13 +52,15 @@ def main():
         return
     frames = int(sys.argv[3]) if len(sys.argv) > 3 else 6
     reps = int(sys.argv[4]) if len(sys.argv) > 4 else 3
-    modes = (0, 1) if has else (0,)
+    sharded = what == "sharded"
+    modes = (0, 1) if has and not (sharded and "off" in sys.argv[5:]) else (0,)
     res = {m: [] for m in modes}
     for _ in range(reps):                       # off, on, off, on, ...: the two share whatever else the machine is doing
         for m in modes:
-            res[m].append(run(name, m, frames))
+            res[m].append(run(name, m, frames, sharded))
     nV, nT, n = res[0][0][2]
-    print(f"{name}: nV {nV}, nT {nT}, {n} subdomains, {frames} frames x {reps} runs per mode, library {dl.LIB_PATH}")
+    print(f"{name}{', one rank under DOTMI_FLAG_FORCE_DIST' if sharded else ''}: nV {nV}, nT {nT}, {n} subdomains, {frames} frames x {reps} "
+          f"runs per mode, library {dl.LIB_PATH}")
     for m in modes:
         rows0, info, _ = res[m][0]
         same = all([r[:3] for r in rr[0]] == [r[:3] for r in rows0] for rr in res[m])
