@@ -233,6 +233,7 @@ int dotmi_set_pcg_coarse(dotmi_handle *h, int32_t mode)
 {
     if (!h) return DOTMI_E_INVALID;
     const char *why = pcg_refusal(h);
+    if (!why && h->dist) why = "single-rank handles only (the subdomains of this one are sharded: its PCG has no coarse space)";
     if (!why && !h->vpart.empty()) why = "the subdomains of this handle are vertex sets (vpart), the coarse plan works on an element partition";
     if (why) {
         h->err = std::string("dotmi_set_pcg_coarse: ") + why;
@@ -347,7 +348,9 @@ int dotmi_pcg_apply_precond(dotmi_handle *h, const double *r, double *w)
         h->err = "dotmi_pcg_apply_precond: r and w must be given";
         return DOTMI_E_INVALID;
     }
-    if (const char *why = pcg_refusal(h)) {
+    const char *why = pcg_refusal(h);
+    if (!why && h->dist) why = "single-rank handles only (the subdomains of this one are sharded)";
+    if (why) {
         h->err = std::string("dotmi_pcg_apply_precond: ") + why;
         return DOTMI_E_INVALID;
     }

@@ -848,6 +848,25 @@ static int take_arguments(dotmi_handle *h, const dotmi_mesh *mesh, const dotmi_p
             return DOTMI_E_INVALID;
         }
     }
+    if (h->flags & DOTMI_FLAG_NEWTON_PCG_DIST) {
+        // the same step on sharded subdomains (dotmi_pcg.hip): a flag of its own, as it changes which collectives the communicator
+        // carries; on one rank without FORCE_DIST it is DOTMI_FLAG_NEWTON_PCG
+        const char *why = (h->flags & DOTMI_FLAG_OWNER_EXCHANGE) ? "not with DOTMI_FLAG_OWNER_EXCHANGE (the vectors of the recurrences are replicated)"
+                          : (h->flags & DOTMI_FLAG_GSDD)         ? "not with DOTMI_FLAG_GSDD (a GSDD handle solves one subdomain at a time)"
+                          : (h->flags & DOTMI_FLAG_NEWTON)       ? "not with DOTMI_FLAG_NEWTON (a Newton handle factorises H as one subdomain)"
+                          : (h->flags & DOTMI_FLAG_LBFGS_PD)     ? "not with DOTMI_FLAG_LBFGS_PD (no Hessian block solve)"
+                          : (h->flags & DOTMI_FLAG_LBFGS_HI)     ? "not with DOTMI_FLAG_LBFGS_HI (no Hessian block solve)"
+                          : (h->flags & DOTMI_FLAG_ASYNC_REFRESH)
+                              ? "not with DOTMI_FLAG_ASYNC_REFRESH (a Newton iteration factorises at its own iterate)"
+                          : (h->flags & DOTMI_FLAG_DOT_COARSE) ? "not with DOTMI_FLAG_DOT_COARSE (the sharded PCG has no coarse space)"
+                          : mesh->vpart                        ? "not with a vertex partition (vpart): it is single-GPU only"
+                                                               : nullptr;
+        if (why) {
+            h->err = std::string("DOTMI_FLAG_NEWTON_PCG_DIST: ") + why;
+            return DOTMI_E_INVALID;
+        }
+        h->newtonPcg = true;
+    }
     if (h->hi) {
         const int bad = DOTMI_FLAG_FORCE_DIST | DOTMI_FLAG_OWNER_EXCHANGE | DOTMI_FLAG_GSDD | DOTMI_FLAG_NEWTON | DOTMI_FLAG_LBFGS_PD |
                         DOTMI_FLAG_ASYNC_REFRESH;
@@ -921,8 +940,9 @@ static int take_arguments(dotmi_handle *h, const dotmi_mesh *mesh, const dotmi_p
 static int choose_loop_form(dotmi_handle *h)
 {
     h->gsdd = (h->flags & DOTMI_FLAG_GSDD) != 0;
-    h->newton = (h->flags & (DOTMI_FLAG_NEWTON | DOTMI_FLAG_NEWTON_PCG)) != 0;   // (Newton-PCG: the same loop, dotmi_pcg.hip for the solve)
-    if (h->newton && (h->dist || h->gsdd)) {
+    h->newton = (h->flags & (DOTMI_FLAG_NEWTON | DOTMI_FLAG_NEWTON_PCG | DOTMI_FLAG_NEWTON_PCG_DIST)) != 0;   // (Newton-PCG: the same loop, dotmi_pcg.hip for the solve)
+    // (DOTMI_FLAG_NEWTON_PCG_DIST: the one Newton loop a sharded handle runs -- refactor, trial and backtrack have their sharded branches)
+    if (h->newton && ((h->dist && !(h->flags & DOTMI_FLAG_NEWTON_PCG_DIST)) || h->gsdd)) {
         h->err = "DOTMI_FLAG_NEWTON: single GPU, not together with DOTMI_FLAG_GSDD";
         return DOTMI_E_INVALID;
     }
@@ -952,7 +972,7 @@ static int choose_loop_form(dotmi_handle *h)
     // the fixed-corotational SVD the doubled element work costs what the saved launch gives -- bunny5K 1.656 -> 1.696 ms, measured)
     if (h->earlyBs && !h->dist && h->world == 1 && h->tune.fuseStep && h->tune.fuseDir && h->tune.vertexPatches != 0 &&
         (h->mat == DOTMI_ENERGY_SNH || h->tune.vertexPatches > 0) &&
-        h->P.ntiles - h->P.ntilesWide + h->P.nquad > 0 && !(h->flags & (DOTMI_FLAG_GSDD | DOTMI_FLAG_NEWTON | DOTMI_FLAG_NEWTON_PCG | DOTMI_FLAG_HOST_LOOP))) {
+        h->P.ntiles - h->P.ntilesWide + h->P.nquad > 0 && !(h->flags & (DOTMI_FLAG_GSDD | DOTMI_FLAG_NEWTON | DOTMI_FLAG_NEWTON_PCG | DOTMI_FLAG_NEWTON_PCG_DIST | DOTMI_FLAG_HOST_LOOP))) {
         const HostVPatches HV = build_vpatches(h->nV, h->nT, h->T.data(), h->Xrest.data(), 512, 85);
         // (the kernel's static LDS counts against the 64 KB of a workgroup too)
         // the records are chosen per handle, only where their 6 PO doubles still fit: a mesh whose patches fit without them keeps

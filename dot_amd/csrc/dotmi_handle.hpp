@@ -238,8 +238,9 @@ struct dotmi_handle {
     double icShift = 0.0;
     int icAttempts = 0;
     // DOTMI_FLAG_NEWTON_PCG: `newton` with the PCG of dotmi_pcg.hip in place of the single block-solve application, any number of
-    // subdomains.  The PCG's state exists on every single-rank handle with H and the block solve (dotmi_solve_hessian): isd from
-    // create, the vectors from the first solve; its iterate u is the handle's p
+    // subdomains; DOTMI_FLAG_NEWTON_PCG_DIST: the same on sharded subdomains.  The PCG's state exists on every handle with H and the
+    // block solve (dotmi_solve_hessian): isd from create, the vectors (and the sharded rows' packet) from the first solve; its iterate
+    // u is the handle's p
     bool newtonPcg = false;
     DevPcg pcg;
     double *h_pcg = nullptr;                   // pinned: PCG_READBACK doubles, the records and the |r|^2 partials of a batch's end

@@ -583,11 +583,15 @@ struct DevPcg {
     double *partA = nullptr, *partB = nullptr;   // their row-major twins (NB_RED x RED_K)
     double *isd = nullptr;       // nV: 1 / sqrt(dup)
     double *r = nullptr, *d = nullptr, *Hd = nullptr, *w = nullptr, *s = nullptr;   // 3 nV each, allocated by the first solve
+    double *pkt = nullptr;       // sharded Hessian rows: the packet [s (3 nV) | gamma | delta] the ranks sum (first solve; null otherwise)
 };
 constexpr int PCG_READBACK = 2 * (int)(sizeof(PcgRec) / sizeof(double)) + 2 * NB_RED;
 void launch_pcg_init(const DevPcg &C, int n, const double *b, double *u, double *q, hipStream_t st);
 void launch_pcg_spmv(const DevMesh &M, const DevPcg &C, const double *Hval, const double *zsum, int it, hipStream_t st);
 void launch_pcg_update(const DevPcg &C, int n, double *u, double *q, int it, double rel_tol, hipStream_t st);
+// sharded Hessian rows: w whole, s and the gamma / delta partials on the rows [v0, v1) into C.pkt / partA; the update that reads the summed packet
+void launch_pcg_spmv_rows(const DevMesh &M, const DevPcg &C, const double *Hval, const double *zsum, int v0, int v1, int it, hipStream_t st);
+void launch_pcg_update_packet(const DevPcg &C, int n, double *u, double *q, int it, double rel_tol, hipStream_t st);
 
 // ---- the rigid-mode coarse space of Newton-PCG's preconditioner (dotmi_set_pcg_coarse; dotmi_coarse.hip / k_coarse.hip; lists:
 // coarse_plan.hpp): M = M_sym + Z A0^-1 Z^T, A0 = Z^T H Z, six columns of Z per subdomain -------------------------------------------

@@ -1,9 +1,10 @@
 // dotmi_pcg.hip -- Newton-PCG: a linear solve with the global projected Hessian, H u = b, by conjugate gradients preconditioned with
 // the symmetric scaling of DOT's block solve (kernels and recurrences: k_pcg.hip).  It costs the subdomain factorisation the handle
 // already has plus one streaming block-solve application per iteration, so it scales like a DOT step where the reference's Newton
-// (one subdomain, a factor of the whole mesh per iteration) does not.  dotmi_solve_hessian exposes the solve on every single-rank
-// handle that has both H and the block solve; DOTMI_FLAG_NEWTON_PCG puts it into run_newton_loop (dotmi_loop.hip) in place of the
-// single application.  The reference has no counterpart (its Newton is Optimizer::solve_oneStep on CHOLMOD, Optimizer.cpp:703-749).
+// (one subdomain, a factor of the whole mesh per iteration) does not.  dotmi_solve_hessian exposes the solve on every handle that
+// has both H and the block solve; DOTMI_FLAG_NEWTON_PCG puts it into run_newton_loop (dotmi_loop.hip) in place of the single
+// application, DOTMI_FLAG_NEWTON_PCG_DIST does so on sharded subdomains (pcg_iteration below has the collectives; DESIGN.md sections
+// 6 and 9).  The reference has no counterpart (its Newton is Optimizer::solve_oneStep on CHOLMOD, Optimizer.cpp:703-749).
 #include "dotmi_handle.hpp"
 
 namespace dotmi {
@@ -30,10 +31,83 @@ static int pcg_alloc(dotmi_handle *h)
     double **vecs[] = {&C.r, &C.d, &C.Hd, &C.w, &C.s};
     for (double **pp : vecs)
         if (int rc = dalloc(h, pp, (size_t)h->n)) return rc;
+    if (h->shardHess) {   // the packet [s | gamma | delta] of the sharded rows' second collective
+        if (int rc = dalloc(h, &C.pkt, (size_t)h->n + 2)) return rc;
+        HIPCHECK(h, hipMemsetAsync(C.pkt, 0, sizeof(double) * ((size_t)h->n + 2), h->st));
+    }
     HIPCHECK(h, hipHostMalloc((void **)&h->h_pcg, sizeof(double) * PCG_READBACK));
     HIPCHECK(h, hipMemsetAsync(blk, 0, sizeof(double) * PCG_READBACK, h->st));
     C.partBT = blk + 2 * (sizeof(PcgRec) / sizeof(double));
     C.rec = (PcgRec *)blk;
+    return 0;
+}
+
+// CG iteration k.  One rank: four launches.  Sharded subdomains (h->dist): the block solves and the merge run over the rank's own
+// subdomains and leave its share of zsum = S q in h->z; one all-reduce of n doubles makes zsum whole, and with a replicated Hessian
+// the two kernels then run unchanged and redundantly on replicated vectors.  With sharded Hessian rows a rank multiplies its rows
+// [v0, v1) only: pcg_spmv_rows_kernel leaves s on them (zeros elsewhere) in the packet [s (n) | gamma | delta], reduce_rows_kernel
+// puts the rank's two scalars into its tail (as reduce_step_dots does), a second all-reduce of n + 2 doubles sums it and
+// pcg_update_kernel<true> reads s and the scalars from it.  gamma, delta, |r|^2, the verdict and u are functions of all-reduced data
+// only: bit-identical on every rank.  The collectives are issued whatever the record says -- a gated kernel returns at once and the
+// payload is scratch -- so every rank issues the same sequence (the rule of the DOT slots, dotmi_devloop.hip).
+static int pcg_iteration(dotmi_handle *h, bool coarse, int k, double rel_tol)
+{
+    const DevPcg &C = h->pcg;
+    LbfgsArgs L0;
+    memset(&L0, 0, sizeof(L0));
+    const Bracket br = backsolve_bracket(h);
+    if (coarse) coarse_restrict_solve(h, C.r);                          // y = A0^-1 Z^T r (needs nothing of the block solve)
+    launch_gemv(h->P, h->q, h->st, nullptr, br.ev0, br.ev1);           // the block solves of q = r (.) isd
+    launch_merge(h->M, h->P, L0, h->z, h->partC, 0, h->st);             // zsum = S q: no division, no dots
+    if (coarse) coarse_prolong(h, h->z);                                // zsum += (Z y) / isd: w = M_sym r + Z y
+    if (h->dist)
+        if (int rc = allreduce_sum(h, h->z, (size_t)h->n)) return rc;
+    if (!h->shardHess) {
+        launch_pcg_spmv(h->M, C, h->Hval, h->z, k, h->st);
+        launch_pcg_update(C, h->n, h->p, h->q, k, rel_tol, h->st);
+        return 0;
+    }
+    launch_pcg_spmv_rows(h->M, C, h->Hval, h->z, h->v0, h->v1, k, h->st);
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(64), 0, h->st, C.partA, NB_RED, RED_K, 2, 0.0, 0.0, 0, C.pkt + h->n);
+    if (int rc = allreduce_sum(h, C.pkt, (size_t)h->n + 2)) return rc;
+    launch_pcg_update_packet(C, h->n, h->p, h->q, k, rel_tol, h->st);
+    return 0;
+}
+
+// world > 1, after a batch: every rank takes the record's (state, iter, rr, bb) and the batch's last |r|^2 from rank 0 and the ranks
+// check that they had the same state and iteration count -- one collective of 9 doubles: rank 0's five values (zeros from the
+// others: a broadcast), every rank's (state, iter) and their squares.  The ranks agree exactly when the variance
+// vanishes, world * sum(v^2) == (sum v)^2 (small integers, exact in FP64): the test of enqueue_batches (dotmi_devloop.hip), taken on
+// reduced data only, so ranks that disagree fail together instead of one of them waiting in the next all-reduce.
+static int pcg_agree(dotmi_handle *h, int *state, int *iter, double *rr, double *bb, double *rrLast)
+{
+    if (h->world <= 1) return 0;
+    const double mine[2] = {(double)*state, (double)*iter};
+    double red[9] = {0.0, 0.0, 0.0, 0.0, 0.0, mine[0], mine[1], mine[0] * mine[0], mine[1] * mine[1]};
+    if (h->rank == 0) {
+        red[0] = mine[0];
+        red[1] = mine[1];
+        red[2] = *rr;
+        red[3] = *bb;
+        red[4] = *rrLast;
+    }
+    HIPCHECK(h, hipMemcpyAsync(h->ctrlDev, red, sizeof(red), hipMemcpyHostToDevice, h->st));
+    if (int rc = allreduce_sum(h, h->ctrlDev, 9)) return rc;
+    HIPCHECK(h, hipMemcpyAsync(red, h->ctrlDev, sizeof(red), hipMemcpyDeviceToHost, h->st));
+    HIPCHECK(h, hipStreamSynchronize(h->st));
+    const double w = (double)h->world;
+    if (w * red[7] != red[5] * red[5] || w * red[8] != red[6] * red[6]) {
+        h->err = "the ranks left a batch of PCG iterations in different states (this rank: state " + std::to_string(*state) + " after " +
+                 std::to_string(*iter) + " iterations; sum over " + std::to_string(h->world) + " ranks: " +
+                 std::to_string((long long)red[5]) + " / " + std::to_string((long long)red[6]) + ")";
+        h->poisoned = true;
+        return DOTMI_E_DEVICE;
+    }
+    *state = (int)red[0];
+    *iter = (int)red[1];
+    *rr = red[2];
+    *bb = red[3];
+    *rrLast = red[4];
     return 0;
 }
 
@@ -42,6 +116,8 @@ static int pcg_alloc(dotmi_handle *h)
 // convergence and breakdown for every iteration but the batch's last, whose |r|^2 the host sums in the same order.  An iteration
 // enqueued behind the deciding one finds the ended record and leaves u alone; its block solve and merge -- the existing launches,
 // unchanged -- run on a right-hand side nobody reads.
+// Sharded subdomains: b, like every vector of the recurrences, is replicated; pcg_iteration has the collectives of an iteration and
+// pcg_agree what the ranks exchange after a batch.
 // returns 0 converged, 2 cap or breakdown (u is the last iterate: every CG iterate from zero is a descent direction), < 0 error
 int pcg_solve(dotmi_handle *h, const double *b, double rel_tol, int max_iter, int check_every, int *iters, double *rel_res)
 {
@@ -50,8 +126,6 @@ int pcg_solve(dotmi_handle *h, const double *b, double rel_tol, int max_iter, in
     const bool coarse = h->coarse.mode != 0 && h->coarse.active;
     const DevPcg &C = h->pcg;
     const int n = h->n;
-    LbfgsArgs L0;
-    memset(&L0, 0, sizeof(L0));
     launch_pcg_init(C, n, b, h->p, h->q, h->st);
     int k = 0, state = PCG_RUNNING, done = 0;
     double rr = 0.0, bb = 0.0;
@@ -59,13 +133,7 @@ int pcg_solve(dotmi_handle *h, const double *b, double rel_tol, int max_iter, in
         const int nb = std::min(check_every, max_iter - k);
         for (int j = 0; j < nb; ++j) {
             ++k;
-            const Bracket br = backsolve_bracket(h);
-            if (coarse) coarse_restrict_solve(h, C.r);                          // y = A0^-1 Z^T r (needs nothing of the block solve)
-            launch_gemv(h->P, h->q, h->st, nullptr, br.ev0, br.ev1);           // the block solves of q = r (.) isd
-            launch_merge(h->M, h->P, L0, h->z, h->partC, 0, h->st);             // zsum = S q: no division, no dots
-            if (coarse) coarse_prolong(h, h->z);                                // zsum += (Z y) / isd: w = M_sym r + Z y
-            launch_pcg_spmv(h->M, C, h->Hval, h->z, k, h->st);
-            launch_pcg_update(C, n, h->p, h->q, k, rel_tol, h->st);
+            if (int rc = pcg_iteration(h, coarse, k, rel_tol)) return rc;
         }
         HIPCHECK(h, hipMemcpyAsync(h->h_pcg, C.rec, sizeof(double) * PCG_READBACK, hipMemcpyDeviceToHost, h->st));
         HIPCHECK(h, hipStreamSynchronize(h->st));
@@ -74,13 +142,15 @@ int pcg_solve(dotmi_handle *h, const double *b, double rel_tol, int max_iter, in
         state = rec.state;
         done = rec.iter;
         bb = rec.bb;
+        // iteration k's |r|^2 is in the partials (if it ran, the device would decide on it in iteration k + 1's prologue)
+        const double *col = h->h_pcg + 2 * (sizeof(PcgRec) / sizeof(double)) + (size_t)(k & 1) * NB_RED;
+        double rrLast = chunked_sum(NB_RED, [&](int i) { return col[i]; });
+        if (int rc = pcg_agree(h, &state, &done, &rec.rr, &bb, &rrLast)) return rc;   // (world > 1: rank 0's, or all fail together)
         if (state != PCG_RUNNING) {
             rr = rec.rr;
             break;
         }
-        // iteration k ran: its |r|^2 is in the partials (the device would decide on it in iteration k + 1's prologue)
-        const double *col = h->h_pcg + 2 * (sizeof(PcgRec) / sizeof(double)) + (size_t)(k & 1) * NB_RED;
-        rr = chunked_sum(NB_RED, [&](int i) { return col[i]; });
+        rr = rrLast;
         if (rr <= rel_tol * rel_tol * bb) state = PCG_CONVERGED;
         else if (k >= max_iter) break;
     }
@@ -98,9 +168,9 @@ const char *pcg_refusal(const dotmi_handle *h)
 {
     return h->pd      ? "an LBFGS-PD handle has no Hessian block solve"
            : h->hi    ? "an LBFGS-HI handle has no Hessian block solve"
-           : h->dist  ? "single-rank handles only (the subdomains of this one are sharded)"
-           : h->shardHess ? "the rows of the global Hessian are sharded over the ranks on this handle"
            : h->gsdd  ? "a GSDD handle solves one subdomain at a time"
+           // (owner exchange: its vectors are not replicated, and its refresh leaves the slice [v0, v1) of the SpMV unassembled)
+           : h->owner ? "not on a handle with DOTMI_FLAG_OWNER_EXCHANGE (its vectors are valid on a rank's own vertices only)"
                       : nullptr;
 }
 

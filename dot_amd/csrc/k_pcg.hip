@@ -14,6 +14,10 @@
 // has the partials of |r|^2, gamma and delta together; from then on the kernels of this unit return at once and u stays as it is,
 // so the host may enqueue several iterations between two reads of the record.  Reductions: NB_RED rows through write_partials, summed
 // in chunked_sum's order; no atomics; two solves of one system are bit-identical.
+// Sharded Hessian rows (DOTMI_FLAG_NEWTON_PCG_DIST, dotmi_solve_hessian on such a handle): pcg_spmv_rows_kernel in place of
+// pcg_spmv_kernel -- w whole (pointwise from the already summed zsum), s and the partials of gamma and delta on the rank's rows
+// [v0, v1) only, s into the packet [s (n) | gamma | delta] that the ranks sum -- and pcg_update_kernel<true>, which takes s and the
+// two scalars from the summed packet.
 #include "k_device.hpp"
 
 namespace dotmi {
@@ -78,25 +82,41 @@ __global__ __launch_bounds__(256) void pcg_init_kernel(int n, const double *__re
     }
 }
 
-// w = zsum (.) isd, s = H w on the kernel's rows; partials of gamma = r.w (column 0) and delta = w.s (column 1).  The mapping of
+// w = zsum (.) isd, s = H w on the rows [v0, v1); partials of gamma = r.w (column 0) and delta = w.s (column 1).  The mapping of
 // spmv_dots_kernel (k_loopvec.hip): 8 lanes per block row, SPMV_R rows per lane group and trip with their column loops interleaved,
 // Hval entry-major through hval_idx; the column operand is scaled as it is loaded, so no launch exists only to scale.
-// it: this iteration (1, 2, ...); a solve that has ended (the record of iteration it - 1) leaves at once
-__global__ __launch_bounds__(256) void pcg_spmv_kernel(int nV, const int *__restrict__ adj_ptr, const int *__restrict__ adj_idx,
-                                                       const double *__restrict__ Hval, const double *__restrict__ zsum,
-                                                       const double *__restrict__ isd, const double *__restrict__ r,
-                                                       double *__restrict__ w, double *__restrict__ s, double *__restrict__ partA,
-                                                       double *__restrict__ partAT, const PcgRec *__restrict__ rec, int it)
+// it: this iteration (1, 2, ...); a solve that has ended (the record of iteration it - 1) leaves at once.
+// One body for both kernels below, so that the two mappings cannot drift apart.
+// ROWS = false (pcg_spmv_kernel): every row, [v0, v1) = [0, nV); the rows' lanes write w and s.
+// ROWS = true (pcg_spmv_rows_kernel, a handle whose Hessian rows are sharded): Hval holds the rank's rows [v0, v1) of the product
+// (and those of its subdomains' vertices), so s and the partials are taken over these rows only; s goes into the packet
+// [s (3 nV) | gamma | delta] that one all-reduce sums over the ranks, and the pointwise trips in front of the rows zero the packet
+// outside the slice and write w whole -- it is pointwise from the already summed zsum, the same product the rows' lanes form for
+// their dots, so the bits agree.  An ended solve leaves the packet as it is: it then travels as scratch (every rank issues the same
+// collectives).
+template <bool ROWS>
+__device__ __forceinline__ void pcg_spmv_body(int nV, int v0, int v1, const int *__restrict__ adj_ptr, const int *__restrict__ adj_idx,
+                                              const double *__restrict__ Hval, const double *__restrict__ zsum,
+                                              const double *__restrict__ isd, const double *__restrict__ r, double *__restrict__ w,
+                                              double *__restrict__ s, double *__restrict__ partA, double *__restrict__ partAT,
+                                              const PcgRec *__restrict__ rec, int it, double *sm)
 {
-    __shared__ double sm[4 * RED_K];
     if (rec[(it & 1) ^ 1].state != PCG_RUNNING) return;
+    if constexpr (ROWS) {
+        const int n = 3 * nV, stride = gridDim.x * blockDim.x;
+        for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += stride) {
+            const int v = k / 3;
+            w[k] = zsum[k] * isd[v];
+            if (v < v0 || v >= v1) s[k] = 0.0;
+        }
+    }
     double acc[RED_K];
 #pragma unroll
     for (int j = 0; j < RED_K; ++j) acc[j] = 0.0;
     const int sub = threadIdx.x & 7;
     const int ngroups = gridDim.x * 32;
     constexpr int R = 3;   // (SPMV_R of the direction kernels)
-    for (int vbase = blockIdx.x * 32 + (threadIdx.x >> 3); vbase < nV; vbase += R * ngroups) {
+    for (int vbase = v0 + blockIdx.x * 32 + (threadIdx.x >> 3); vbase < v1; vbase += R * ngroups) {
         double a[R][3], wr[R][3], rr[R][3];
         int kb[R], nk[R], nkmax = 0;
 #pragma unroll
@@ -105,7 +125,7 @@ __global__ __launch_bounds__(256) void pcg_spmv_kernel(int nV, const int *__rest
             kb[u] = nk[u] = 0;
 #pragma unroll
             for (int dd = 0; dd < 3; ++dd) a[u][dd] = wr[u][dd] = rr[u][dd] = 0.0;
-            if (v < nV) {
+            if (v < v1) {
                 kb[u] = adj_ptr[v];
                 nk[u] = adj_ptr[v + 1] - kb[u];
                 // the row's own w and r do not depend on the column loop: requested first
@@ -149,8 +169,10 @@ __global__ __launch_bounds__(256) void pcg_spmv_kernel(int nV, const int *__rest
         for (int u = 0; u < R; ++u) {
             const int v = vbase + u * ngroups;
             const double a0 = group8_sum(a[u][0]), a1 = group8_sum(a[u][1]), a2 = group8_sum(a[u][2]);
-            if (sub == 0 && v < nV) {
-                w[3 * v] = wr[u][0]; w[3 * v + 1] = wr[u][1]; w[3 * v + 2] = wr[u][2];
+            if (sub == 0 && v < v1) {
+                if constexpr (!ROWS) {
+                    w[3 * v] = wr[u][0]; w[3 * v + 1] = wr[u][1]; w[3 * v + 2] = wr[u][2];
+                }
                 s[3 * v] = a0; s[3 * v + 1] = a1; s[3 * v + 2] = a2;
                 acc[0] += rr[u][0] * wr[u][0] + rr[u][1] * wr[u][1] + rr[u][2] * wr[u][2];
                 acc[1] += wr[u][0] * a0 + wr[u][1] * a1 + wr[u][2] * a2;
@@ -160,6 +182,27 @@ __global__ __launch_bounds__(256) void pcg_spmv_kernel(int nV, const int *__rest
     write_partials(acc, 2, partA, sm, partAT);
 }
 
+__global__ __launch_bounds__(256) void pcg_spmv_kernel(int nV, const int *__restrict__ adj_ptr, const int *__restrict__ adj_idx,
+                                                       const double *__restrict__ Hval, const double *__restrict__ zsum,
+                                                       const double *__restrict__ isd, const double *__restrict__ r,
+                                                       double *__restrict__ w, double *__restrict__ s, double *__restrict__ partA,
+                                                       double *__restrict__ partAT, const PcgRec *__restrict__ rec, int it)
+{
+    __shared__ double sm[4 * RED_K];
+    pcg_spmv_body<false>(nV, 0, nV, adj_ptr, adj_idx, Hval, zsum, isd, r, w, s, partA, partAT, rec, it, sm);
+}
+
+__global__ __launch_bounds__(256) void pcg_spmv_rows_kernel(int nV, int v0, int v1, const int *__restrict__ adj_ptr,
+                                                            const int *__restrict__ adj_idx, const double *__restrict__ Hval,
+                                                            const double *__restrict__ zsum, const double *__restrict__ isd,
+                                                            const double *__restrict__ r, double *__restrict__ w,
+                                                            double *__restrict__ pkt, double *__restrict__ partA,
+                                                            double *__restrict__ partAT, const PcgRec *__restrict__ rec, int it)
+{
+    __shared__ double sm[4 * RED_K];
+    pcg_spmv_body<true>(nV, v0, v1, adj_ptr, adj_idx, Hval, zsum, isd, r, w, pkt, partA, partAT, rec, it, sm);
+}
+
 // Iteration `it`.  Prologue (wave 0 of every workgroup, the same arithmetic everywhere): the record of iteration it - 1, the sums of
 // this iteration's gamma and delta and of the last iteration's |r|^2; then the verdict --
 //   the solve had ended before                          -> nothing (workgroup 0 carries the record over to this parity)
@@ -167,6 +210,9 @@ __global__ __launch_bounds__(256) void pcg_spmv_kernel(int nV, const int *__rest
 //   gamma or the denominator of alpha not positive / not finite -> breakdown after it - 1 iterations (nothing is divided by them)
 //   else beta, alpha and the vector updates of iteration `it`, q = r (.) isd for the next block solve, the partials of |r|^2
 // The body's operands of the first trip are requested before the prologue (k_loopvec.hip, build_p_kernel).
+// PACKET (sharded Hessian rows): s is the summed packet [s (n) | gamma | delta] and the two scalars are its tail -- the partAT
+// columns, which hold this rank's rows only, are not read; |r|^2 stays the redundant sum over the replicated r
+template <bool PACKET>
 __global__ __launch_bounds__(256) void pcg_update_kernel(int n, const double *__restrict__ isd, const double *__restrict__ w,
                                                          const double *__restrict__ s, double *__restrict__ u, double *__restrict__ r,
                                                          double *__restrict__ d, double *__restrict__ Hd, double *__restrict__ q,
@@ -191,9 +237,18 @@ __global__ __launch_bounds__(256) void pcg_update_kernel(int n, const double *__
     }
     if (threadIdx.x < 64) {
         const PcgRec prev = rec[par ^ 1];
-        const double *const cols[3] = {partAT, partAT + NB_RED, partBT + (size_t)(par ^ 1) * NB_RED};
         double tot[3];
-        pcg_sum_columns<3>(cols, tot);
+        if constexpr (PACKET) {
+            const double *const cols[1] = {partBT + (size_t)(par ^ 1) * NB_RED};
+            double t1[1];
+            tot[0] = s[n];
+            tot[1] = s[n + 1];
+            pcg_sum_columns<1>(cols, t1);
+            tot[2] = t1[0];
+        } else {
+            const double *const cols[3] = {partAT, partAT + NB_RED, partBT + (size_t)(par ^ 1) * NB_RED};
+            pcg_sum_columns<3>(cols, tot);
+        }
         const double gamma = tot[0], delta = tot[1];
         const double rr = prev.state == PCG_RUNNING ? tot[2] : prev.rr;
         const double bb = prev.state != PCG_RUNNING ? prev.bb : (prev.iter == 0 ? rr : prev.bb);
@@ -269,8 +324,18 @@ void launch_pcg_spmv(const DevMesh &M, const DevPcg &C, const double *Hval, cons
 }
 void launch_pcg_update(const DevPcg &C, int n, double *u, double *q, int it, double rel_tol, hipStream_t st)
 {
-    hipLaunchKernelGGL(pcg_update_kernel, dim3(NB_RED), dim3(256), 0, st, n, (const double *)C.isd, (const double *)C.w,
+    hipLaunchKernelGGL(pcg_update_kernel<false>, dim3(NB_RED), dim3(256), 0, st, n, (const double *)C.isd, (const double *)C.w,
                        (const double *)C.s, u, C.r, C.d, C.Hd, q, (const double *)C.partAT, C.partB, C.partBT, C.rec, it, rel_tol);
+}
+void launch_pcg_spmv_rows(const DevMesh &M, const DevPcg &C, const double *Hval, const double *zsum, int v0, int v1, int it, hipStream_t st)
+{
+    hipLaunchKernelGGL(pcg_spmv_rows_kernel, dim3(NB_RED), dim3(256), 0, st, M.nV, v0, v1, (const int *)M.adj_ptr, (const int *)M.adj_idx,
+                       Hval, zsum, (const double *)C.isd, (const double *)C.r, C.w, C.pkt, C.partA, C.partAT, (const PcgRec *)C.rec, it);
+}
+void launch_pcg_update_packet(const DevPcg &C, int n, double *u, double *q, int it, double rel_tol, hipStream_t st)
+{
+    hipLaunchKernelGGL(pcg_update_kernel<true>, dim3(NB_RED), dim3(256), 0, st, n, (const double *)C.isd, (const double *)C.w,
+                       (const double *)C.pkt, u, C.r, C.d, C.Hd, q, (const double *)C.partAT, C.partB, C.partBT, C.rec, it, rel_tol);
 }
 
 }  // namespace dotmi

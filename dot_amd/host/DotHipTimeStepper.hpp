@@ -57,6 +57,9 @@ struct Options {  // the Config fields the DOT stepper reads (src/Config.hpp)
     // instead of one factor of the whole mesh; partitionAmt / epart as for DOT, unit first step.  The solves' forcing term, iteration
     // cap and iterations per read-back (dotmi_set_pcg)
     bool newtonPCG = false;
+    // the same stepper on sharded subdomains (DOTMI_FLAG_NEWTON_PCG_DIST): with world > 1 and commId, or DOTMI_FLAG_FORCE_DIST in
+    // flags; every rank sets it or none (it adds one collective per CG iteration, two with sharded Hessian rows).  Not with pcgCoarse
+    bool newtonPCGDist = false;
     double pcgRelTol = 1e-3;
     int pcgMaxIter = 500, pcgCheckEvery = 8;
     // the rigid-mode coarse term of those solves' preconditioner (dotmi_set_pcg_coarse): off by default
@@ -130,11 +133,11 @@ public:
         p.world = opt_.world;
         p.comm_id = opt_.commId;
         p.flags = opt_.flags | (opt_.lbfgsPD ? DOTMI_FLAG_LBFGS_PD : 0) | (opt_.lbfgsHI ? DOTMI_FLAG_LBFGS_HI : 0) |
-                  (opt_.newtonPCG ? DOTMI_FLAG_NEWTON_PCG : 0);
+                  (opt_.newtonPCG ? DOTMI_FLAG_NEWTON_PCG : 0) | (opt_.newtonPCGDist ? DOTMI_FLAG_NEWTON_PCG_DIST : 0);
         if (int rc = dotmi_create(&m, &p, x0_.data(), &h_))
             throw std::runtime_error(std::string("dotmi_create: ") + dotmi_last_error(nullptr) + " (" +
                                      std::to_string(rc) + ")");
-        if (opt_.newtonPCG) check(dotmi_set_pcg(h_, opt_.pcgRelTol, opt_.pcgMaxIter, opt_.pcgCheckEvery), "set_pcg");
+        if (opt_.newtonPCG || opt_.newtonPCGDist) check(dotmi_set_pcg(h_, opt_.pcgRelTol, opt_.pcgMaxIter, opt_.pcgCheckEvery), "set_pcg");
         if (opt_.pcgCoarse) check(dotmi_set_pcg_coarse(h_, 1), "set_pcg_coarse");
         if (opt_.dotCoarse) check(dotmi_set_dot_coarse(h_, 1), "set_dot_coarse");
     }

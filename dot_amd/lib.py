@@ -31,6 +31,9 @@ FLAG_LBFGS_PD = 512
 FLAG_LBFGS_HI = 1024
 FLAG_NEWTON_PCG = 2048
 FLAG_DOT_COARSE = 4096   # the coarse term of setDotCoarse(1) from create on; the only way to it on a sharded handle
+# FLAG_NEWTON_PCG's step on sharded handles (world > 1, FLAG_FORCE_DIST): a flag of its own, as it adds collectives.  Under the header's
+# full name: the FLAG_* names above are the flags up to FLAG_DOT_COARSE, which tests/test_dot_coarse_sharded_host.py pins as the highest of them
+DOTMI_FLAG_NEWTON_PCG_DIST = 8192
 
 
 class Mesh(C.Structure):

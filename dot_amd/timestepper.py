@@ -35,7 +35,9 @@ class DOTTimeStepper:
         library then stages its collectives through host memory and calls it instead of RCCL
         (dotmi_params::allreduce) -- e.g. a torch.distributed gloo all_reduce.
         mu, lam: optional per-element Lame parameters, shape (nT,) (dotmi_mesh::mu / ::lambda); either one left out is
-        the constant that the scene's YM and PR give."""
+        the constant that the scene's YM and PR give.
+        flags: _lib.DOTMI_FLAG_NEWTON_PCG_DIST is the Newton-PCG step on sharded handles -- with world / rank and comm_id or the allreduce
+        hook, or _lib.FLAG_FORCE_DIST on one rank; every rank passes it or none (it adds collectives)."""
         L = _lib.load()
         cfg = scene.cfg
         self.scene = scene
@@ -286,7 +288,7 @@ class DOTTimeStepper:
     def solveHessian(self, b, rel_tol: float = 1e-8, max_iter: int = 500):
         """H u = b with the handle's current projected Hessian by conjugate gradients on the subdomain factors (dotmi_solve_hessian)
         -> (u (nV,3), iterations, |r|/|b|).  self.last_solve_status is the call's return value: 0 converged, 2 stopped at max_iter
-        or broke down (u is then the last iterate)."""
+        or broke down (u is then the last iterate).  On world > 1 every rank calls it together with the same b."""
         b = np.ascontiguousarray(b, dtype=np.float64)
         u = np.empty((self.nV, 3))
         it, res = C.c_int32(), C.c_double()
@@ -296,7 +298,7 @@ class DOTTimeStepper:
         return u, it.value, res.value
 
     def setPCG(self, rel_tol: float = 1e-3, max_iter: int = 500, check_every: int = 8):
-        """the solves of a _lib.FLAG_NEWTON_PCG step: forcing term, iteration cap; iterations between two read-backs (dotmi_set_pcg)"""
+        """the solves of a _lib.FLAG_NEWTON_PCG / _NEWTON_PCG_DIST step: forcing term, iteration cap; iterations between two read-backs (dotmi_set_pcg)"""
         self._check(self._L.dotmi_set_pcg(self._h, rel_tol, max_iter, check_every), "set_pcg")
 
     def pcgInfo(self):

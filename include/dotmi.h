@@ -198,6 +198,22 @@ enum {
                                      * dotmi_pcg_coarse_matrix (the whole A0 on every rank) work on such a handle.  dotmi_create fails
                                      * with DOTMI_E_INVALID and a message for the flag with OWNER_EXCHANGE, GSDD, NEWTON, NEWTON_PCG,
                                      * LBFGS_PD, LBFGS_HI, ASYNC_REFRESH, a vpart, or more than 256 subdomains. */
+#define DOTMI_FLAG_NEWTON_PCG_DIST 8192 /* DOTMI_FLAG_NEWTON_PCG's step on handles whose subdomains are sharded: accepted on one rank, with
+                                     * FORCE_DIST and with world > 1 (RCCL or the dotmi_params.allreduce hook), in both sharding modes of
+                                     * the element pass and the refresh.  One rank without FORCE_DIST: exactly DOTMI_FLAG_NEWTON_PCG
+                                     * (bit-identical).  A flag of its own because it changes which collectives the communicator carries:
+                                     * every rank must pass it or none.  Per CG iteration, with a replicated Hessian, one all-reduce of
+                                     * n doubles (the ranks' shares of zsum = S q); with sharded Hessian rows a second one of n + 2
+                                     * doubles, the packet [s = H w on the rank's rows, zeros elsewhere | gamma | delta].  Every
+                                     * collective is issued in every enqueued iteration, whatever the device's verdict; after each batch
+                                     * of check_every iterations the ranks adopt rank 0's (state, iterations, |r|^2, |b|^2) in one
+                                     * collective of 9 doubles and fail together with DOTMI_E_DEVICE when they disagree.  The vectors of
+                                     * the recurrences are replicated, so the scalars, the verdict and p are bit-identical on every rank.
+                                     * dotmi_set_pcg and dotmi_pcg_info as on one rank; dotmi_set_pcg_coarse stays refused on sharded
+                                     * handles.  Over real links its behaviour is unmeasured.  dotmi_create fails
+                                     * with DOTMI_E_INVALID and a message for the flag with OWNER_EXCHANGE, GSDD, NEWTON, LBFGS_PD,
+                                     * LBFGS_HI, ASYNC_REFRESH, DOT_COARSE or a vpart; together with DOTMI_FLAG_NEWTON_PCG that flag's own
+                                     * checks run first. */
 
 typedef struct {
     int32_t iters;       /* L-BFGS iterations (innerIterAmt delta, DOTTimeStepper.cpp:338) */
@@ -481,9 +497,11 @@ int dotmi_ic_factor(dotmi_handle *h, int32_t cap, double *blocks);
  * solves.  b, u: nV*3.  Stops when the recursive residual |r| <= rel_tol |b|, after max_iter iterations, or on breakdown (a
  * non-positive or non-finite r.M r or curvature: NaN or rounding, H and the preconditioner being SPD); *iters = iterations done,
  * *rel_res = |r| / |b| at exit (either may be NULL); b = 0 returns u = 0 after 0 iterations.  Two solves of one system are
- * bit-identical, whatever the read-back interval.  Any single-rank handle that has both H and the block solve (DOT, two-level form,
- * Newton, a vpart); DOTMI_E_INVALID on LBFGS-PD, LBFGS-HI, GSDD and sharded handles, NULL b or u, rel_tol <= 0 or non-finite,
- * max_iter < 1.  Returns 0 converged, 2 cap or breakdown (u is the last iterate), < 0 error. */
+ * bit-identical, whatever the read-back interval.  Any handle that has both H and the block solve (DOT, two-level form, Newton, a
+ * vpart, sharded subdomains in both sharding modes of the refresh -- the collectives of DOTMI_FLAG_NEWTON_PCG_DIST, with or without
+ * that flag); on world > 1 EVERY rank must call it together, with the same b, rel_tol and max_iter, and every rank gets the same
+ * u.  DOTMI_E_INVALID on LBFGS-PD, LBFGS-HI, GSDD and DOTMI_FLAG_OWNER_EXCHANGE handles, NULL b or u, rel_tol <= 0 or non-finite, max_iter < 1.  Returns 0
+ * converged, 2 cap or breakdown (u is the last iterate), < 0 error (DOTMI_E_DEVICE on every rank when the ranks disagree). */
 int dotmi_solve_hessian(dotmi_handle *h, const double *b, double *u, double rel_tol, int32_t max_iter, int32_t *iters,
                         double *rel_res);
 /* the settings of DOTMI_FLAG_NEWTON_PCG's solves (rel_tol = the forcing term eta, max_iter) and, for dotmi_solve_hessian too, the
@@ -500,7 +518,8 @@ int dotmi_pcg_info(const dotmi_handle *h, int64_t *solves, int64_t *iters_total,
  * on rebuilds it with x = the handle's current iterate, frozen together with the centroids until the next build.  A subdomain with
  * fewer than 3 free vertices gets zero columns and an identity block.  If A0 still meets a non-positive pivot (collinear free
  * vertices) the coarse term is off until the next successful build: the solves run on M_sym alone, the handle is not poisoned.
- * DOTMI_E_INVALID on the handles dotmi_solve_hessian refuses and on a vpart handle, for any other mode, and above 256 subdomains
+ * DOTMI_E_INVALID on the handles dotmi_solve_hessian refuses, on sharded handles (world > 1, DOTMI_FLAG_FORCE_DIST: the sharded PCG
+ * has no coarse space) and on a vpart handle, for any other mode, and above 256 subdomains
  * (A0^-1 is applied through a dense inverse factor of dimension 6 nParts <= 1536: a storage choice).  No device work. */
 int dotmi_set_pcg_coarse(dotmi_handle *h, int32_t mode);
 /* *dim = 6 nParts with the mode on, else 0; the subdomains the last build dropped; *active = 1 when the solves add the coarse term
@@ -510,7 +529,7 @@ int dotmi_pcg_coarse_info(const dotmi_handle *h, int32_t *dim, int32_t *dropped_
  * Returns dim (A0 == NULL: only that); cap: room in A0, in doubles; DOTMI_E_INVALID before the first build. */
 int dotmi_pcg_coarse_matrix(dotmi_handle *h, int32_t cap, double *A0);
 /* one application of the preconditioner exactly as the PCG uses it: w = M_sym r, plus Z A0^-1 Z^T r when the coarse term is active
- * (a stale A0 is rebuilt first).  r, w: nV*3.  Refused like dotmi_solve_hessian. */
+ * (a stale A0 is rebuilt first).  r, w: nV*3.  Refused like dotmi_solve_hessian, and on sharded handles. */
 int dotmi_pcg_apply_precond(dotmi_handle *h, const double *r, double *w);
 /* The same rigid-mode coarse term in DOT's own loop (the reference has no counterpart, so iteration counts
  * differ from its: opt-in).  mode 0 = off (the default: every entry runs exactly the launches it runs without this one), 1 = the
