@@ -285,7 +285,7 @@ int dotmi_probe_direction(dotmi_handle *h, const double *x, int32_t m, const dou
         for (int j = 0; j < m; ++j) L.sy[i][j] = dot(S + (size_t)i * n, Y + (size_t)j * n);
         L.ys[i] = L.sy[i][i];
     }
-    two_loop_xi(m, b, L.sy, L.ys, xi);
+    lbfgs_two_loop_xi(m, b, L.sy, L.ys, xi);
     launch_build_q(n, h->g_trial, L, xi, h->q, h->st);
     if (int rc = apply_precond(h, h->q, h->z, L)) return rc;
     launch_build_p(n, h->z, L, h->partC, xi, h->p, h->st);

@@ -750,16 +750,6 @@ LbfgsArgs lbfgs_args(const dotmi_handle *h)
     return L;
 }
 
-int free_slot(const dotmi_handle *h)
-{
-    for (int s = 0; s <= h->hist; ++s) {
-        bool used = false;
-        for (int i = 0; i < h->m; ++i) used |= (h->order[i] == s);
-        if (!used) return s;
-    }
-    return 0;
-}
-
 }  // namespace dotmi
 
 extern "C" {

@@ -147,10 +147,8 @@ static void slot_backsolve(dotmi_handle *h, const Slot &s)
     const double *ctlR = h->owner ? h->partGR : h->partR;   // owner exchange: the statistics rode in the gradient's packet
     const Bracket br = backsolve_bracket(h);
     h->slotTimed.push_back(br.at);
-    CtlArgs ca{h->ctl, s.ctlE, ctlR, h->alpha_dev, h->h_flags, s.nb, h->pairNow ? 2 : 0};
-    (h->pairNow ? (h->vpNow ? launch_gemv_pair_vp : launch_gemv_pair) : h->specNow ? launch_gemv_spec : h->vpNow ? launch_gemv_vp : launch_gemv)(
-        h->P, nullptr, h->st, h->ctl, br.ev0, br.ev1, &ca,
-        (int)h->slotTimed.size() /* the slot's epoch, 1-based */);
+    CtlLaunch ca{{h->ctl, s.ctlE, ctlR, h->alpha_dev, h->h_flags, s.nb, h->pairNow ? 2 : 0}, h->ctlForm};
+    launch_gemv(h->P, nullptr, h->st, h->ctl, br.ev0, br.ev1, &ca, (int)h->slotTimed.size() /* the slot's epoch, 1-based */);
 }
 
 // stage 5, merge: z = u - sum_j xi_j (M y_j) from the tile partials and the cached M y_j (dotmi_set_dot_coarse: u with + Z y, so the
@@ -296,6 +294,8 @@ static void choose_step_forms(dotmi_handle *h)
     // second half of a paired launch is the element pass' energy only -- stiff monkey, ten steps, same box: 15.12 -> 14.17 ms per
     // step (111.8 -> 107.6 us per iteration)
     h->vpNow = h->vpFits && h->earlyNow && !h->dist && !h->specNow && !(h->pairNow && h->tune.vertexPatches < 0);
+    // the controller that understands these slots
+    h->ctlForm = h->pairNow ? (h->vpNow ? CTL_PAIR_VP : CTL_PAIR) : h->specNow ? CTL_SPEC : h->vpNow ? CTL_VP : CTL_PLAIN;
 }
 
 // the loop state of a fresh step, filled in pinned memory and uploaded; returns the slot from which the controller posts progress
@@ -376,7 +376,7 @@ static int step_start_sharded(dotmi_handle *h, int nb)
     launch_build_qpad(h->P, h->g, L0, nullptr, h->st, nullptr);
     const CoarseMerge *co = dot_coarse(h);   // (DOTMI_FLAG_DOT_COARSE, never with the owner exchange: as in slot_merge)
     if (co) dot_coarse_restrict(h, h->zstage + n);
-    CtlArgs ca{h->ctl, h->gstage + n, ctlR, h->alpha_dev, h->h_flags, 1, 1};
+    CtlLaunch ca{{h->ctl, h->gstage + n, ctlR, h->alpha_dev, h->h_flags, 1, 1}, CTL_PLAIN};
     launch_gemv(h->P, nullptr, h->st, h->ctl, nullptr, nullptr, &ca, 1 << 30);
     launch_merge(h->M, h->P, L0, h->zstage, h->partC, 0, h->st, h->ctl, h->held());
     if (!h->owner) {
@@ -436,8 +436,9 @@ static int enqueue_step_start(dotmi_handle *h)
     const CoarseMerge *co = dot_coarse(h);
     if (co && h->dist) dot_coarse_restrict(h, h->zstage + h->n);
     else if (co) dot_coarse_restrict_solve(h);
-    CtlArgs ca{h->ctl, h->partE, h->partR, h->alpha_dev, h->h_flags, nb, 1};
-    (h->vpNow ? launch_gemv_vp : launch_gemv)(h->P, nullptr, h->st, h->ctl, nullptr, nullptr, &ca, 1 << 30);
+    // (no trial to judge yet: the plain controller, which only differs in how many rows of statistics there are)
+    CtlLaunch ca{{h->ctl, h->partE, h->partR, h->alpha_dev, h->h_flags, nb, 1}, h->vpNow ? CTL_VP : CTL_PLAIN};
+    launch_gemv(h->P, nullptr, h->st, h->ctl, nullptr, nullptr, &ca, 1 << 30);
     if (!h->dist) {
         launch_merge_early(h->M, h->P, h->z, h->partC, 1, h->st, h->ctl, nullptr, nullptr, VList(), nullptr, 0, nullptr, h->partCT, co);
     } else {

@@ -188,6 +188,7 @@ struct dotmi_handle {
     bool specNow = false;       // this step's new-direction slots take the unit step speculatively (launch_dirstep)
     const DevPatches &stepPT() const { return specNow ? PTspec : PT; }   // the element patches of the running step
     int specSlots = 0, specRedo = 0;
+    int ctlForm = CTL_PLAIN;    // the controller in the back-solve launch of this step's slots: what pairNow / specNow / vpNow make it
     int prevFirst = 0, prevUnit = 0;   // last step's first trials / of those, the ones whose estimate alpha_0 was the unit step
     int pairState[3] = {1, 1, 1};   // DevLoop::pairCtr, carried from step to step
     double *gstage = nullptr;   // sharded element pass, device loop: [g (n) ; 0 ; E] staging buffer of the gradient all-reduce
@@ -368,7 +369,6 @@ int upload(dotmi_handle *h, T **ptr, const std::vector<T> &v)
 int build_device_mesh(dotmi_handle *h);
 double host_target_gres(const dotmi_handle *h);
 LbfgsArgs lbfgs_args(const dotmi_handle *h);
-int free_slot(const dotmi_handle *h);
 // dotmi_refresh.hip
 int refactor_issue(dotmi_handle *h, const double *x);
 int refactor_finish(dotmi_handle *h, double *ms_hess, double *ms_fact);
@@ -435,7 +435,6 @@ int reduce_step_dots(dotmi_handle *h, const double **spart);
 void stage_energy(dotmi_handle *h, int nb, double *dst);
 GatherArgs gather_args(const dotmi_handle *h);
 ElemVertArgs elem_vertex_args(const dotmi_handle *h);
-void two_loop_xi(int m, const double *b, const double (*sy)[HIST_MAX], const double *ys, double *xi);
 // dotmi_devloop.hip
 int run_device_loop(dotmi_handle *h, LoopOut &r);
 

@@ -2,13 +2,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "lbfgs_history.hpp"   // HIST_MAX
 #include "nd_layout.hpp"
 #include "tile_factor.hpp"
 #include <stdint.h>
 
 namespace dotmi {
 
-constexpr int HIST_MAX = 6;     // L-BFGS pairs kept (reference uses 5, DOTTimeStepper.cpp:45)
 // workgroups of the element pass when the mesh has more patches than that: what is resident at once with the prefetching
 // instantiation's registers (Stable Neo-Hookean 158: three per CU; fixed-corotational with its SVD 190: two) x 256 CUs
 inline int elem_wg_cap(int mat) { return mat == 1 ? 768 : 512; }
@@ -349,7 +349,10 @@ struct VList {
     const int *v = nullptr;
     int n = 0;
 };
-// the controller's operands when it runs as one workgroup of another launch (launch_gemv)
+// the forms of the loop controller (k_loopctl.hpp; the instantiations of backsolve_ctl_kernel): plain, a step with paired trials, a
+// step that takes the unit step speculatively, a step on vertex patches, a step with paired trials on vertex patches
+constexpr int CTL_PLAIN = 0, CTL_PAIR = 1, CTL_SPEC = 2, CTL_VP = 3, CTL_PAIR_VP = 4;
+// the controller's operands when it runs as one workgroup of another launch (launch_gemv): the kernel's argument
 struct CtlArgs {
     DevLoop *ctl;
     const double *partE, *partR, *alpha_dev;
@@ -357,6 +360,12 @@ struct CtlArgs {
     int nbE;
     int init;   // bit 0: the evaluation at the start of the step (nothing to decide yet); bit 1: a step with paired trials -- the
                 // full step's energy partials follow partE at + 2 ELEM_NB_MAX, alpha_dev[1] > 0 marks a paired slot
+};
+// ... and what launch_gemv takes: the operands with the form of the controller that reads them (CTL_*: which instantiation it launches).
+// The form stays out of the kernel's argument: eight bytes more there cost every back-solve launch 0.6 - 0.8 us (bar17K: 44.5 -> 45.2 us)
+struct CtlLaunch {
+    CtlArgs a;
+    int form;
 };
 
 // ---- kernel launchers (k_*.hip) ------------------------------------------------------------------
@@ -427,22 +436,13 @@ void launch_build_q(int n, const double *g, const LbfgsArgs &L, const double *xi
 // subdomain back-solve: psub_s = X_s^T (X_s q[dofmap_s])
 // q == nullptr: P.rpad already holds the right-hand sides (launch_build_qpad); else they are gathered from q first
 // ca: the loop controller runs as workgroup 0 of the (first) launch, beside the tiles, which then ignore the retry phase
-// (the back-solve is speculative: issued on the trial gradient before the controller has accepted the trial)
+// (the back-solve is speculative: issued on the trial gradient before the controller has accepted the trial); ca->form says which
+// controller (CtlLaunch): paired slots (CtlArgs::init bit 1), the unit step taken speculatively (DevLoop::specPartials), statistics in one row
+// per vertex patch (CtlArgs::nbE rows)
 void launch_gemv(const DevParts &P, const double *q, hipStream_t st, const DevLoop *ctl = nullptr,
-                 hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, const CtlArgs *ca = nullptr, int spec = 0);
-// ... the PAIR instantiation: the controller that understands paired slots (CtlArgs::init bit 1)
-void launch_gemv_pair(const DevParts &P, const double *q, hipStream_t st, const DevLoop *ctl = nullptr,
-                      hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, const CtlArgs *ca = nullptr, int spec = 0);
-// ... the controller of a step that takes the unit step speculatively (checks alpha_0 afterwards; DevLoop::specPartials)
-void launch_gemv_spec(const DevParts &P, const double *q, hipStream_t st, const DevLoop *ctl = nullptr,
-                      hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, const CtlArgs *ca = nullptr, int spec = 0);
+                 hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, const CtlLaunch *ca = nullptr, int spec = 0);
 // (a.alpha_min < 0: a PAIRED launch -- twice as many workgroups, the second half the energy of the full step: StepArgs::alpha_min)
 void launch_elem_vertex(const DevVPatches &VP, int mat, const ElemVertArgs &a, hipStream_t st, const DevLoop *ctl);
-void launch_gemv_pair_vp(const DevParts &P, const double *q, hipStream_t st, const DevLoop *ctl = nullptr,
-                         hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, const CtlArgs *ca = nullptr, int spec = 0);
-// ... the controller of a step on vertex patches (k_elemvert.hip): it sums as many statistic rows as there are patches (CtlArgs::nbE)
-void launch_gemv_vp(const DevParts &P, const double *q, hipStream_t st, const DevLoop *ctl = nullptr,
-                    hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, const CtlArgs *ca = nullptr, int spec = 0);
 // the direction kernel and the first trial's element pass at the unit step in one launch of two workgroup populations
 // (k_dirstep.hip): replaces launch_spmv_zp + launch_elem_energy_grad in the slots of a speculating step
 bool dirstep_fits(const DevPatches &PT);   // (meshes of at most 512 patches: every patch a workgroup)

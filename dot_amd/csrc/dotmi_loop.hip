@@ -64,17 +64,6 @@ GatherArgs gather_args(const dotmi_handle *h)
     return a;
 }
 
-// first half of the two-loop recursion on the host's m x m scalars (DOTTimeStepper.cpp:386-404)
-void two_loop_xi(int m, const double *b, const double (*sy)[HIST_MAX], const double *ys, double *xi)
-{
-    for (int i = 0; i < HIST_MAX; ++i) xi[i] = 0.0;
-    for (int i = m - 1; i >= 0; --i) {
-        double sq = -b[i];
-        for (int j = m - 1; j > i; --j) sq -= xi[j] * sy[i][j];
-        xi[i] = sq / ys[i];
-    }
-}
-
 // p = D^-1 sum_s R_s^T W_s R_s q   (DOTTimeStepper.cpp:406-450); leaves y_i.z partials in partC
 // dotmi_set_dot_coarse with an active term: + Z A0^-1 Z^T q -- the restriction from the padded right-hand sides (where launch_gemv has
 // put q, or build_qpad before it) and the coarse solve behind the back-solve, the prolongation inside the merge (sharded subdomains,
@@ -296,39 +285,6 @@ static int run_newton_loop(dotmi_handle *h, LoopOut &r, double *ms_hess, double 
     return 0;
 }
 
-// history update of the host-driven loop (DOTTimeStepper.cpp:474-494) from the statistics R of the accepted trial, whose
-// pair went to `slot`
-static void push_pair(dotmi_handle *h, int slot, const double *R)
-{
-    const double ys_new = R[1], sg_new = R[2];
-    const double *siy = R + 3, *snyj = R + 3 + HIST_MAX, *sig = R + 3 + 2 * HIST_MAX;
-    if (ys_new <= 0.0) {
-        for (int i = 0; i < h->m; ++i) h->b[i] = sig[i];
-        return;
-    }
-    int m = h->m;
-    int off = 0;
-    if (m == h->hist) {  // drop the oldest pair
-        off = 1;
-        for (int i = 0; i + 1 < m; ++i) {
-            h->order[i] = h->order[i + 1];
-            h->ys[i] = h->ys[i + 1];
-            for (int j = 0; j + 1 < m; ++j) h->sy[i][j] = h->sy[i + 1][j + 1];
-        }
-        m -= 1;
-    }
-    for (int i = 0; i < m; ++i) {
-        h->sy[i][m] = siy[i + off];
-        h->sy[m][i] = snyj[i + off];
-        h->b[i] = sig[i + off];
-    }
-    h->order[m] = slot;
-    h->ys[m] = ys_new;
-    h->sy[m][m] = ys_new;
-    h->b[m] = sg_new;
-    h->m = m + 1;
-}
-
 // The host-driven L-BFGS-H loop (DOTMI_FLAG_HOST_LOOP, LBFGS-PD and LBFGS-HI): one stream synchronisation per line-search trial, the
 // two-loop's scalars and the accept / halve / converged decisions on the host.  In the q-based order of the reference
 static int run_host_loop(dotmi_handle *h, LoopOut &r)
@@ -336,9 +292,9 @@ static int run_host_loop(dotmi_handle *h, LoopOut &r)
     const int n = h->n;
     double R[RED_K];
     do {
-        // ---- two-loop, first half (host scalars) + q ------------------------------------------------
+        // ---- two-loop, first half (host scalars, lbfgs_history.hpp) + q -----------------------------
         double xi[HIST_MAX];
-        two_loop_xi(h->m, h->b, h->sy, h->ys, xi);
+        lbfgs_two_loop_xi(h->m, h->b, h->sy, h->ys, xi);
         const LbfgsArgs L = lbfgs_args(h);
         phase_mark(h, -1);
         if (h->pd) {
@@ -371,7 +327,7 @@ static int run_host_loop(dotmi_handle *h, LoopOut &r)
             launch_step_forward(n, h->x, h->p, h->x_trial, spart, 0.0, 1, h->alphaMin, h->alpha_dev, h->h_alpha, h->st);
         }
         phase_mark(h, DOTMI_T_LINESEARCH_OTHER);
-        const int slot = free_slot(h);
+        const int slot = lbfgs_free_slot(h->hist, h->m, h->order);
         double E = 0;
         if (int rc = trial(h, h->x_trial, h->g_trial, 1, L, slot, &E)) return rc;
         double alpha = h->h_alpha[0];
@@ -384,7 +340,8 @@ static int run_host_loop(dotmi_handle *h, LoopOut &r)
         std::swap(h->g, h->g_trial);
         sum_stats(h, RED_K, R);
         r.g2 = R[0];
-        push_pair(h, slot, R);
+        // history update (DOTTimeStepper.cpp:474-494) from the statistics of the accepted trial: y.s, s.g and the three rows
+        lbfgs_push_pair(h->hist, slot, R[1], R[2], R + 3, R + 3 + HIST_MAX, R + 3 + 2 * HIST_MAX, h->m, h->order, h->ys, h->b, h->sy);
         h->log_alpha.push_back(alpha);
         h->log_E.push_back(r.lastE);
         h->log_g2.push_back(r.g2);

@@ -1,466 +1,13 @@
-// k_backsolve.hip -- subdomain back-solve (DOTTimeStepper.cpp:406-431) and the loop controller (Optimizer.cpp:806-833, DOTTimeStepper.cpp:474-494)
+// k_backsolve.hip -- subdomain back-solve (DOTTimeStepper.cpp:406-431) and the kernels that run the loop controller (k_loopctl.hpp):
+// a launch of its own, or workgroup 0 of the back-solve launch
 // (one translation unit per kernel family since round 6: an edit to one family no longer moves the register allocation and
 // scalar loads of the others; every unit is compiled once.  Conventions and the reference map: k_device.hpp)
 #include "k_device.hpp"
+#include "k_loopctl.hpp"
 
 namespace dotmi {
 
-// ------------------------------------------------------------------------------------------------
-// loop controller: what the host loop of dotmi_step does between a trial and the next launch
-// (line search Optimizer.cpp:806-833, history update DOTTimeStepper.cpp:474-494, stopping test
-// Optimizer.cpp:317-330), on the device.  One wavefront; the partial sums are added in block order,
-// the same order the host path uses, so both paths produce the same bits.
-// ------------------------------------------------------------------------------------------------
-// (a device function: the controller is a launch of its own, or workgroup 0 of the back-solve launch -- 256 threads)
-// CTL_PAIR: the controller of a step with paired line-search trials (it understands paired slots: the full step's energy partials
-// in partE2, alpha_dev[1] > 0 marks a paired slot).  CTL_SPEC: the controller of a step whose new-direction slots take the unit
-// step speculatively (k_dirstep.hip): it sums the SpMV partials itself -- the element pass's prologue, the same additions -- and
-// when alpha_0 = clamp(-p.g / p.Hp, alphaMin, 1) is not 1 the slot did not evaluate the reference's first trial: its back-solve is
-// stopped and the next slot evaluates x + alpha_0 p as the first trial it is (phase 1, redo: nothing counted twice).  Template
-// parameters: the plain instantiation compiles those branches away (the pairing until round 5 through a second compilation of the
-// file under -DDOTMI_PAIR_TU).
-// CTL_VP: the controller of a step on vertex patches (k_elemvert.hip): the statistics come in one row per PATCH (nbE rows, like the
-// energy partials) instead of NB_RED rows; summed in chunked_sum's order over that many rows.
-// CTL_PAIR_VP: both -- a step with paired trials on vertex patches.
-constexpr int CTL_PLAIN = 0, CTL_PAIR = 1, CTL_SPEC = 2, CTL_VP = 3, CTL_PAIR_VP = 4;
-template <int CTL>
-__device__ __forceinline__ void loop_control_body(DevLoop *__restrict__ ctl, const double *__restrict__ partE, int nbE,
-                                  const double *__restrict__ partR, const double *__restrict__ alpha_dev,
-                                  int *__restrict__ flags_host, int init, const double *__restrict__ partE2 = nullptr)
-{
-    constexpr bool PAIR = CTL == CTL_PAIR || CTL == CTL_PAIR_VP, SPEC = CTL == CTL_SPEC;
-    constexpr bool VPROWS = CTL == CTL_VP || CTL == CTL_PAIR_VP;   // one row of statistics per patch (nbE rows)
-    static_assert(sizeof(DevLoop) % 8 == 0, "DevLoop is copied as 8-byte words");
-    static_assert(RED_K <= 32, "two passes of 16 columns");
-    __shared__ double chunk[RED_K + 2][SUM_CHUNKS];
-    __shared__ double R[RED_K + 2];
-    __shared__ DevLoop C;  // the state is worked on in LDS: one wide load, one wide store
-    const int t = threadIdx.x;
-    constexpr int NW8 = (int)(sizeof(DevLoop) / 8);
-    {
-        const unsigned long long *src = reinterpret_cast<const unsigned long long *>(ctl);
-        unsigned long long *dst = reinterpret_cast<unsigned long long *>(&C);
-        for (int i = t; i < NW8; i += 256) dst[i] = src[i];
-    }
-    const double alpha_in = *alpha_dev;
-    // SPEC: the partials of p.g and p.Hp, requested with everything else (wave 0; summed below as elem_patch_body's prologue does)
-    double pgv[NB_RED / 64], pHpv[NB_RED / 64];
-    if constexpr (SPEC) {
-        if (t < 64 && !init) {
-            const double *__restrict__ sp = ctl->specPartials;
-#pragma unroll
-            for (int u = 0; u < NB_RED / 64; ++u) {
-                pgv[u] = sp[(size_t)(t + 64 * u) * RED_K];
-                pHpv[u] = sp[(size_t)(t + 64 * u) * RED_K + 1];
-            }
-        }
-    }
-    const double alpha_full = (PAIR && partE2 && !init) ? alpha_dev[1] : 0.0;   // > 0: a paired slot (elem_patch_kernel)
-    __shared__ double chunk2[PAIR ? 2 : 1][SUM_CHUNKS];
-    // chunked_sum() order (dotmi_internal.hpp), one thread per (column, chunk): every load of the kernel is in flight at
-    // once and the dependent add chains are 16 long instead of NB_RED long.  The column index runs fastest over the
-    // lanes, so a load instruction touches a few 168-byte partial rows instead of 64 different ones.
-    {
-        constexpr int LR = (NB_RED + SUM_CHUNKS - 1) / SUM_CHUNKS;
-        static_assert(LR * SUM_CHUNKS == NB_RED, "chunks of equal length");
-        constexpr int NPAIR = RED_K * SUM_CHUNKS;            // (statistic column, chunk) pairs
-        static_assert(NPAIR + 2 * SUM_CHUNKS <= 512, "two passes of 256 threads");
-        const int qa = t, qb = t + 256;
-        const int colA = qa % RED_K, chA = qa / RED_K;
-        const int colB = qb % RED_K, chB = qb / RED_K;
-        const bool hasA = qa < NPAIR, hasB = qb < NPAIR;
-        double va[LR], vb[LR];
-        if constexpr (!VPROWS) {
-            if (hasA) {
-#pragma unroll
-                for (int k = 0; k < LR; ++k) va[k] = partR[(size_t)(chA * LR + k) * RED_K + colA];
-            }
-            if (hasB) {
-#pragma unroll
-                for (int k = 0; k < LR; ++k) vb[k] = partR[(size_t)(chB * LR + k) * RED_K + colB];
-            }
-        }
-        const int te = qb - NPAIR;  // the next 2 * SUM_CHUNKS slots: the two energy columns
-        if (te >= 0 && te < 2 * SUM_CHUNKS) {
-            const int LE = (nbE + SUM_CHUNKS - 1) / SUM_CHUNKS, c = te / SUM_CHUNKS, ch = te % SUM_CHUNKS;
-            const int k0 = ch * LE, k1 = min(nbE, (ch + 1) * LE);
-            double e = 0.0;
-            int k = k0;
-            for (; k + 8 <= k1; k += 8) {
-                double ve[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) ve[u] = partE[2 * (k + u) + c];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) e += ve[u];
-            }
-            for (; k < k1; ++k) e += partE[2 * k + c];
-            chunk[RED_K + c][ch] = e;
-            if (PAIR && alpha_full > 0.0) {   // the same chunks of the full step's partials (same order: the same bits as a plain slot)
-                double e2 = 0.0;
-                int k2 = k0;
-                for (; k2 + 8 <= k1; k2 += 8) {
-                    double ve[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) ve[u] = partE2[2 * (k2 + u) + c];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) e2 += ve[u];
-                }
-                for (; k2 < k1; ++k2) e2 += partE2[2 * k2 + c];
-                chunk2[PAIR ? c : 0][ch] = e2;
-            }
-        }
-        if constexpr (VPROWS) {
-            // nbE rows of statistics: chunk ch of column col = rows [ch LE, (ch + 1) LE), eight loads in flight
-            auto chunk_rows = [&](int col, int ch) {
-                const int LE = (nbE + SUM_CHUNKS - 1) / SUM_CHUNKS;
-                const int k0 = ch * LE, k1 = min(nbE, (ch + 1) * LE);
-                double s = 0.0;
-                int k = k0;
-                for (; k + 8 <= k1; k += 8) {
-                    double v8[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) v8[u] = partR[(size_t)(k + u) * RED_K + col];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) s += v8[u];
-                }
-                for (; k < k1; ++k) s += partR[(size_t)k * RED_K + col];
-                return s;
-            };
-            if (hasA) chunk[colA][chA] = chunk_rows(colA, chA);
-            if (hasB) chunk[colB][chB] = chunk_rows(colB, chB);
-        } else {
-        if (hasA) {
-            double a = 0.0;
-#pragma unroll
-            for (int k = 0; k < LR; ++k) a += va[k];
-            chunk[colA][chA] = a;
-        }
-        if (hasB) {
-            double b = 0.0;
-#pragma unroll
-            for (int k = 0; k < LR; ++k) b += vb[k];
-            chunk[colB][chB] = b;
-        }
-        }
-    }
-    double a0spec = 1.0;   // SPEC: alpha_0 of the direction the slot computed (valid in thread 0)
-    if constexpr (SPEC) {
-        if (t < 64 && !init) {
-            double pg = 0.0, pHp = 0.0;
-#pragma unroll
-            for (int u = 0; u < NB_RED / 64; ++u) {
-                pg += pgv[u];
-                pHp += pHpv[u];
-            }
-            pg = wave_sum(pg);
-            pHp = wave_sum(pHp);
-            a0spec = fmax(ctl->alphaMin, fmin(1.0, -pg / pHp));  // Optimizer.cpp:1085
-        }
-    }
-    __syncthreads();
-    if (C.status != 0) return;
-    if (t < RED_K + 2) {
-        double acc = 0.0;
-#pragma unroll
-        for (int c = 0; c < SUM_CHUNKS; ++c) acc += chunk[t][c];
-        R[t] = acc;
-    }
-    __syncthreads();
-    if (t == 0 && init) {
-        // evaluation at the start of the step (DOTTimeStepper.cpp:299): nothing to decide yet
-        const double E = C.dtSq * R[RED_K] + R[RED_K + 1];
-        C.evals++;
-        C.E_cur = C.E0 = E;
-        C.g2_cur = C.g2_0 = R[0];
-    } else if (t == 0) {
-        double alpha = alpha_in;
-        const double E = C.dtSq * R[RED_K] + R[RED_K + 1];
-        int kind = 0;
-        bool decided = false;
-        if constexpr (PAIR) {
-            if (C.slots < C.kindCap) C.slot_kind[C.slots] = C.phase == 0 ? 1 : 2;
-            C.slots++;
-            kind = (C.phase == 0 || C.redo) ? 0 : 1;   // first trial of an iteration / retry after a halving
-            // what a first trial with alpha_0 < 1 teaches the pairing rule (a redone trial has taught it already)
-            const double a0 = alpha_full > 0.0 ? alpha_full : alpha_in;
-            const bool learns = C.phase == 0 && a0 < 1.0;
-            if (C.phase == 0) {
-                C.firstTrials++;
-                C.unitFirst += a0 == 1.0 ? 1 : 0;
-            }
-            C.redo = 0;
-            if (alpha_full > 0.0) {
-                // Paired slot: the energy of the FULL step first, as the reference's line search would see it
-                double ea = 0.0, ei = 0.0;
-#pragma unroll
-                for (int c = 0; c < SUM_CHUNKS; ++c) {
-                    ea += chunk2[0][c];
-                    ei += chunk2[PAIR ? 1 : 0][c];
-                }
-                const double EA = C.dtSq * ea + ei;
-                C.pairSlots++;
-                {
-                    int &pc = C.pairCtr[pair_band(alpha_full)];
-                    pc = (EA > C.E_cur) ? min(3, pc + 1) : max(0, pc - 1);
-                }
-                if (!(EA > C.E_cur)) {
-                    // the full step is acceptable: the slot's gradient belongs to the half step and is of no use.  The next slot
-                    // evaluates the full step as a plain trial (its energy is counted there); nothing else has happened
-                    C.pairRedo++;
-                    C.abortEpoch = C.slots;
-                    __hip_atomic_store(&ctl->abortEpoch, C.slots, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    C.holdVerdict = 2 * C.slots + 1;
-                    __hip_atomic_store(&ctl->holdVerdict, C.holdVerdict, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    C.phase = 1;
-                    C.alpha = alpha_full;
-                    C.redo = 1;
-                    decided = true;
-                } else {
-                    // rejected: one halving; the trial in front of the controller is the retry with the half step
-                    C.evals++;
-                    C.halvings++;
-                    int &ctr = C.predCtr[kind][C.predHist[kind] & 3];
-                    ctr = min(3, ctr + 1);
-                    C.predHist[kind] = ((C.predHist[kind] << 1) | 1) & 3;
-                    kind = 1;
-                }
-            }
-            if (!decided) C.evals++;
-            C.heldSlots += (C.holdNext || alpha_full > 0.0) ? 1 : 0;
-            if (learns && alpha_full == 0.0) {
-                int &pc = C.pairCtr[pair_band(a0)];
-                pc = (E > C.E_cur && alpha > 0.0) ? min(3, pc + 1) : max(0, pc - 1);
-            }
-        } else if constexpr (SPEC) {
-            if (C.slots < C.kindCap) C.slot_kind[C.slots] = C.phase == 0 ? 1 : 2;
-            C.slots++;
-            kind = (C.phase == 0 || C.redo) ? 0 : 1;   // first trial of an iteration (a redone slot is one) / retry after a halving
-            C.redo = 0;
-            if (C.phase == 0) {
-                // the slot computed a new direction and evaluated x + 1 p beside it
-                C.firstTrials++;
-                C.unitFirst += a0spec == 1.0 ? 1 : 0;
-                C.specSlots++;
-                if (a0spec != 1.0) {
-                    // the estimate lies inside (alphaMin, 1): the unit step is not the line search's first trial.  Nothing has
-                    // happened yet: the slot's back-solve stops, the next slot evaluates x + alpha_0 p (its energy is counted there)
-                    C.specRedo++;
-                    C.abortEpoch = C.slots;
-                    __hip_atomic_store(&ctl->abortEpoch, C.slots, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    C.holdVerdict = 2 * C.slots + 1;
-                    __hip_atomic_store(&ctl->holdVerdict, C.holdVerdict, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    C.phase = 1;
-                    C.alpha = a0spec;
-                    C.redo = 1;
-                    decided = true;
-                }
-            }
-            if (!decided) C.evals++;
-            C.heldSlots += C.holdNext;
-        } else {
-            C.evals++;
-            if (C.slots < C.kindCap) C.slot_kind[C.slots] = C.phase == 0 ? 1 : 2;
-            C.slots++;
-            kind = C.phase == 0 ? 0 : 1;   // first trial of an iteration / retry after a halving
-            if (C.phase == 0) {   // (the gate of the next step's speculation: how often the estimate is the unit step)
-                C.firstTrials++;
-                C.unitFirst += alpha_in == 1.0 ? 1 : 0;
-            }
-            C.heldSlots += C.holdNext;
-        }
-        if (decided) {
-        } else if (E > C.E_cur && alpha > 0.0) {
-            // back-tracking (c1 = 0, lower bound 0)
-            // a speculative back-solve on this trial's gradient may be running beside this workgroup: tell it to stop
-            C.abortEpoch = C.slots;
-            __hip_atomic_store(&ctl->abortEpoch, C.slots, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            C.holdVerdict = 2 * C.slots + 1;   // ... and one that has been waiting for the verdict to leave
-            __hip_atomic_store(&ctl->holdVerdict, C.holdVerdict, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            {
-                int &ctr = C.predCtr[kind][C.predHist[kind] & 3];
-                ctr = min(3, ctr + 1);
-                C.predHist[kind] = ((C.predHist[kind] << 1) | 1) & 3;
-            }
-            C.heldRejected += (C.holdNext || alpha_full > 0.0) ? 1 : 0;
-            alpha /= 2.0;
-            C.halvings++;
-            if (alpha == 0.0) {
-                // the step length underflowed: the reference stops at the last trial point (Optimizer.cpp:819-861)
-                C.status = 3;
-                double *tmp = C.x_cur;
-                C.x_cur = C.x_trial;
-                C.x_trial = tmp;
-                C.E_cur = E;
-            } else {
-                C.phase = 1;
-                C.alpha = alpha;
-            }
-        } else {
-            double *tmp = C.x_cur;
-            C.x_cur = C.x_trial;
-            C.x_trial = tmp;
-            tmp = C.g_cur;
-            C.g_cur = C.g_trial;
-            C.g_trial = tmp;
-            C.E_cur = E;
-            const double g2 = R[0];
-            C.g2_cur = g2;
-            const bool last = C.iter + 1 >= C.iterCap || !(g2 > C.tol);
-            if (last) {
-                // the loop ends with this iterate: a speculative back-solve for the next direction (running beside this
-                // workgroup) may stop -- said before the history update below
-                C.abortEpoch = C.slots;
-                __hip_atomic_store(&ctl->abortEpoch, C.slots, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            C.holdVerdict = 2 * C.slots + (last ? 1 : 0);   // a held back-solve may start now (or leave)
-            __hip_atomic_store(&ctl->holdVerdict, C.holdVerdict, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            {
-                int &ctr = C.predCtr[kind][C.predHist[kind] & 3];
-                ctr = max(0, ctr - 1);
-                C.predHist[kind] = (C.predHist[kind] << 1) & 3;
-            }
-            // The history update and the first half of the two-loop below are the host loop's statements
-            // (dotmi_step) with every array held in registers: all loops are unrolled to HIST_MAX with guards, so
-            // nothing is indexed dynamically and no LDS round trip sits in the dependent chain.  The operations
-            // and their order are the host's, so the two loops stay bit-identical.
-            constexpr int H = HIST_MAX;
-            const double ys_new = R[1], sg_new = R[2];
-            double siy[H], snyj[H], sig[H], ys[H], b[H], sy[H][H], xi[H];
-            int order[H];
-#pragma unroll
-            for (int i = 0; i < H; ++i) {
-                siy[i] = R[3 + i];
-                snyj[i] = R[3 + H + i];
-                sig[i] = R[3 + 2 * H + i];
-                ys[i] = C.L.ys[i];
-                b[i] = C.b[i];
-                order[i] = C.order[i];
-#pragma unroll
-                for (int jj = 0; jj < H; ++jj) sy[i][jj] = C.L.sy[i][jj];
-            }
-            int m = C.L.m;
-            const int hist = C.hist, newslot = C.slot;
-            C.pairNew = ys_new > 0.0 ? 1 : 0;
-            if (ys_new > 0.0) {
-                int off = 0;
-                if (m == hist) {  // drop the oldest pair
-                    off = 1;
-#pragma unroll
-                    for (int i = 0; i + 1 < H; ++i) {
-                        order[i] = order[i + 1];
-                        ys[i] = ys[i + 1];
-#pragma unroll
-                        for (int jj = 0; jj + 1 < H; ++jj) sy[i][jj] = sy[i + 1][jj + 1];
-                    }
-                    m -= 1;
-                }
-#pragma unroll
-                for (int i = 0; i < H; ++i) {
-                    // value i + off of the three statistic rows
-                    const double a_siy = (off && i + 1 < H) ? siy[i + 1 < H ? i + 1 : i] : siy[i];
-                    const double a_sny = (off && i + 1 < H) ? snyj[i + 1 < H ? i + 1 : i] : snyj[i];
-                    const double a_sig = (off && i + 1 < H) ? sig[i + 1 < H ? i + 1 : i] : sig[i];
-                    if (i < m) {
-#pragma unroll
-                        for (int jj = 0; jj < H; ++jj)
-                            if (jj == m) {
-                                sy[i][jj] = a_siy;   // sy[i][m]
-                            }
-#pragma unroll
-                        for (int ii = 0; ii < H; ++ii)
-                            if (ii == m) sy[ii][i] = a_sny;   // sy[m][i]
-                        b[i] = a_sig;
-                    }
-                }
-#pragma unroll
-                for (int i = 0; i < H; ++i)
-                    if (i == m) {
-                        order[i] = newslot;
-                        ys[i] = ys_new;
-                        sy[i][i] = ys_new;
-                        b[i] = sg_new;
-                    }
-                m += 1;
-            } else {
-#pragma unroll
-                for (int i = 0; i < H; ++i)
-                    if (i < m) b[i] = sig[i];
-            }
-            if (C.iter < C.logCap) {
-                C.log_alpha[C.iter] = alpha;
-                C.log_E[C.iter] = E;
-                C.log_g2[C.iter] = g2;
-            }
-            C.iter++;
-#pragma unroll
-            for (int i = 0; i < H; ++i) xi[i] = 0.0;
-            int fs = C.slot;
-            if (C.iter >= C.iterCap) C.status = 2;
-            else if (!(g2 > C.tol)) C.status = 1;
-            if (C.status == 0) {
-                // next direction: first half of the two-loop, free slot
-#pragma unroll
-                for (int i = H - 1; i >= 0; --i)
-                    if (i < m) {
-                        double sq = -b[i];
-#pragma unroll
-                        for (int jj = H - 1; jj > i; --jj)
-                            if (jj < m) sq -= xi[jj] * sy[i][jj];
-                        xi[i] = sq / ys[i];
-                    }
-                fs = 0;
-                bool found = false;
-#pragma unroll
-                for (int sl = 0; sl <= H; ++sl) {
-                    bool used = false;
-#pragma unroll
-                    for (int i = 0; i < H; ++i) used |= (i < m && order[i] == sl);
-                    if (!found && sl <= hist && !used) {
-                        fs = sl;
-                        found = true;
-                    }
-                }
-                C.phase = 0;
-            }
-            // back to the shared copy (stores only; the operand views take their pointers from the slot table)
-            C.L.m = m;
-            C.slot = fs;
-#pragma unroll
-            for (int i = 0; i < H; ++i) {
-                C.L.ys[i] = ys[i];
-                C.b[i] = b[i];
-                C.order[i] = order[i];
-                C.X.xi[i] = xi[i];
-#pragma unroll
-                for (int jj = 0; jj < H; ++jj) C.L.sy[i][jj] = sy[i][jj];
-                if (i < m) {
-                    C.L.s[i] = C.S[order[i]];
-                    C.L.y[i] = C.Y[order[i]];
-                }
-            }
-            devloop_resolve(C);   // (S[slot], MY[order[i]], HS[order[i]]: the kernels of the next slot read them resolved)
-        }
-    }
-    // forecast for the slot that follows: hold its back-solve if its kind's counter for the current pattern says "rejected"
-    if (t == 0 && !init) {
-        const int nk = C.phase == 0 ? 0 : 1;
-        C.holdNext = (C.holdEnable && C.status == 0 && !((PAIR || SPEC) && C.redo) && C.predCtr[nk][C.predHist[nk] & 3] >= 2) ? 1 : 0;
-    }
-    __syncthreads();
-    {
-        unsigned long long *dst = reinterpret_cast<unsigned long long *>(ctl);
-        const unsigned long long *src = reinterpret_cast<const unsigned long long *>(&C);
-        for (int i = t; i < NW8; i += 256) dst[i] = src[i];
-    }
-    // a store to host memory holds the kernel's end back by several microseconds: only near the expected
-    // end of the loop, where the host needs the progress to stop enqueueing
-    if (t == 0 && !init && (C.status != 0 || C.slots >= C.notifyFrom)) {
-        __threadfence_system();
-        flags_host[1] = C.slots;
-        flags_host[0] = C.status;
-    }
-}
-
+// the controller as a launch of its own: one workgroup, the plain form (the q-based order; back-solves with no 256-thread launch)
 __global__ __launch_bounds__(256) void loop_control_kernel(DevLoop *__restrict__ ctl,
                                                            const double *__restrict__ partE, int nbE,
                                                            const double *__restrict__ partR,
@@ -1345,34 +892,18 @@ static void launch_gemv_impl(const DevParts &P, const double *q, hipStream_t st,
                                   P.tl.panel, P.tl.rowBase, P.tl.rowPos, (const double *)P.tl.packed, P.psub, ctl);
     }
 }
+// one instantiation per form of the controller (without a controller the form plays no part)
 void launch_gemv(const DevParts &P, const double *q, hipStream_t st, const DevLoop *ctl, hipEvent_t ev0, hipEvent_t ev1,
-                 const CtlArgs *ca, int spec)
+                 const CtlLaunch *cl, int spec)
 {
-    launch_gemv_impl<CTL_PLAIN>(P, q, st, ctl, ev0, ev1, ca, spec);
-}
-// ... with the controller that understands paired slots (CtlArgs::init bit 1)
-void launch_gemv_pair(const DevParts &P, const double *q, hipStream_t st, const DevLoop *ctl, hipEvent_t ev0, hipEvent_t ev1,
-                      const CtlArgs *ca, int spec)
-{
-    launch_gemv_impl<CTL_PAIR>(P, q, st, ctl, ev0, ev1, ca, spec);
-}
-// ... paired trials on vertex patches
-void launch_gemv_pair_vp(const DevParts &P, const double *q, hipStream_t st, const DevLoop *ctl, hipEvent_t ev0, hipEvent_t ev1,
-                         const CtlArgs *ca, int spec)
-{
-    launch_gemv_impl<CTL_PAIR_VP>(P, q, st, ctl, ev0, ev1, ca, spec);
-}
-// ... with the controller of a step on vertex patches (k_elemvert.hip)
-void launch_gemv_vp(const DevParts &P, const double *q, hipStream_t st, const DevLoop *ctl, hipEvent_t ev0, hipEvent_t ev1,
-                    const CtlArgs *ca, int spec)
-{
-    launch_gemv_impl<CTL_VP>(P, q, st, ctl, ev0, ev1, ca, spec);
-}
-// ... with the controller of a step that takes the unit step speculatively (k_dirstep.hip)
-void launch_gemv_spec(const DevParts &P, const double *q, hipStream_t st, const DevLoop *ctl, hipEvent_t ev0, hipEvent_t ev1,
-                      const CtlArgs *ca, int spec)
-{
-    launch_gemv_impl<CTL_SPEC>(P, q, st, ctl, ev0, ev1, ca, spec);
+    const CtlArgs *ca = cl ? &cl->a : nullptr;
+    switch (cl ? cl->form : CTL_PLAIN) {
+    case CTL_PAIR: return launch_gemv_impl<CTL_PAIR>(P, q, st, ctl, ev0, ev1, ca, spec);
+    case CTL_SPEC: return launch_gemv_impl<CTL_SPEC>(P, q, st, ctl, ev0, ev1, ca, spec);
+    case CTL_VP: return launch_gemv_impl<CTL_VP>(P, q, st, ctl, ev0, ev1, ca, spec);
+    case CTL_PAIR_VP: return launch_gemv_impl<CTL_PAIR_VP>(P, q, st, ctl, ev0, ev1, ca, spec);
+    default: return launch_gemv_impl<CTL_PLAIN>(P, q, st, ctl, ev0, ev1, ca, spec);
+    }
 }
 // the tile partials of every owned subdomain summed in the subdomains' own order (coalesced) -> psub
 void launch_reduce_partial(const DevParts &P, hipStream_t st, const DevLoop *ctl)

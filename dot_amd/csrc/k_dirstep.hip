@@ -16,7 +16,7 @@
 // binds at 1 in most iterations (bar17K: 192 of 192; refined horse 82 %; stiff monkey 69 %).  Here workgroups [0, NB_RED) run
 // spmv_zp_body (p, H p, the partials of p.g and p.Hp) and workgroups [NB_RED, NB_RED + nbE) run elem_patch_body in its SPEC form
 // on x + 1 p, forming p_v = z_v + sum_j delta_j s_j[v] themselves for the vertices they read (k_elembody.hpp).  No population
-// waits for the other; the gather scales the new pair with 1; the controller (loop_control_body<CTL_SPEC>, k_backsolve.hip) sums
+// waits for the other; the gather scales the new pair with 1; the controller (loop_control_body<CTL_SPEC>, k_loopctl.hpp) sums
 // the SpMV partials as the element pass's prologue would have, and when alpha_0 is NOT 1 it stops the slot's back-solve and has
 // the slot redone as the first trial with the true alpha_0 (phase 1, DevLoop::redo) -- so the sequence of evaluated trials, their
 // energies, the accepted steps and every vector are the unspeculated loop's, bit for bit.  A step speculates when at least nine

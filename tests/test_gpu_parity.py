@@ -632,7 +632,7 @@ def test_every_dissection_depth_gives_the_same_preconditioner(levels, nd_min, mo
     ts.close(); orc.close()
 
 
-@pytest.mark.parametrize("history", [2, 5, 6])
+@pytest.mark.parametrize("history", [1, 2, 5, 6])   # (1: every accepted trial drops the oldest pair)
 def test_iteration_cap_and_history_lengths_in_both_loops(history, monkeypatch):
     """Iteration cap (return code 2, Optimizer.cpp:317-330) and the L-BFGS history rotation at other lengths than
     the reference's 5 -- the device-resident loop control and the host loop must agree bit for bit, and a capped
