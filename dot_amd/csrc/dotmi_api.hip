@@ -538,7 +538,7 @@ int dotmi_bench_kernel(dotmi_handle *h, int32_t kind, int32_t reps, double *ms_p
         // (split form, big meshes: the coalesced reduce of the tile partials is the first half of the merge)
         run = [&] {
             if (!h->P.mt_ptr) launch_reduce_partial(h->P, h->st);
-            launch_merge(h->M, h->P, L, h->z, h->partC, 1 | 2, h->st);
+            launch_merge(h->M, h->P, L, {.z = h->z, .partials = h->partC, .dots = true, .divide = true}, h->st);
         };
         break;
     case DOTMI_BENCH_BUILD_QPAD:         // g + m history vectors read, padded right-hand sides written
@@ -587,8 +587,7 @@ int dotmi_bench_kernel(dotmi_handle *h, int32_t kind, int32_t reps, double *ms_p
         live = true;
         run = [&] {
             if (!h->P.mt_ptr) launch_reduce_partial(h->P, h->st, h->ctl);
-            launch_merge_early(h->M, h->P, h->z, h->partC, 0, h->st, h->ctl, nullptr, nullptr, VList(), nullptr, 0, nullptr,
-                               h->dist ? nullptr : h->partCT);
+            launch_merge_early(h->M, h->P, {.z = h->z, .partials = h->partC, .partialsT = h->dist ? nullptr : h->partCT}, h->st, h->ctl);
         };
         break;
     case DOTMI_BENCH_ELEM_STEP: {        // the element pass with the line-search step inside: + p read, trial point written

@@ -365,7 +365,7 @@ int dotmi_pcg_apply_precond(dotmi_handle *h, const double *r, double *w)
     const Bracket br = backsolve_bracket(h);
     if (coarse) coarse_restrict_solve(h, h->tmpn);
     launch_gemv(h->P, h->q, h->st, nullptr, br.ev0, br.ev1);
-    launch_merge(h->M, h->P, L0, h->z, h->partC, 0, h->st);               // zsum = S q
+    launch_merge(h->M, h->P, L0, {.z = h->z}, h->st);                     // zsum = S q
     if (coarse) coarse_prolong(h, h->z);
     launch_coarse_scale(h->n, h->z, h->pcg.isd, h->tmpn, h->st);          // w = zsum (.) isd, as pcg_spmv_kernel forms it
     HIPCHECK(h, hipMemcpyAsync(w, h->tmpn, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->st));

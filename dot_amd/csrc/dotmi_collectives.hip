@@ -58,6 +58,24 @@ int allreduce_sum(dotmi_handle *h, double *dev, size_t n)
     return 0;
 }
 
+// Sharded subdomains, the sum over the ranks behind a back-solve: the undivided merge of this rank's subdomains (the vertices of vl)
+// into the packet [zsum (n) ; c (dot_coarse_tail)] -- whose tail the caller has filled with this rank's part of c = Z^T r
+// (dot_coarse_restrict) --, the one collective of the iteration, A0 y = c on the summed tail on every rank when the coarse term is
+// active, then the launch that divides by the multiplicity, adds Z y and takes the y_i . z into partC.  ctl: every kernel gated as in
+// the device-resident loop; the collective is issued whatever the controller decides, so every rank enqueues the same sequence (the
+// early order's sum travels in a staging buffer: a slot whose merge is gated off leaves z alone)
+int merge_over_ranks(dotmi_handle *h, const LbfgsArgs &L, double *packet, RankSumEnd end, const DevLoop *ctl, VList vl)
+{
+    const CoarseMerge *co = dot_coarse(h);
+    launch_merge(h->M, h->P, L, {.z = packet, .vl = vl}, h->st, ctl);
+    if (int rc = allreduce_sum(h, packet, h->n + dot_coarse_tail(h))) return rc;
+    if (co) dot_coarse_solve(h, packet + h->n, ctl, 0);
+    const int first = end == RANKSUM_EARLY_FIRST;
+    if (end == RANKSUM_ZFINISH) launch_zfinish(h->nV, h->P.dup, L, packet, h->partC, h->st, ctl, co);
+    else launch_merge_early(h->M, h->P, {.z = h->z, .partials = h->partC, .first = first, .zsum = packet, .co = co}, h->st, ctl);
+    return 0;
+}
+
 // Every rank takes its accept / halve / converged decisions from RANK 0's control scalars (the ranks
 // compute them redundantly on replicated data, but a single differing bit would make them branch apart and dead-lock
 // in the next collective).  vals: host array, replaced by rank 0's on every rank.  One small collective per trial.

@@ -156,23 +156,18 @@ static void slot_backsolve(dotmi_handle *h, const Slot &s)
 static int slot_merge(dotmi_handle *h)
 {
     if (!h->dist) {
-        launch_merge_early(h->M, h->P, h->z, h->partC, 0, h->st, h->ctl, nullptr, nullptr, VList(), nullptr, 0, nullptr, h->partCT,
-                           dot_coarse(h));
+        launch_merge_early(h->M, h->P, {.z = h->z, .partials = h->partC, .partialsT = h->partCT, .co = dot_coarse(h)}, h->st, h->ctl);
     } else if (!h->owner) {
         // sharded subdomains: this rank's part of the sum, the one collective of the iteration (issued in every slot,
         // whatever the controller decided: every rank enqueues the same sequence), then the division and the history terms
         // (the sum travels in a staging buffer: in a slot whose merge is gated off -- retry, past the end -- the collective
         // still runs, on stale scratch, and z is left alone)
-        LbfgsArgs L0;
-        memset(&L0, 0, sizeof(L0));
         // DOTMI_FLAG_DOT_COARSE: the packet is [zsum (n) ; c (nc)] -- slot_coarse has left this rank's part of c = Z^T (-g_trial) in the
         // tail --, every rank solves A0 y = c on the summed tail behind the collective (gated like the merge that reads y: the
         // controller has spoken by now) and the zsum branch of the merge adds Z y behind the division
-        const CoarseMerge *co = dot_coarse(h);
-        launch_merge(h->M, h->P, L0, h->zstage, h->partC, 0, h->st, h->ctl, h->held());
-        if (int rc = allreduce_sum(h, h->zstage, h->n + dot_coarse_tail(h))) return rc;
-        if (co) dot_coarse_solve(h, h->zstage + h->n, h->ctl, 0);
-        launch_merge_early(h->M, h->P, h->z, h->partC, 0, h->st, h->ctl, h->zstage, nullptr, VList(), nullptr, 0, nullptr, nullptr, co);
+        LbfgsArgs L0;
+        memset(&L0, 0, sizeof(L0));
+        return merge_over_ranks(h, L0, h->zstage, RANKSUM_EARLY, h->ctl, h->held());
     } else {
         // owner exchange: merge_early merges the tiles itself.
         // zstage: this rank's subdomains' sum, zero on the vertices it does not hold; only the shared vertices' entries
@@ -180,9 +175,11 @@ static int slot_merge(dotmi_handle *h)
         // the loop forms from it.  The five y_i . z travel inside the packet: merge_early merges this rank's tiles itself -- z,
         // u_old, M y_new and the y_i . z on the vertices only this rank holds, its part of the sum (to zstage) and its share
         // of the y_i . z on the shared ones --, then the exchange, then the shared vertices
-        launch_merge_early(h->M, h->P, h->z, h->partC, 0, h->st, h->ctl, nullptr, h->ownMask, h->held(), h->vkind, 1, h->zstage);
+        launch_merge_early(h->M, h->P, {.z = h->z, .partials = h->partC, .ownMask = h->ownMask, .vl = h->held(), .kind = h->vkind, .pre = 1,
+                                        .zshare = h->zstage}, h->st, h->ctl);
         if (int rc = exchange_solve_packed(h)) return rc;
-        if (h->nShared > 0) launch_merge_early(h->M, h->P, h->z, nullptr, 0, h->st, h->ctl, h->zstage, h->ownMask, h->shared());
+        if (h->nShared > 0)
+            launch_merge_early(h->M, h->P, {.z = h->z, .zsum = h->zstage, .ownMask = h->ownMask, .vl = h->shared()}, h->st, h->ctl);
     }
     return 0;
 }
@@ -224,15 +221,12 @@ static int enqueue_loop_slot(dotmi_handle *h)
     h->slotTimed.push_back(br.at);
     launch_gemv(h->P, nullptr, h->st, h->ctl, br.ev0, br.ev1);
     if (!h->dist) {
-        launch_merge(h->M, h->P, L0, h->z, h->partC, 1 | 2, h->st, h->ctl, VList(), co);
+        launch_merge(h->M, h->P, L0, {.z = h->z, .partials = h->partC, .dots = true, .divide = true, .co = co}, h->st, h->ctl);
     } else {
         // sharded subdomains: the one collective of an iteration, enqueued like a kernel.  It runs in every slot (also
         // in retries and past the end, where the kernels around it return at once), so every rank issues the same
         // sequence of collectives whatever the controller decides
-        launch_merge(h->M, h->P, L0, h->z, h->partC, 0, h->st, h->ctl);
-        if (int rc = allreduce_sum(h, h->z, n + dot_coarse_tail(h))) return rc;
-        if (co) dot_coarse_solve(h, h->z + n, h->ctl, 0);
-        launch_zfinish(h->nV, h->P.dup, L0, h->z, h->partC, h->st, h->ctl, co);
+        if (int rc = merge_over_ranks(h, L0, h->z, RANKSUM_ZFINISH, h->ctl)) return rc;
     }
     launch_build_p(n, h->z, L0, h->partC, nullptr, h->p, h->st, h->ctl);
     launch_spmv_dots(h->M, h->Hval, h->p, h->g, nullptr, h->v0, h->v1, h->partS, h->st, h->ctl);
@@ -378,17 +372,12 @@ static int step_start_sharded(dotmi_handle *h, int nb)
     if (co) dot_coarse_restrict(h, h->zstage + n);
     CtlLaunch ca{{h->ctl, h->gstage + n, ctlR, h->alpha_dev, h->h_flags, 1, 1}, CTL_PLAIN};
     launch_gemv(h->P, nullptr, h->st, h->ctl, nullptr, nullptr, &ca, 1 << 30);
-    launch_merge(h->M, h->P, L0, h->zstage, h->partC, 0, h->st, h->ctl, h->held());
-    if (!h->owner) {
-        if (int rc = allreduce_sum(h, h->zstage, n + dot_coarse_tail(h))) return rc;
-        if (co) dot_coarse_solve(h, h->zstage + n, h->ctl, 0);
-        launch_merge_early(h->M, h->P, h->z, h->partC, 1, h->st, h->ctl, h->zstage, nullptr, VList(), nullptr, 0, nullptr, nullptr, co);
-    } else {
-        if (int rc = exchange_iface(h, h->zstage, nullptr, 0)) return rc;
-        // (no pair yet: no y_i . z to sum)
-        launch_merge_early(h->M, h->P, h->z, nullptr, 1, h->st, h->ctl, h->zstage, h->ownMask, h->held());
-        HIPCHECK(h, hipMemsetAsync(h->partGC, 0, sizeof(double) * HIST_MAX, h->st));
-    }
+    if (!h->owner) return merge_over_ranks(h, L0, h->zstage, RANKSUM_EARLY_FIRST, h->ctl, h->held());
+    launch_merge(h->M, h->P, L0, {.z = h->zstage, .vl = h->held()}, h->st, h->ctl);
+    if (int rc = exchange_iface(h, h->zstage, nullptr, 0)) return rc;
+    // (no pair yet: no y_i . z to sum, no partials)
+    launch_merge_early(h->M, h->P, {.z = h->z, .first = 1, .zsum = h->zstage, .ownMask = h->ownMask, .vl = h->held()}, h->st, h->ctl);
+    HIPCHECK(h, hipMemsetAsync(h->partGC, 0, sizeof(double) * HIST_MAX, h->st));
     return 0;
 }
 
@@ -439,14 +428,8 @@ static int enqueue_step_start(dotmi_handle *h)
     // (no trial to judge yet: the plain controller, which only differs in how many rows of statistics there are)
     CtlLaunch ca{{h->ctl, h->partE, h->partR, h->alpha_dev, h->h_flags, nb, 1}, h->vpNow ? CTL_VP : CTL_PLAIN};
     launch_gemv(h->P, nullptr, h->st, h->ctl, nullptr, nullptr, &ca, 1 << 30);
-    if (!h->dist) {
-        launch_merge_early(h->M, h->P, h->z, h->partC, 1, h->st, h->ctl, nullptr, nullptr, VList(), nullptr, 0, nullptr, h->partCT, co);
-    } else {
-        launch_merge(h->M, h->P, L0, h->zstage, h->partC, 0, h->st, h->ctl);
-        if (int rc = allreduce_sum(h, h->zstage, h->n + dot_coarse_tail(h))) return rc;
-        if (co) dot_coarse_solve(h, h->zstage + h->n, h->ctl, 0);
-        launch_merge_early(h->M, h->P, h->z, h->partC, 1, h->st, h->ctl, h->zstage, nullptr, VList(), nullptr, 0, nullptr, nullptr, co);
-    }
+    if (h->dist) return merge_over_ranks(h, L0, h->zstage, RANKSUM_EARLY_FIRST, h->ctl);
+    launch_merge_early(h->M, h->P, {.z = h->z, .partials = h->partC, .partialsT = h->partCT, .first = 1, .co = co}, h->st, h->ctl);
     return 0;
 }
 

@@ -418,6 +418,13 @@ int adopt_rank0(dotmi_handle *h, double *vals, int n);
 int exchange_iface(dotmi_handle *h, double *vec, double *tailp, int ntail);
 int exchange_gradient_packed(dotmi_handle *h, int n, int nbE, const double *partials, int ncols);
 int exchange_solve_packed(dotmi_handle *h);
+// the merge's sum over the ranks of a sharded handle, and what finishes it
+enum RankSumEnd {
+    RANKSUM_ZFINISH,       // launch_zfinish on the packet, in place (q-based order, host loop)
+    RANKSUM_EARLY,         // the zsum branch of launch_merge_early into h->z (early order)
+    RANKSUM_EARLY_FIRST    // ... at the start of the step (MergeEarlyArgs::first)
+};
+int merge_over_ranks(dotmi_handle *h, const LbfgsArgs &L, double *packet, RankSumEnd end, const DevLoop *ctl, VList vl = VList());
 // dotmi_loop.hip
 struct Bracket {
     hipEvent_t ev0, ev1;   // DOTMI_FLAG_TIME_BACKSOLVE: the events around a sampled back-solve, else nulls

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "lbfgs_history.hpp"   // HIST_MAX
+#include "merge_sum.hpp"       // MT_PAD
 #include "nd_layout.hpp"
 #include "tile_factor.hpp"
 #include <stdint.h>
@@ -218,8 +219,6 @@ struct DevIC {
     double *yw = nullptr;           // 3 nV: the forward sweep's result in order position
     int *flag = nullptr;            // set by a non-positive pivot
 };
-
-constexpr int MT_PAD = -2147483647 - 1;   // end of a dof's interleaved list (no offset, plain or complemented, has this value)
 
 struct CoarseMerge;   // (below, with DevCoarse)
 struct LbfgsArgs {
@@ -453,20 +452,28 @@ void launch_dirstep(const DevMesh &M, const DevPatches &PT, int mat, double dtSq
 // spec (device loop, early back-solve): 1: rpad = -g_cur, 2: rpad = -g_trial whatever the phase; no history terms
 void launch_build_qpad(const DevParts &P, const double *g, const LbfgsArgs &L, const double *xi_host, hipStream_t st,
                        const DevLoop *ctl = nullptr, int spec = 0);
-// early back-solve: u = merge(tile partials) / dup = -M g;  M y of the newest pair = u_old - u;  z = u - sum_j xi_j M y_j
-// (+ partial dots y_i . z);  first: start of the step (no history, u_old is only set)
 void launch_reduce_partial(const DevParts &P, hipStream_t st, const DevLoop *ctl = nullptr);
 void launch_twolevel_pack(const DevParts &P, hipStream_t st);   // after a factorisation (two-level form): the panels' rows -> P.tl.packed
-// zsum: the all-reduced sum (over all ranks' subdomains) of the undivided partial merges, in a staging buffer
-// ownMask (owner exchange): the y_i . z partials over the vertices this rank owns only
-// kind, pre, zshare (owner exchange with the y_i . z in the packet; zsum = nullptr: the kernel merges this rank's tiles itself):
-// before the exchange the whole work on the vertices only this rank holds; on the shared ones (kind bit 1) this rank's part of the
-// sum goes to zshare and its share of y_i . z to the partials; afterwards a launch over the shared vertices (zsum = the unpacked
-// sums, partials = nullptr)
-void launch_merge_early(const DevMesh &M, const DevParts &P, double *z, double *partials, int first, hipStream_t st,
-                        const DevLoop *ctl, const double *zsum = nullptr, const uint8_t *ownMask = nullptr, VList vl = VList(),
-                        const uint8_t *kind = nullptr, int pre = 0, double *zshare = nullptr, double *partialsT = nullptr,
-                        const CoarseMerge *co = nullptr);   // co (dotmi_set_dot_coarse): u += Z y behind the division, the COARSE instantiation
+// early back-solve: u = merge(tile partials) / dup = -M g;  M y of the newest pair = u_old - u;  z = u - sum_j xi_j M y_j
+// (+ partial dots y_i . z).  Device loop only.  The call sites name what differs from the defaults: {.z = ..., .first = 1, ...}
+struct MergeEarlyArgs {
+    double *z = nullptr;
+    double *partials = nullptr;         // the y_i . z, row-major [NB_RED][RED_K]; nullptr: none (they came with the packet, yz_pre_kernel)
+    double *partialsT = nullptr;        // the same once more, column-major
+    int first = 0;                      // start of the step: no history, u_old is only set
+    const double *zsum = nullptr;       // the all-reduced sum (over all ranks' subdomains) of the undivided partial merges, in a staging
+                                        // buffer: the division and the history terms are left.  nullptr: the kernel merges the tiles
+    const uint8_t *ownMask = nullptr;   // owner exchange: the y_i . z partials over the vertices this rank owns only
+    VList vl;                           // owner exchange: the vertices visited
+    // owner exchange with the y_i . z in the packet (pre = 1, zsum = nullptr): before the exchange the whole work on the vertices only this
+    // rank holds; on the shared ones (kind bit 1) this rank's part of the sum goes to zshare and its share of y_i . z to the partials;
+    // afterwards a launch over the shared vertices (zsum = the unpacked sums, partials = nullptr)
+    const uint8_t *kind = nullptr;
+    int pre = 0;
+    double *zshare = nullptr;
+    const CoarseMerge *co = nullptr;    // dotmi_set_dot_coarse: u += Z y behind the division, the COARSE instantiation
+};
+void launch_merge_early(const DevMesh &M, const DevParts &P, const MergeEarlyArgs &a, hipStream_t st, const DevLoop *ctl);
 // owner exchange: the entries of the vertices held by more than one rank, packed / unpacked (idx: their vertex ids);
 // tail: `ntail` further scalars copied from / to tailp behind the packed entries
 // red0 / red1: partial arrays whose rows workgroup 0 of the pack sums into the packet's tail (pack[dst ...]): `cols` columns of
@@ -489,9 +496,17 @@ void launch_mask_owned(int n, double *v, const uint8_t *ownMask, hipStream_t st)
 // tiles are job[0..njobs); then p = 0 except p[dofs of part ls] = psub_s  (ADMMDDTimeStepper::fill, :1646-1665)
 void launch_gemv_part(const DevParts &P, int ls, const int4 *job, int njobs, const int2 *lwork, int nlwork, const double *q,
                       int n, double *p, hipStream_t st);
-// z = merge(psub) / dup  (+ partial dots y_i . z);  co (dotmi_set_dot_coarse): z += Z y behind the division, the COARSE instantiations
-void launch_merge(const DevMesh &M, const DevParts &P, const LbfgsArgs &L, double *z, double *partials,
-                  int with_dots, hipStream_t st, const DevLoop *ctl = nullptr, VList vl = VList(), const CoarseMerge *co = nullptr);
+// z = merge(tile partials, or psub) (/ dup) (+ Z y) (+ partial dots y_i . z)
+struct MergeArgs {
+    double *z = nullptr;
+    double *partials = nullptr;        // the y_i . z (dots)
+    bool dots = false;                 // accumulate the y_i . z partials
+    bool divide = false;               // divide by dup (false: the undivided sum over this rank's subdomains)
+    VList vl;                          // owner exchange: the vertices visited
+    const CoarseMerge *co = nullptr;   // dotmi_set_dot_coarse: z += Z y behind the division, the COARSE instantiations
+};
+void launch_merge(const DevMesh &M, const DevParts &P, const LbfgsArgs &L, const MergeArgs &a, hipStream_t st,
+                  const DevLoop *ctl = nullptr);
 // partial dots y_i . z only (multi-GPU path after all-reduce)
 // p = z + sum_j delta_j s_j, delta from c partials, xi and SY
 void launch_build_p(int n, const double *z, const LbfgsArgs &L, const double *c_partials,

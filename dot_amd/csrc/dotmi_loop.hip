@@ -72,21 +72,15 @@ int apply_precond(dotmi_handle *h, const double *q, double *z, const LbfgsArgs &
 {
     const Bracket br = backsolve_bracket(h);
     launch_gemv(h->P, q, h->st, nullptr, br.ev0, br.ev1);
-    if (!h->dist) {
-        const CoarseMerge *co = dot_coarse(h);
-        if (co) dot_coarse_restrict_solve(h);
-        launch_merge(h->M, h->P, L, z, h->partC, 1 | 2, h->st, nullptr, VList(), co);
-    } else {
+    const CoarseMerge *co = dot_coarse(h);
+    if (h->dist) {
         // DOTMI_FLAG_DOT_COARSE: c = Z^T q of this rank's subdomains in the tail of z, summed with z; the solve on every rank behind the
         // collective; the prolongation behind the division (z: one of the handle's vectors, which have room for the tail)
-        const CoarseMerge *co = dot_coarse(h);
-        const size_t tail = dot_coarse_tail(h);
         if (co) dot_coarse_restrict(h, z + h->n);
-        launch_merge(h->M, h->P, L, z, h->partC, 0, h->st);
-        if (int rc = allreduce_sum(h, z, h->n + tail)) return rc;
-        if (co) dot_coarse_solve(h, z + h->n);
-        launch_zfinish(h->nV, h->P.dup, L, z, h->partC, h->st, nullptr, co);
+        return merge_over_ranks(h, L, z, RANKSUM_ZFINISH, nullptr);
     }
+    if (co) dot_coarse_restrict_solve(h);
+    launch_merge(h->M, h->P, L, {.z = z, .partials = h->partC, .dots = true, .divide = true, .co = co}, h->st);
     return 0;
 }
 

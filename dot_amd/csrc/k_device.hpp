@@ -5,6 +5,7 @@
 //                     the paired / speculative instantiations
 //   k_loopvec.hip     the loop's vector kernels: vertex gather, pair statistics, two-loop kernels, merges, SpMV + dots, owner-exchange
 //                     packets, small state kernels
+//                     (the merges' sum over subdomains and tiles: merge_sum.hpp, host-compilable; merge_check.cpp checks its three forms)
 //   k_backsolve.hip   subdomain back-solve tiles, the loop controller (k_loopctl.hpp; a launch of its own or workgroup 0 of the back-solve launch)
 //   k_tilefactor.hip  block-sparse inverse-Cholesky on 64 x 64 tiles (FP64 MFMA), level and dataflow schedules
 //   k_refresh.hip     once per step: element Hessians, global assembly, subdomain matrix fill

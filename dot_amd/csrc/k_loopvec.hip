@@ -38,6 +38,19 @@ struct HistView {
         }
     }
 };
+// ... or as a kernel reads them in place: the controller's in device-loop mode, else the launch's
+template <bool DEV>
+__device__ __forceinline__ const LbfgsArgs &loop_history(const DevLoop *__restrict__ ctl, const LbfgsArgs &L)
+{
+    if constexpr (DEV) return ctl->L;
+    else return L;
+}
+template <bool DEV>   // (and the two-loop's first coefficients with them)
+__device__ __forceinline__ const XiArgs &loop_xi(const DevLoop *__restrict__ ctl, const XiArgs &X)
+{
+    if constexpr (DEV) return ctl->X;
+    else return X;
+}
 template <class LV>
 __device__ __forceinline__ void pair_stats_accum(int k, double gn, double sn, double yn, const LV &L,
                                                  double (&acc)[RED_K])
@@ -246,10 +259,7 @@ __global__ __launch_bounds__(256) void pair_stats_kernel(int n, GatherArgs a, Lb
         a.s_new = ctl->S[ctl->slot];
         a.y_new = ctl->Y[ctl->slot];
     }
-    const LbfgsArgs &Lr = [&]() -> const LbfgsArgs & {
-        if constexpr (DEV) return ctl->L;
-        else return L;
-    }();
+    const LbfgsArgs &Lr = loop_history<DEV>(ctl, L);
     double acc[RED_K];
 #pragma unroll
     for (int j = 0; j < RED_K; ++j) acc[j] = 0.0;
@@ -305,14 +315,8 @@ __global__ __launch_bounds__(256) void build_q_kernel(int n, const double *__res
         if (ctl->status != 0 || ctl->phase != 0) return;
         g = ctl->g_cur;
     }
-    const LbfgsArgs &Lr = [&]() -> const LbfgsArgs & {
-        if constexpr (DEV) return ctl->L;
-        else return L;
-    }();
-    const XiArgs &Xr = [&]() -> const XiArgs & {
-        if constexpr (DEV) return ctl->X;
-        else return X;
-    }();
+    const LbfgsArgs &Lr = loop_history<DEV>(ctl, L);
+    const XiArgs &Xr = loop_xi<DEV>(ctl, X);
     const int stride = gridDim.x * blockDim.x;
     for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += stride) {
         double v = -g[k];
@@ -348,14 +352,8 @@ __global__ __launch_bounds__(256) void build_qpad_kernel(int total, const int *_
         if (ctl->status != 0 || (ctl->phase != 0 && spec != 2)) return;
         g = spec == 2 ? ctl->g_trial : ctl->g_cur;
     }
-    const LbfgsArgs &Lr = [&]() -> const LbfgsArgs & {
-        if constexpr (DEV) return ctl->L;
-        else return L;
-    }();
-    const XiArgs &Xr = [&]() -> const XiArgs & {
-        if constexpr (DEV) return ctl->X;
-        else return X;
-    }();
+    const LbfgsArgs &Lr = loop_history<DEV>(ctl, L);
+    const XiArgs &Xr = loop_xi<DEV>(ctl, X);
     const int m = spec ? 0 : Lr.m;   // early back-solve: the history terms are applied after the solve (merge_early)
     const int stride = gridDim.x * blockDim.x;
     for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < total; k += stride) {
@@ -395,14 +393,8 @@ __global__ __launch_bounds__(256) void build_p_kernel(int n, const double *__res
     if constexpr (DEV) {
         if (ctl->status != 0 || ctl->phase != 0) return;
     }
-    const LbfgsArgs &Lr = [&]() -> const LbfgsArgs & {
-        if constexpr (DEV) return ctl->L;
-        else return L;
-    }();
-    const XiArgs &Xr = [&]() -> const XiArgs & {
-        if constexpr (DEV) return ctl->X;
-        else return X;
-    }();
+    const LbfgsArgs &Lr = loop_history<DEV>(ctl, L);
+    const XiArgs &Xr = loop_xi<DEV>(ctl, X);
     // the body's operands do not depend on the coefficients: they are requested before the prologue below (partial sums
     // and the short recurrence), so their latency is hidden behind it.  The grid covers n in one trip (launch_build_p).
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -496,9 +488,13 @@ void launch_multidot(int n, const double *v, const double *const *vecs, int m, d
 // t_s + omega_s x (x_v - c_s)  behind the division by the multiplicity: M' r = M r + Z A0^-1 Z^T r.  The last kernel parameter is
 // MergeCoarse<COARSE>: empty without the term, so the plain instantiations keep their arguments and their code.
 template <bool COARSE>
-struct MergeCoarse {};
+struct MergeCoarse {
+    static constexpr bool on = false;
+};
 template <>
-struct MergeCoarse<true> : CoarseMerge {};
+struct MergeCoarse<true> : CoarseMerge {
+    static constexpr bool on = true;
+};
 // y = A0^-1 Z^T r from the row blocks' parts in ascending block order (coarse_prolong_kernel's prologue) into LDS, by every workgroup
 __device__ __forceinline__ void coarse_load_y(const CoarseMerge &co, double *y)
 {
@@ -526,6 +522,27 @@ __device__ __forceinline__ double coarse_term(const CoarseMerge &co, const doubl
     return w * a;
 }
 
+// ---- what the merge kernels' prologues share ----
+// a DEV kernel of a slot that is a line-search retry, or lies past the end of the loop, returns at once
+template <bool DEV>
+__device__ __forceinline__ bool merge_gated_off(const DevLoop *__restrict__ ctl)
+{
+    if constexpr (DEV) return ctl->status != 0 || ctl->phase != 0;
+    else return false;
+}
+// y of the coarse term in LDS (COARSE instantiations; nullptr otherwise)
+template <bool COARSE>
+__device__ __forceinline__ double *merge_coarse_y(const MergeCoarse<COARSE> &co)
+{
+    if constexpr (COARSE) {
+        __shared__ double ybuf[COARSE_NC_MAX];
+        coarse_load_y(co, ybuf);
+        return ybuf;
+    } else {
+        return nullptr;
+    }
+}
+
 // z_v = (sum over parts containing v of p_s[local v]) / dup_v ; partial dots c_i = y_i . z
 template <bool DEV, bool COARSE = false>
 __global__ __launch_bounds__(256) void merge_kernel(int nV, const int *__restrict__ vp_ptr,
@@ -537,19 +554,9 @@ __global__ __launch_bounds__(256) void merge_kernel(int nV, const int *__restric
                                                     const DevLoop *__restrict__ ctl, VList vl, MergeCoarse<COARSE> co)
 {
     __shared__ double sm[4 * RED_K];
-    if constexpr (DEV) {
-        if (ctl->status != 0 || ctl->phase != 0) return;
-    }
-    double *ysh = nullptr;
-    if constexpr (COARSE) {
-        __shared__ double ybuf[COARSE_NC_MAX];
-        ysh = ybuf;
-        coarse_load_y(co, ysh);
-    }
-    const LbfgsArgs &Lr = [&]() -> const LbfgsArgs & {
-        if constexpr (DEV) return ctl->L;
-        else return L;
-    }();
+    if (merge_gated_off<DEV>(ctl)) return;
+    double *ysh = merge_coarse_y(co);
+    const LbfgsArgs &Lr = loop_history<DEV>(ctl, L);
     double acc[RED_K];
 #pragma unroll
     for (int j = 0; j < RED_K; ++j) acc[j] = 0.0;
@@ -557,7 +564,6 @@ __global__ __launch_bounds__(256) void merge_kernel(int nV, const int *__restric
     const int nvis = vl.v ? vl.n : nV;
     for (int jv = blockIdx.x * blockDim.x + threadIdx.x; jv < nvis; jv += stride) {
         const int v = vl_vtx(vl, jv);
-        double z0 = 0, z1 = 0, z2 = 0;
         const int k0 = vp_ptr[v], k1 = vp_ptr[v + 1];
         // everything that does not depend on the slot list is requested before it is walked
         const int d = divide ? dup[v] : 1;
@@ -572,28 +578,9 @@ __global__ __launch_bounds__(256) void merge_kernel(int nV, const int *__restric
                     yv[i][2] = yi[2];
                 }
         }
-        // slots four at a time (a vertex is in 1-3 subdomains, rarely more): offsets first, then the values
-        for (int k = k0; k < k1; k += 4) {
-            int off[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) off[u] = (k + u < k1) ? vp_off[k + u] : -1;
-            double w[4][3];
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (off[u] >= 0) {
-                    const double *ps = psub + off[u];
-                    w[u][0] = ps[0];
-                    w[u][1] = ps[1];
-                    w[u][2] = ps[2];
-                }
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (off[u] >= 0) {
-                    z0 += w[u][0];
-                    z1 += w[u][1];
-                    z2 += w[u][2];
-                }
-        }
+        double zv[3] = {0.0, 0.0, 0.0};
+        merge_sum_psub(k0, k1, vp_off, psub, zv);
+        double z0 = zv[0], z1 = zv[1], z2 = zv[2];
         if (d > 1) {
             z0 /= d;
             z1 /= d;
@@ -621,37 +608,7 @@ __global__ __launch_bounds__(256) void merge_kernel(int nV, const int *__restric
 // subdomains holding the vertex of (the sum over that subdomain's tiles holding the column of ppart[tile][column]) --
 // the additions of reduce_partial_p_kernel followed by merge_kernel, in their order, without the psub round trip and
 // without a launch in between.
-constexpr int MT_CH = 24;   // list entries in flight per thread (a dof has ~15: two subdomains x ~8 tiles)
-// the walk over dof k's list in its wave-interleaved form (DevParts::mt_il): u = sum over the subdomains of (sum over the
-// subdomain's tiles of their partial) -- the additions of the CSR walk in its order; k >> 6 is uniform over the wave
-__device__ __forceinline__ double merge_walk_interleaved(int k, const int2 *__restrict__ mt_wave, const int *__restrict__ mt_il,
-                                                         const double *__restrict__ ppart, double u)
-{
-    const int2 wb = mt_wave[k >> 6];
-    const int *__restrict__ lst = mt_il + wb.x + (k & 63);
-    double ps = 0.0;
-    for (int q0 = 0; q0 < wb.y; q0 += MT_CH) {
-        int off[MT_CH];
-#pragma unroll
-        for (int q = 0; q < MT_CH; ++q) off[q] = (q0 + q < wb.y) ? lst[64 * (q0 + q)] : MT_PAD;
-        double w[MT_CH];
-#pragma unroll
-        for (int q = 0; q < MT_CH; ++q) {
-            const int o = off[q] < 0 ? ~off[q] : off[q];
-            w[q] = (off[q] != MT_PAD) ? ppart[o] : 0.0;
-        }
-#pragma unroll
-        for (int q = 0; q < MT_CH; ++q)
-            if (off[q] != MT_PAD) {
-                if (off[q] < 0 && q0 + q > 0) {   // a new subdomain starts: close the previous one
-                    u += ps;
-                    ps = 0.0;
-                }
-                ps += w[q];
-            }
-    }
-    return u + ps;
-}
+// (the list walks: merge_sum.hpp)
 template <bool DEV, bool COARSE = false>
 __global__ __launch_bounds__(256) void merge_tiles_kernel(int n3, const int *__restrict__ mt_ptr,
                                                           const int *__restrict__ mt_ent, const int *__restrict__ dup,
@@ -662,20 +619,10 @@ __global__ __launch_bounds__(256) void merge_tiles_kernel(int n3, const int *__r
                                                           MergeCoarse<COARSE> co)
 {
     __shared__ double sm[4 * RED_K];
-    if constexpr (DEV) {
-        if (ctl->status != 0 || ctl->phase != 0) return;
-    }
-    double *ysh = nullptr;
-    if constexpr (COARSE) {
-        __shared__ double ybuf[COARSE_NC_MAX];
-        ysh = ybuf;
-        coarse_load_y(co, ysh);
-    }
+    if (merge_gated_off<DEV>(ctl)) return;
+    double *ysh = merge_coarse_y(co);
     const bool il = mt_il != nullptr && vl.v == nullptr;
-    const LbfgsArgs &Lr = [&]() -> const LbfgsArgs & {
-        if constexpr (DEV) return ctl->L;
-        else return L;
-    }();
+    const LbfgsArgs &Lr = loop_history<DEV>(ctl, L);
     double acc[RED_K];
 #pragma unroll
     for (int j = 0; j < RED_K; ++j) acc[j] = 0.0;
@@ -691,30 +638,9 @@ __global__ __launch_bounds__(256) void merge_tiles_kernel(int n3, const int *__r
             for (int i = 0; i < HIST_MAX; ++i)
                 if (i < Lr.m) yk[i] = Lr.y[i][k];
         }
-        double zk = 0.0, ps = 0.0;
-        if (il) zk = merge_walk_interleaved(k, mt_wave, mt_il, ppart, 0.0);
-        // MT_CH entries at a time: offsets first, then the values, then the adds in list order
-        for (int e = e0; e < e1; e += MT_CH) {
-            int off[MT_CH];
-#pragma unroll
-            for (int u = 0; u < MT_CH; ++u) off[u] = (e + u < e1) ? mt_ent[e + u] : 0;
-            double w[MT_CH];
-#pragma unroll
-            for (int u = 0; u < MT_CH; ++u) {
-                const int o = off[u] < 0 ? ~off[u] : off[u];
-                w[u] = (e + u < e1) ? ppart[o] : 0.0;
-            }
-#pragma unroll
-            for (int u = 0; u < MT_CH; ++u)
-                if (e + u < e1) {
-                    if (off[u] < 0 && e + u > e0) {   // a new subdomain starts: close the previous one
-                        zk += ps;
-                        ps = 0.0;
-                    }
-                    ps += w[u];
-                }
-        }
-        zk += ps;
+        double zk = 0.0;
+        if (il) zk = merge_sum_interleaved(k, mt_wave, mt_il, ppart, 0.0);
+        zk = merge_sum_csr(e0, e1, mt_ent, ppart, zk);   // (il: an empty list)
         if (d > 1) zk /= d;
         if constexpr (COARSE) zk += coarse_term(co, ysh, k / 3, k % 3);
         z[k] = zk;
@@ -751,7 +677,8 @@ __global__ __launch_bounds__(NT) void merge_tiles_early_kernel(int n3, const int
     __shared__ double sm[(NT / 64) * RED_K];
     KSTAMP(1, 0);
     // (every load of the loop state in front of the first branch, the pointers resolved by the controller: one round trip)
-    const int status = ctl->status, phase = ctl->phase, lm = ctl->L.m, pnew = ctl->pairNew;
+    const bool off = merge_gated_off<true>(ctl);
+    const int lm = ctl->L.m, pnew = ctl->pairNew;
     double *__restrict__ u_old = ctl->u_old;
     double *my_new_r = ctl->my_new;
     HistView Lr;
@@ -763,13 +690,8 @@ __global__ __launch_bounds__(NT) void merge_tiles_early_kernel(int n3, const int
         my[i] = ctl->Lmy[i];
         xi[i] = ctl->X.xi[i];
     }
-    if (status != 0 || phase != 0) return;
-    double *ysh = nullptr;
-    if constexpr (COARSE) {
-        __shared__ double ybuf[COARSE_NC_MAX];
-        ysh = ybuf;
-        coarse_load_y(co, ysh);
-    }
+    if (off) return;
+    double *ysh = merge_coarse_y(co);
     const bool il = mt_il != nullptr && vl.v == nullptr && !psub && !zsum;
     const int m = first ? 0 : lm;
     const bool pairNew = !first && pnew != 0 && m > 0;
@@ -809,42 +731,16 @@ __global__ __launch_bounds__(NT) void merge_tiles_early_kernel(int n3, const int
         // zsum (sharded subdomains): the all-reduced sum over every rank's subdomains (merge_tiles_kernel without the division
         // into a staging buffer, then the collective -- on the staging buffer, so that a slot whose merge is gated off leaves z
         // alone); only the division and the history terms are left
-        double u = zsum ? zsum[k] : 0.0, ps = 0.0;
-        if (il) u = merge_walk_interleaved(k, mt_wave, mt_il, ppart, 0.0);
+        double u = zsum ? zsum[k] : 0.0;
+        if (il) u = merge_sum_interleaved(k, mt_wave, mt_il, ppart, 0.0);
         if (psub && !zsum) {
             // split form (big meshes): the subdomains' own sums are in psub (reduce_partial_p_kernel); same additions in the
-            // same order as the list walk below -- tiles of a subdomain first, then the subdomains
-            const int dd = k - 3 * vtx;
-            for (int c = c0; c < c1; c += 4) {
-                double w[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) w[q] = (c + q < c1) ? psub[vp_off[c + q] + dd] : 0.0;
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if (c + q < c1) u += w[q];
-            }
+            // same order as the list walks -- tiles of a subdomain first, then the subdomains
+            double us[1] = {u};
+            merge_sum_psub(c0, c1, vp_off, psub + (k - 3 * vtx), us);
+            u = us[0];
         }
-        for (int e = e0; e < e1; e += MT_CH) {
-            int off[MT_CH];
-#pragma unroll
-            for (int q = 0; q < MT_CH; ++q) off[q] = (e + q < e1) ? mt_ent[e + q] : 0;
-            double w[MT_CH];
-#pragma unroll
-            for (int q = 0; q < MT_CH; ++q) {
-                const int o = off[q] < 0 ? ~off[q] : off[q];
-                w[q] = (e + q < e1) ? ppart[o] : 0.0;
-            }
-#pragma unroll
-            for (int q = 0; q < MT_CH; ++q)
-                if (e + q < e1) {
-                    if (off[q] < 0 && e + q > e0) {   // a new subdomain starts: close the previous one
-                        u += ps;
-                        ps = 0.0;
-                    }
-                    ps += w[q];
-                }
-        }
-        u += ps;
+        u = merge_sum_csr(e0, e1, mt_ent, ppart, u);   // (zsum, il, psub: an empty list)
         KSTAMP(1, 2);
         if (pre && (kind[vtx] & 2)) {
             // Owner exchange with the y_i . z in the packet, BEFORE it travels, at a vertex other ranks hold too: u is this
@@ -999,64 +895,44 @@ void launch_mask_owned(int n, double *v, const uint8_t *ownMask, hipStream_t st)
     hipLaunchKernelGGL(mask_owned_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, v, ownMask);
 }
 
-// the arguments of a COARSE instantiation from the handle's record
-static MergeCoarse<true> merge_coarse(const CoarseMerge *co)
+// One dispatch for the three merge launchers: f(bool_constant<first>, MergeCoarse<co != nullptr>) with the handle's record as the
+// COARSE instantiation's last kernel argument.  `first`: DEV (launch_merge, launch_zfinish), the 512-thread form (launch_merge_early).
+template <class F>
+static void merge_dispatch(bool first, const CoarseMerge *co, F &&f)
 {
     MergeCoarse<true> c;
-    static_cast<CoarseMerge &>(c) = *co;
-    return c;
+    if (co) static_cast<CoarseMerge &>(c) = *co;
+    if (first && co) f(std::true_type(), c);
+    else if (first) f(std::true_type(), MergeCoarse<false>());
+    else if (co) f(std::false_type(), c);
+    else f(std::false_type(), MergeCoarse<false>());
 }
 
-void launch_merge_early(const DevMesh &M, const DevParts &P, double *z, double *partials, int first, hipStream_t st,
-                        const DevLoop *ctl, const double *zsum, const uint8_t *ownMask, VList vl, const uint8_t *kind, int pre,
-                        double *zshare, double *partialsT, const CoarseMerge *co)
+void launch_merge_early(const DevMesh &M, const DevParts &P, const MergeEarlyArgs &a, hipStream_t st, const DevLoop *ctl)
 {
     const bool split = !P.mt_ptr;
     // (a thread of the 256-thread form takes a dof per trip: beyond two trips -- 1 M tets: eight -- workgroups of 1024 threads)
-    const long long ndof = vl.v ? 3ll * vl.n : 3ll * M.nV;
-#define DOTMI_MERGE_EARLY(NT, COARSE, ...)                                                                                              \
-    hipLaunchKernelGGL((merge_tiles_early_kernel<NT, COARSE>), dim3(NB_RED), dim3(NT), 0, st, 3 * M.nV, P.mt_ptr, P.mt_ent, P.dup, P.ppart, \
-                       first, zsum, split ? P.vp_ptr : nullptr, split ? P.vp_off : nullptr, split ? (const double *)P.psub : nullptr,  \
-                       ownMask, vl, kind, pre, zshare, z, partials, ctl, P.mt_wave, P.mt_il, partialsT, __VA_ARGS__)
-    if (ndof > 2ll * NB_RED * 256) {
-        if (co) DOTMI_MERGE_EARLY(512, true, merge_coarse(co));
-        else DOTMI_MERGE_EARLY(512, false, MergeCoarse<false>());
-    } else {
-        if (co) DOTMI_MERGE_EARLY(256, true, merge_coarse(co));
-        else DOTMI_MERGE_EARLY(256, false, MergeCoarse<false>());
-    }
-#undef DOTMI_MERGE_EARLY
+    const long long ndof = a.vl.v ? 3ll * a.vl.n : 3ll * M.nV;
+    merge_dispatch(ndof > 2ll * NB_RED * 256, a.co, [&](auto wide, auto c) {
+        constexpr int NT = decltype(wide)::value ? 512 : 256;
+        hipLaunchKernelGGL((merge_tiles_early_kernel<NT, decltype(c)::on>), dim3(NB_RED), dim3(NT), 0, st, 3 * M.nV, P.mt_ptr, P.mt_ent,
+                           P.dup, P.ppart, a.first, a.zsum, split ? P.vp_ptr : nullptr, split ? P.vp_off : nullptr,
+                           split ? (const double *)P.psub : nullptr, a.ownMask, a.vl, a.kind, a.pre, a.zshare, a.z, a.partials, ctl,
+                           P.mt_wave, P.mt_il, a.partialsT, c);
+    });
 }
 
-void launch_merge(const DevMesh &M, const DevParts &P, const LbfgsArgs &L, double *z, double *partials,
-                  int with_dots, hipStream_t st, const DevLoop *ctl, VList vl, const CoarseMerge *co)
+void launch_merge(const DevMesh &M, const DevParts &P, const LbfgsArgs &L, const MergeArgs &a, hipStream_t st, const DevLoop *ctl)
 {
-    // with_dots: bit0 = accumulate y_i.z partials, bit1 = divide by dup
-#define DOTMI_MERGE_TILES(DEV, COARSE, ...)                                                                                             \
-    hipLaunchKernelGGL((merge_tiles_kernel<DEV, COARSE>), dim3(NB_RED), dim3(256), 0, st, 3 * M.nV, P.mt_ptr, P.mt_ent, P.dup, P.ppart, L, \
-                       with_dots & 1, (with_dots >> 1) & 1, z, partials, ctl, vl, P.mt_wave, P.mt_il, __VA_ARGS__)
-#define DOTMI_MERGE_PSUB(DEV, COARSE, ...)                                                                                              \
-    hipLaunchKernelGGL((merge_kernel<DEV, COARSE>), dim3(NB_RED), dim3(256), 0, st, M.nV, P.vp_ptr, P.vp_off, P.dup, P.psub, L,          \
-                       with_dots & 1, (with_dots >> 1) & 1, z, partials, ctl, vl, __VA_ARGS__)
-    if (P.mt_ptr) {   // (launch_gemv left the tile partials in ppart and skipped the reduce)
-        if (ctl) {
-            if (co) DOTMI_MERGE_TILES(true, true, merge_coarse(co));
-            else DOTMI_MERGE_TILES(true, false, MergeCoarse<false>());
-        } else {
-            if (co) DOTMI_MERGE_TILES(false, true, merge_coarse(co));
-            else DOTMI_MERGE_TILES(false, false, MergeCoarse<false>());
-        }
-        return;
-    }
-    if (ctl) {
-        if (co) DOTMI_MERGE_PSUB(true, true, merge_coarse(co));
-        else DOTMI_MERGE_PSUB(true, false, MergeCoarse<false>());
-    } else {
-        if (co) DOTMI_MERGE_PSUB(false, true, merge_coarse(co));
-        else DOTMI_MERGE_PSUB(false, false, MergeCoarse<false>());
-    }
-#undef DOTMI_MERGE_TILES
-#undef DOTMI_MERGE_PSUB
+    merge_dispatch(ctl != nullptr, a.co, [&](auto dev, auto c) {
+        constexpr bool DEV = decltype(dev)::value, COARSE = decltype(c)::on;
+        if (P.mt_ptr)   // (launch_gemv left the tile partials in ppart and skipped the reduce)
+            hipLaunchKernelGGL((merge_tiles_kernel<DEV, COARSE>), dim3(NB_RED), dim3(256), 0, st, 3 * M.nV, P.mt_ptr, P.mt_ent, P.dup,
+                               P.ppart, L, (int)a.dots, (int)a.divide, a.z, a.partials, ctl, a.vl, P.mt_wave, P.mt_il, c);
+        else
+            hipLaunchKernelGGL((merge_kernel<DEV, COARSE>), dim3(NB_RED), dim3(256), 0, st, M.nV, P.vp_ptr, P.vp_off, P.dup, P.psub, L,
+                               (int)a.dots, (int)a.divide, a.z, a.partials, ctl, a.vl, c);
+    });
 }
 
 // Sharded subdomains: z holds the all-reduced SUM over every subdomain; z_v /= dup_v and the partial dots c_i = y_i . z,
@@ -1069,19 +945,9 @@ __global__ __launch_bounds__(256) void zfinish_kernel(int nV, const int *__restr
                                                       const DevLoop *__restrict__ ctl, MergeCoarse<COARSE> co)
 {
     __shared__ double sm[4 * RED_K];
-    if constexpr (DEV) {
-        if (ctl->status != 0 || ctl->phase != 0) return;
-    }
-    double *ysh = nullptr;
-    if constexpr (COARSE) {
-        __shared__ double ybuf[COARSE_NC_MAX];
-        ysh = ybuf;
-        coarse_load_y(co, ysh);
-    }
-    const LbfgsArgs &Lr = [&]() -> const LbfgsArgs & {
-        if constexpr (DEV) return ctl->L;
-        else return L;
-    }();
+    if (merge_gated_off<DEV>(ctl)) return;
+    double *ysh = merge_coarse_y(co);
+    const LbfgsArgs &Lr = loop_history<DEV>(ctl, L);
     double acc[RED_K];
 #pragma unroll
     for (int j = 0; j < RED_K; ++j) acc[j] = 0.0;
@@ -1117,16 +983,10 @@ __global__ __launch_bounds__(256) void zfinish_kernel(int nV, const int *__restr
 void launch_zfinish(int nV, const int *dup, const LbfgsArgs &L, double *z, double *partials, hipStream_t st,
                     const DevLoop *ctl, const CoarseMerge *co)
 {
-#define DOTMI_ZFINISH(DEV, COARSE, ...)                                                                                                 \
-    hipLaunchKernelGGL((zfinish_kernel<DEV, COARSE>), dim3(NB_RED), dim3(256), 0, st, nV, dup, L, z, partials, ctl, __VA_ARGS__)
-    if (ctl) {
-        if (co) DOTMI_ZFINISH(true, true, merge_coarse(co));
-        else DOTMI_ZFINISH(true, false, MergeCoarse<false>());
-    } else {
-        if (co) DOTMI_ZFINISH(false, true, merge_coarse(co));
-        else DOTMI_ZFINISH(false, false, MergeCoarse<false>());
-    }
-#undef DOTMI_ZFINISH
+    merge_dispatch(ctl != nullptr, co, [&](auto dev, auto c) {
+        hipLaunchKernelGGL((zfinish_kernel<decltype(dev)::value, decltype(c)::on>), dim3(NB_RED), dim3(256), 0, st, nV, dup, L, z,
+                           partials, ctl, c);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
