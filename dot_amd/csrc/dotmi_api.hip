@@ -130,11 +130,10 @@ int dotmi_eval_energy(dotmi_handle *h, const double *x, double *E)
     HIPCHECK(h, hipSetDevice(h->device));
     if (resolve_refresh(h) == DOTMI_E_DEVICE) return DOTMI_E_DEVICE;   // (asynchronous refresh of the last step)
     if (int rc = upload_tmp(h, x, h->x_trial)) return rc;
-    int nb = 0;
-    launch_elem_energy_grad(h->M, h->PTall, h->mat, h->dtSq, h->x_trial, h->xt, 0, h->nV, 0, h->partE,
-                            &nb, h->st);
+    const int nb = eval_all_elements(h, h->x_trial, 0);
     HIPCHECK(h, hipMemcpyAsync(h->h_partE, h->partE, sizeof(double) * 2 * nb, hipMemcpyDeviceToHost, h->st));
     HIPCHECK(h, hipStreamSynchronize(h->st));
+    // (left to right, not energy_of_partials' chunks: this entry's sum keeps the order it has always had, bit for bit)
     double se = 0, si = 0;
     for (int b = 0; b < nb; ++b) {
         se += h->h_partE[2 * b];
@@ -150,20 +149,7 @@ int dotmi_eval_gradient(dotmi_handle *h, const double *x, double *g)
     HIPCHECK(h, hipSetDevice(h->device));
     if (resolve_refresh(h) == DOTMI_E_DEVICE) return DOTMI_E_DEVICE;   // (asynchronous refresh of the last step)
     if (int rc = upload_tmp(h, x, h->x_trial)) return rc;
-    int nb = 0;
-    launch_elem_energy_grad(h->M, h->PTall, h->mat, h->dtSq, h->x_trial, h->xt, 0, h->nV, 1, h->partE,
-                            &nb, h->st);
-    GatherArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = h->x_trial;
-    a.xt = h->xt;
-    a.g_new = h->g_trial;
-    a.make_pair = 0;
-    a.iv0 = 0;
-    a.iv1 = h->nV;
-    LbfgsArgs L;
-    memset(&L, 0, sizeof(L));
-    launch_vertex_gather(h->M, h->PTall, a, L, h->partR, h->st);
+    eval_all_elements(h, h->x_trial, 1);
     HIPCHECK(h, hipMemcpyAsync(g, h->g_trial, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->st));
     HIPCHECK(h, hipStreamSynchronize(h->st));
     return 0;
@@ -210,13 +196,11 @@ int dotmi_apply_precond(dotmi_handle *h, const double *r, double *p)
     if (int rc = enter_with_factors(h)) return rc;
     if (int rc = dot_coarse_refresh(h)) return rc;   // (dotmi_set_dot_coarse: nothing unless the mode is on and A0 is stale)
     if (int rc = upload_tmp(h, r, h->q)) return rc;
-    LbfgsArgs L;
-    memset(&L, 0, sizeof(L));
     if (h->pd) {
-        if (int rc = pd_apply(h, h->q, h->z, L)) return rc;
+        if (int rc = pd_apply(h, h->q, h->z, NO_HISTORY)) return rc;
     } else if (h->hi) {
-        if (int rc = ic_apply(h, h->q, h->z, L)) return rc;
-    } else if (int rc = apply_precond(h, h->q, h->z, L)) return rc;
+        if (int rc = ic_apply(h, h->q, h->z, NO_HISTORY)) return rc;
+    } else if (int rc = apply_precond(h, h->q, h->z, NO_HISTORY)) return rc;
     HIPCHECK(h, hipMemcpyAsync(p, h->z, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->st));
     HIPCHECK(h, hipStreamSynchronize(h->st));
     return 0;
@@ -253,24 +237,13 @@ int dotmi_probe_direction(dotmi_handle *h, const double *x, int32_t m, const dou
         HIPCHECK(h, hipMemcpyAsync(h->S[i], S + (size_t)i * n, bytes, hipMemcpyHostToDevice, h->st));
         HIPCHECK(h, hipMemcpyAsync(h->Y[i], Y + (size_t)i * n, bytes, hipMemcpyHostToDevice, h->st));
     }
-    int nb = 0;
-    launch_elem_energy_grad(h->M, h->PTall, h->mat, h->dtSq, h->tmpn, h->xt, 0, h->nV, 1, h->partE, &nb,
-                            h->st);
-    GatherArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = h->tmpn;
-    a.xt = h->xt;
-    a.g_new = h->g_trial;
-    a.iv0 = 0;
-    a.iv1 = h->nV;
-    LbfgsArgs L;
-    memset(&L, 0, sizeof(L));
-    launch_vertex_gather(h->M, h->PTall, a, L, h->partR, h->st);
+    eval_all_elements(h, h->tmpn, 1);
     std::vector<double> g(n);
     HIPCHECK(h, hipMemcpyAsync(g.data(), h->g_trial, bytes, hipMemcpyDeviceToHost, h->st));
     HIPCHECK(h, hipStreamSynchronize(h->st));
     // Gram matrix and the first half of the two-loop on the host (the running loop gets the same numbers from the
     // gather kernel's partial sums)
+    LbfgsArgs L{};
     L.m = m;
     double b[HIST_MAX] = {0}, xi[HIST_MAX];
     auto dot = [&](const double *u, const double *v) {
@@ -290,9 +263,11 @@ int dotmi_probe_direction(dotmi_handle *h, const double *x, int32_t m, const dou
     if (int rc = apply_precond(h, h->q, h->z, L)) return rc;
     launch_build_p(n, h->z, L, h->partC, xi, h->p, h->st);
     launch_spmv_dots(h->M, h->Hval, h->p, h->g_trial, nullptr, 0, h->nV, h->partS, h->st);
-    launch_step_forward(n, h->tmpn, h->p, h->x_trial, h->partS, 0.0, 1, h->alphaMin, h->alpha_dev, h->h_alpha, h->st);
-    launch_elem_energy_grad(h->M, h->PTall, h->mat, h->dtSq, h->x_trial, h->xt, 0, h->nV, 0, h->partE, &nb,
-                            h->st);
+    StepForwardArgs f = step_forward_args(h, h->partS);
+    f.x0 = h->tmpn;
+    f.alpha_out_host = h->h_alpha;
+    launch_step_forward(n, f, h->st);
+    const int nb = eval_all_elements(h, h->x_trial, 0);
     HIPCHECK(h, hipMemcpyAsync(h->h_partE, h->partE, sizeof(double) * 2 * nb, hipMemcpyDeviceToHost, h->st));
     if (g_out) memcpy(g_out, g.data(), bytes);
     if (q_out) HIPCHECK(h, hipMemcpyAsync(q_out, h->q, bytes, hipMemcpyDeviceToHost, h->st));
@@ -300,11 +275,7 @@ int dotmi_probe_direction(dotmi_handle *h, const double *x, int32_t m, const dou
     if (p_out) HIPCHECK(h, hipMemcpyAsync(p_out, h->p, bytes, hipMemcpyDeviceToHost, h->st));
     HIPCHECK(h, hipStreamSynchronize(h->st));
     if (alpha0) *alpha0 = h->h_alpha[0];
-    if (E_trial) {
-        const double se = chunked_sum(nb, [&](int k) { return h->h_partE[2 * k]; });
-        const double si = chunked_sum(nb, [&](int k) { return h->h_partE[2 * k + 1]; });
-        *E_trial = h->dtSq * se + si;
-    }
+    if (E_trial) *E_trial = energy_of_partials(h, nb);
     return 0;
 }
 
@@ -494,32 +465,32 @@ int dotmi_bench_kernel(dotmi_handle *h, int32_t kind, int32_t reps, double *ms_p
         L.y[i] = h->Y[i];
         if (L.ys[i] == 0.0) L.ys[i] = 1.0;
     }
-    int nb = 0;
     int64_t bytes = 0;
     bool live = false;   // the kernel form reads the device loop's state
     std::function<void()> run;
-    GatherArgs a;
-    memset(&a, 0, sizeof(a));
+    // The operands come from the loop's own builders (dotmi_handle.hpp), in the form of a handle without a sharded element pass: on one
+    // that has it, the loop's stages contain collectives, which are not priced here
+    StepElemPass e = step_elem_pass(h, h->x, 1, false);
+    const StepArgs sa{h->p, h->partS, h->alpha_dev, h->alphaMin};
+    GatherArgs a = gather_args(h);
     a.x = h->x;
-    a.xt = h->xt;
     a.g_old = h->g;
     a.p = h->p;
     a.alpha_dev = h->alpha_dev;
     a.g_new = h->g_trial;
     a.s_new = h->S[h->hist];
     a.y_new = h->Y[h->hist];
-    a.iv0 = h->v0;
-    a.iv1 = h->v1;
     a.make_pair = 1;
     double xi[HIST_MAX] = {0, 0, 0, 0, 0, 0};
     switch (kind) {
     case DOTMI_BENCH_ELEM_ENERGY_GRAD:   // 112 nT + 56 nV: energy evaluation incl. inertia (the gradient entries stay on chip)
         bytes = 112 * nTo + 56 * nVo;
-        run = [&] { launch_elem_energy_grad(h->M, h->PT, h->mat, h->dtSq, h->x, h->xt, h->v0, h->v1, 1, h->partE, &nb, h->st); };
+        run = [&] { launch_elem_pass(e.M, h->PT, h->mat, h->dtSq, e.a, h->st); };
         break;
     case DOTMI_BENCH_ELEM_ENERGY:        // 112 nT + 56 nV
         bytes = 112 * nTo + 56 * nVo;
-        run = [&] { launch_elem_energy_grad(h->M, h->PT, h->mat, h->dtSq, h->x, h->xt, h->v0, h->v1, 0, h->partE, &nb, h->st); };
+        e.a.grad = 0;
+        run = [&] { launch_elem_pass(e.M, h->PT, h->mat, h->dtSq, e.a, h->st); };
         break;
     case DOTMI_BENCH_VERTEX_GATHER:      // g write + x, x~, m read (80 nV) + pair: g_old, p read, s, y write + 2m history vectors
         bytes = 80 * (int64_t)nV + (int64_t)(4 + 2 * L.m) * 8 * n;
@@ -551,7 +522,7 @@ int dotmi_bench_kernel(dotmi_handle *h, int32_t kind, int32_t reps, double *ms_p
         break;
     case DOTMI_BENCH_STEP_FORWARD:       // x, p read, x_trial written
         bytes = 8 * (int64_t)n * 3;
-        run = [&] { launch_step_forward(n, h->x, h->p, h->x_trial, h->partS, 0.0, 1, h->alphaMin, h->alpha_dev, nullptr, h->st); };
+        run = [&] { launch_step_forward(n, step_forward_args(h, h->partS), h->st); };
         break;
     case DOTMI_BENCH_ELEM_HESSIAN:       // 112 nT in, 1152 nT out
         if (h->world > 1) return DOTMI_E_INVALID;   // (the refresh re-issued below ends in a collective: not from one rank alone)
@@ -577,10 +548,7 @@ int dotmi_bench_kernel(dotmi_handle *h, int32_t kind, int32_t reps, double *ms_p
     case DOTMI_BENCH_SPMV_ZP:            // 72 nnzb + z, g read, p, Hp written, m pairs of (s_j, H s_j) read
         bytes = 72 * (int64_t)h->M.nnzb + 8 * (int64_t)n * (4 + 2 * L.m);
         live = true;
-        run = [&] {
-            launch_spmv_zp(h->M, h->Hval, h->z, h->dist ? h->partC : h->partCT, h->p, h->Hp, h->partS, h->st, h->ctl, 0, -1, nullptr,
-                           nullptr, VList(), !h->dist);
-        };
+        run = [&] { launch_spmv_zp(h->M, spmv_zp_args(h, false), h->st, h->ctl); };
         break;
     case DOTMI_BENCH_MERGE_EARLY:        // tile partials + u_old read / written, z written, M y_new written, m x (y_j, M y_j) read
         bytes = 8 * (int64_t)h->mergeEntries + 8 * (int64_t)n * (4 + 2 * L.m);
@@ -593,11 +561,9 @@ int dotmi_bench_kernel(dotmi_handle *h, int32_t kind, int32_t reps, double *ms_p
     case DOTMI_BENCH_ELEM_STEP: {        // the element pass with the line-search step inside: + p read, trial point written
         bytes = 112 * nTo + 56 * nVo + 48 * (int64_t)nV;
         live = true;
-        run = [&] {
-            StepArgs sa{h->p, h->partS, h->alpha_dev, h->alphaMin};
-            launch_elem_energy_grad(h->M, h->PT, h->mat, h->dtSq, h->x_trial, h->xt, h->v0, h->v1, 1, h->partE, &nb, h->st, h->ctl,
-                                    h->tune.fuseStep ? &sa : nullptr);
-        };
+        e.a.x = h->x_trial;
+        if (h->tune.fuseStep) e.a.step = &sa;
+        run = [&] { launch_elem_pass(e.M, h->PT, h->mat, h->dtSq, e.a, h->st, h->ctl); };
         break;
     }
     case DOTMI_BENCH_GATHER_EARLY: {     // + H p read, H s_new written, -g into the padded right-hand sides of every holder
@@ -605,15 +571,7 @@ int dotmi_bench_kernel(dotmi_handle *h, int32_t kind, int32_t reps, double *ms_p
         for (int v = 0; v < nV; ++v) held += h->dup[v];
         bytes = 80 * (int64_t)nV + (int64_t)(6 + 2 * L.m) * 8 * n + 24 * held;
         live = true;
-        a.x = nullptr;
-        a.g_old = nullptr;
-        a.g_new = nullptr;
-        a.s_new = nullptr;
-        a.y_new = nullptr;
-        a.hp = h->tune.fuseDir ? h->Hp : nullptr;
-        a.vp_ptr = h->P.vp_ptr;
-        a.vp_off = h->P.vp_off;
-        a.rpad = h->P.rpad;
+        a = early_gather_args(h);
         run = [&] { launch_vertex_gather(h->M, h->PT, a, L, h->partR, h->st, h->ctl); };
         break;
     }
@@ -633,11 +591,9 @@ int dotmi_bench_kernel(dotmi_handle *h, int32_t kind, int32_t reps, double *ms_p
         if (h->dist || !h->specFits) return DOTMI_E_INVALID;
         bytes = 72 * (int64_t)h->M.nnzb + 8 * (int64_t)n * (4 + 2 * L.m) + 112 * nTo + 56 * nVo + 24 * (int64_t)nV;
         live = true;
-        run = [&] {
-            StepArgs sa{h->p, h->partS, h->alpha_dev, h->alphaMin};
-            launch_dirstep(h->M, h->PTspec, h->mat, h->dtSq, h->xt, h->partE, &nb, h->Hval, h->z, h->partCT, h->p, h->Hp, h->partS, h->st,
-                           h->ctl, sa);
-        };
+        e.a.x = h->x_trial;
+        e.a.step = &sa;
+        run = [&] { launch_dirstep(e.M, h->PTspec, h->mat, h->dtSq, spmv_zp_args(h, false), e.a, h->st, h->ctl); };
         break;
     }
     default:
@@ -679,11 +635,10 @@ int dotmi_bench_energy(dotmi_handle *h, int32_t reps, double *ms_per_launch, int
     if (!h || reps < 1) return DOTMI_E_INVALID;
     HIPCHECK(h, hipSetDevice(h->device));
     if (resolve_refresh(h) == DOTMI_E_DEVICE) return DOTMI_E_DEVICE;   // (asynchronous refresh of the last step)
-    int nb = 0;
-    launch_elem_energy_grad(h->M, h->PT, h->mat, h->dtSq, h->x, h->xt, h->v0, h->v1, 0, h->partE, &nb, h->st);
+    const StepElemPass e = step_elem_pass(h, h->x, 0, false);
+    launch_elem_pass(e.M, h->PT, h->mat, h->dtSq, e.a, h->st);
     HIPCHECK(h, hipEventRecord(h->ev0, h->st));
-    for (int i = 0; i < reps; ++i)
-        launch_elem_energy_grad(h->M, h->PT, h->mat, h->dtSq, h->x, h->xt, h->v0, h->v1, 0, h->partE, &nb, h->st);
+    for (int i = 0; i < reps; ++i) launch_elem_pass(e.M, h->PT, h->mat, h->dtSq, e.a, h->st);
     HIPCHECK(h, hipEventRecord(h->ev1, h->st));
     HIPCHECK(h, hipEventSynchronize(h->ev1));
     float ms = 0;

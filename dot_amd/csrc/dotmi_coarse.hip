@@ -358,14 +358,12 @@ int dotmi_pcg_apply_precond(dotmi_handle *h, const double *r, double *w)
     if (int rc = enter_with_factors(h)) return rc;
     if (int rc = coarse_refresh(h)) return rc;
     const bool coarse = h->coarse.mode != 0 && h->coarse.active;
-    LbfgsArgs L0;
-    memset(&L0, 0, sizeof(L0));
     HIPCHECK(h, hipMemcpyAsync(h->tmpn, r, sizeof(double) * h->n, hipMemcpyHostToDevice, h->st));
     launch_coarse_scale(h->n, h->tmpn, h->pcg.isd, h->q, h->st);          // q = r (.) isd
     const Bracket br = backsolve_bracket(h);
     if (coarse) coarse_restrict_solve(h, h->tmpn);
     launch_gemv(h->P, h->q, h->st, nullptr, br.ev0, br.ev1);
-    launch_merge(h->M, h->P, L0, {.z = h->z}, h->st);                     // zsum = S q
+    launch_merge(h->M, h->P, NO_HISTORY, {.z = h->z}, h->st);             // zsum = S q
     if (coarse) coarse_prolong(h, h->z);
     launch_coarse_scale(h->n, h->z, h->pcg.isd, h->tmpn, h->st);          // w = zsum (.) isd, as pcg_spmv_kernel forms it
     HIPCHECK(h, hipMemcpyAsync(w, h->tmpn, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->st));

@@ -17,20 +17,14 @@ static int slot_direction(dotmi_handle *h, Slot &s)
     if (h->specNow) {
         // the direction kernel and the first trial's element pass at the unit step in ONE launch (k_dirstep.hip); a retry slot:
         // the element pass alone, on the stored p with the controller's alpha
-        StepArgs sa{h->p, h->partS, h->alpha_dev, h->alphaMin};
-        launch_dirstep(h->M, h->PTspec, h->mat, h->dtSq, h->xt, h->partE, &s.nb, h->Hval, h->z, h->partCT, h->p, h->Hp, h->partS, h->st,
-                       h->ctl, sa);
-    } else if (h->owner) {
-        launch_spmv_zp(h->M, h->HvalOwn, h->z, h->partGC, h->p, h->Hp, h->partS, h->st, h->ctl, 0, -1, h->heldMask, h->ownMask,
-                       h->held());
-    } else if (h->tune.fuseDir) {   // build_p + spmv_dots in one launch, H p from the cached H s_j
-        // (one rank: the y_i . z partials from their column-major twin, which merge_early writes beside the rows)
-        launch_spmv_zp(h->M, h->Hval, h->z, h->dist ? h->partC : h->partCT, h->p, h->Hp, h->partS, h->st, h->ctl,
-                       h->shardElems ? h->v0 : 0, h->shardElems ? h->v1 : -1, nullptr, nullptr, VList(), !h->dist, h->partST);
+        const StepArgs sa{h->p, h->partS, h->alpha_dev, h->alphaMin};
+        StepElemPass e = step_elem_pass(h, h->x_trial, 1);
+        e.a.step = &sa;
+        s.nb = launch_dirstep(e.M, h->PTspec, h->mat, h->dtSq, spmv_zp_args(h), e.a, h->st, h->ctl);
+    } else if (h->owner || h->tune.fuseDir) {   // build_p + spmv_dots in one launch, H p from the cached H s_j
+        launch_spmv_zp(h->M, spmv_zp_args(h), h->st, h->ctl);
     } else {
-        LbfgsArgs L0;
-        memset(&L0, 0, sizeof(L0));
-        launch_build_p(h->n, h->z, L0, h->partC, nullptr, h->p, h->st, h->ctl);
+        launch_build_p(h->n, h->z, NO_HISTORY, h->partC, nullptr, h->p, h->st, h->ctl);
         launch_spmv_dots(h->M, h->Hval, h->p, h->g, nullptr, h->v0, h->v1, h->partS, h->st, h->ctl);
     }
     // (sharded element pass: the two sums cannot ride on the z all-reduce in front of them -- p.Hp is quadratic in the reduced
@@ -41,7 +35,6 @@ static int slot_direction(dotmi_handle *h, Slot &s)
 // stage 2, trial: the step x_trial = x_cur + alpha p and the element pass there
 static void slot_trial(dotmi_handle *h, Slot &s)
 {
-    const bool ow = h->owner;
     // (not on meshes whose workgroups walk several patches: the prefetched operands leave no registers for it)
     // (sharded element pass: the fused form writes the trial point only on this rank's vertex slice -- its inertia loop --,
     // so the step stays a launch of its own there)
@@ -54,17 +47,18 @@ static void slot_trial(dotmi_handle *h, Slot &s)
         if (h->pairNow) ea.alpha_min = -h->alphaMin;   // (negative: a paired launch, as StepArgs::alpha_min)
         launch_elem_vertex(h->VP, h->mat, ea, h->st, h->ctl);
         s.nb = h->VP.nPatches;
-    } else if (h->tune.fuseStep && (!h->shardElems || ow)) {   // the step inside the element pass
-        StepArgs sa{h->p, s.spart, h->alpha_dev, h->pairNow ? -h->alphaMin : h->alphaMin};   // (negative: a paired launch)
-        // (a step with paired trials takes the PAIR instantiations of these two launches)
-        (h->pairNow ? launch_elem_energy_grad_pair : launch_elem_energy_grad)(
-            ow ? h->Mown : h->M, h->PT, h->mat, h->dtSq, h->x_trial, h->xt, ow ? 0 : h->v0, ow ? h->nV : h->v1, 1, h->partE, &s.nb,
-            h->st, h->ctl, &sa);
     } else {
-        launch_step_forward(h->n, h->x, h->p, h->x_trial, s.spart, 0.0, 1, h->alphaMin, h->alpha_dev, nullptr, h->st, h->ctl,
-                            h->held());
-        launch_elem_energy_grad(ow ? h->Mown : h->M, h->PT, h->mat, h->dtSq, h->x_trial, h->xt, ow ? 0 : h->v0, ow ? h->nV : h->v1,
-                                1, h->partE, &s.nb, h->st, h->ctl);
+        StepElemPass e = step_elem_pass(h, h->x_trial, 1);
+        const StepArgs sa{h->p, s.spart, h->alpha_dev, h->pairNow ? -h->alphaMin : h->alphaMin};   // (negative: a paired launch)
+        if (h->tune.fuseStep && (!h->shardElems || h->owner)) {   // the step inside the element pass
+            e.a.step = &sa;
+            e.a.pair = h->pairNow;   // (a step with paired trials takes the PAIR instantiations)
+        } else {
+            StepForwardArgs f = step_forward_args(h, s.spart);
+            f.vl = h->held();
+            launch_step_forward(h->n, f, h->st, h->ctl);
+        }
+        s.nb = launch_elem_pass(e.M, h->PT, h->mat, h->dtSq, e.a, h->st, h->ctl);
     }
 }
 
@@ -73,20 +67,11 @@ static void slot_trial(dotmi_handle *h, Slot &s)
 static int slot_gradient(dotmi_handle *h, Slot &s)
 {
     const int n = h->n;
-    LbfgsArgs L0;
-    memset(&L0, 0, sizeof(L0));
-    GatherArgs a = gather_args(h);
-    a.p = h->p;
-    a.alpha_dev = h->alpha_dev;
-    a.make_pair = 1;
-    a.hp = (h->tune.fuseDir || h->owner) ? h->Hp : nullptr;   // H s_new = alpha H p beside s_new
-    a.vp_ptr = h->P.vp_ptr;
-    a.vp_off = h->P.vp_off;
-    a.rpad = h->P.rpad;
+    const GatherArgs a = early_gather_args(h);
     s.ctlE = h->partE;
     if (h->vpNow) {
     } else if (!h->shardElems) {
-        launch_vertex_gather(h->M, h->stepPT(), a, L0, h->partR, h->st, h->ctl);
+        launch_vertex_gather(h->M, h->stepPT(), a, NO_HISTORY, h->partR, h->st, h->ctl);
     } else if (h->owner) {
         // Owner exchange, the statistics in the gradient's packet.  The gradient is complete on the vertices only this rank
         // holds: the gather forms the pair, the right-hand sides and the statistics there as on one GPU; on the shared vertices
@@ -100,28 +85,18 @@ static int slot_gradient(dotmi_handle *h, Slot &s)
         ag.kind = h->vkind;
         ag.pre = 1;
         ag.gshare = h->gstage;
-        launch_vertex_gather(h->M, h->PT, ag, L0, h->partR, h->st, h->ctl);
+        launch_vertex_gather(h->M, h->PT, ag, NO_HISTORY, h->partR, h->st, h->ctl);
         if (int rc = exchange_gradient_packed(h, n, s.nb, h->partR, RED_K)) return rc;
         ag.vlist = h->sharedList;
         ag.nlist = h->nShared;
         ag.pre = 0;
-        if (h->nShared > 0) launch_pair_stats(n, ag, L0, nullptr, h->st, h->gstage, h->ctl);
+        if (h->nShared > 0) launch_pair_stats(n, ag, NO_HISTORY, nullptr, h->st, h->gstage, h->ctl);
         s.ctlE = h->gstage + n;   // the controller reads the energy as one block (0, E)
         s.nb = 1;
     } else {
         // this rank's partial gradient and energy to the staging buffer [g (n) ; 0 ; E_local], one all-reduce, then the pair,
         // its statistics, -g into the right-hand sides and H s_new from the SUM (pair_stats)
-        GatherArgs ag = a;
-        ag.make_pair = 0;
-        ag.stage = 1;
-        ag.g_new = h->gstage;
-        ag.hp = nullptr;
-        ag.vp_ptr = ag.vp_off = nullptr;
-        ag.rpad = nullptr;
-        launch_vertex_gather(h->M, h->PT, ag, L0, h->partR, h->st, h->ctl);
-        stage_energy(h, s.nb, h->gstage + n + 1);
-        if (int rc = allreduce_sum(h, h->gstage, (size_t)n + 2)) return rc;
-        launch_pair_stats(n, a, L0, h->partR, h->st, h->gstage, h->ctl);
+        if (int rc = gradient_over_ranks(h, s.nb, a)) return rc;
         s.ctlE = h->gstage + n;   // the controller reads the energy as one block (0, E)
         s.nb = 1;
     }
@@ -165,9 +140,7 @@ static int slot_merge(dotmi_handle *h)
         // DOTMI_FLAG_DOT_COARSE: the packet is [zsum (n) ; c (nc)] -- slot_coarse has left this rank's part of c = Z^T (-g_trial) in the
         // tail --, every rank solves A0 y = c on the summed tail behind the collective (gated like the merge that reads y: the
         // controller has spoken by now) and the zsum branch of the merge adds Z y behind the division
-        LbfgsArgs L0;
-        memset(&L0, 0, sizeof(L0));
-        return merge_over_ranks(h, L0, h->zstage, RANKSUM_EARLY, h->ctl, h->held());
+        return merge_over_ranks(h, NO_HISTORY, h->zstage, RANKSUM_EARLY, h->ctl, h->held());
     } else {
         // owner exchange: merge_early merges the tiles itself.
         // zstage: this rank's subdomains' sum, zero on the vertices it does not hold; only the shared vertices' entries
@@ -209,9 +182,7 @@ static int enqueue_loop_slot(dotmi_handle *h)
 {
     if (h->earlyNow) return enqueue_loop_slot_early(h);
     const int n = h->n;
-    LbfgsArgs L0;
-    memset(&L0, 0, sizeof(L0));
-    launch_build_qpad(h->P, h->g, L0, nullptr, h->st, h->ctl);   // q, straight into the padded right-hand sides
+    launch_build_qpad(h->P, h->g, NO_HISTORY, nullptr, h->st, h->ctl);   // q, straight into the padded right-hand sides
     const CoarseMerge *co = dot_coarse(h);
     // dotmi_set_dot_coarse: y = A0^-1 Z^T q, gated like the back-solve (sharded subdomains: the restriction into the tail of z's
     // packet here, the solve behind the collective below)
@@ -221,41 +192,32 @@ static int enqueue_loop_slot(dotmi_handle *h)
     h->slotTimed.push_back(br.at);
     launch_gemv(h->P, nullptr, h->st, h->ctl, br.ev0, br.ev1);
     if (!h->dist) {
-        launch_merge(h->M, h->P, L0, {.z = h->z, .partials = h->partC, .dots = true, .divide = true, .co = co}, h->st, h->ctl);
+        launch_merge(h->M, h->P, NO_HISTORY, {.z = h->z, .partials = h->partC, .dots = true, .divide = true, .co = co}, h->st, h->ctl);
     } else {
         // sharded subdomains: the one collective of an iteration, enqueued like a kernel.  It runs in every slot (also
         // in retries and past the end, where the kernels around it return at once), so every rank issues the same
         // sequence of collectives whatever the controller decides
-        if (int rc = merge_over_ranks(h, L0, h->z, RANKSUM_ZFINISH, h->ctl)) return rc;
+        if (int rc = merge_over_ranks(h, NO_HISTORY, h->z, RANKSUM_ZFINISH, h->ctl)) return rc;
     }
-    launch_build_p(n, h->z, L0, h->partC, nullptr, h->p, h->st, h->ctl);
+    launch_build_p(n, h->z, NO_HISTORY, h->partC, nullptr, h->p, h->st, h->ctl);
     launch_spmv_dots(h->M, h->Hval, h->p, h->g, nullptr, h->v0, h->v1, h->partS, h->st, h->ctl);
     const double *spart = nullptr;
     if (int rc = reduce_step_dots(h, &spart)) return rc;
-    launch_step_forward(n, h->x, h->p, h->x_trial, spart, 0.0, 1, h->alphaMin, h->alpha_dev, nullptr, h->st, h->ctl);
-    int nb = 0;
-    launch_elem_energy_grad(h->M, h->PT, h->mat, h->dtSq, h->x_trial, h->xt, h->v0, h->v1, 1, h->partE, &nb, h->st, h->ctl);
+    launch_step_forward(n, step_forward_args(h, spart), h->st, h->ctl);
+    const StepElemPass e = step_elem_pass(h, h->x_trial, 1);
+    const int nb = launch_elem_pass(e.M, h->PT, h->mat, h->dtSq, e.a, h->st, h->ctl);
     GatherArgs a = gather_args(h);
     a.p = h->p;
     a.alpha_dev = h->alpha_dev;
+    a.make_pair = 1;
     if (!h->shardElems) {
-        a.make_pair = 1;
-        launch_vertex_gather(h->M, h->PT, a, L0, h->partR, h->st, h->ctl);
+        launch_vertex_gather(h->M, h->PT, a, NO_HISTORY, h->partR, h->st, h->ctl);
         launch_loop_control(h->ctl, h->partE, nb, h->partR, h->alpha_dev, h->h_flags, h->st);
         return 0;
     }
-    // sharded element pass: the partial gradient of this rank's elements and its energy go to the staging buffer
-    // [g (n) ; 0 ; E_local], one all-reduce, then the pair + statistics from the summed gradient (which is copied to
-    // the trial gradient, whose address only the controller knows).  The controller reads the energy as one "block"
-    // (0, E): dtSq * 0 + E.
-    a.make_pair = 0;
-    a.stage = 1;
-    a.g_new = h->gstage;
-    launch_vertex_gather(h->M, h->PT, a, L0, h->partR, h->st, h->ctl);
-    stage_energy(h, nb, h->gstage + n + 1);
-    if (int rc = allreduce_sum(h, h->gstage, (size_t)n + 2)) return rc;
-    a.make_pair = 1;
-    launch_pair_stats(n, a, L0, h->partR, h->st, h->gstage, h->ctl);
+    // sharded element pass: the gradient and the energy summed over the ranks, the pair + statistics from the sum (no right-hand
+    // sides, no H s_new in this order).  The controller reads the energy as one "block" (0, E): dtSq * 0 + E.
+    if (int rc = gradient_over_ranks(h, nb, a)) return rc;
     launch_loop_control(h->ctl, h->gstage + n, 1, h->partR, h->alpha_dev, h->h_flags, h->st);
     return 0;
 }
@@ -343,8 +305,6 @@ static int init_devloop(dotmi_handle *h, int *notifyFrom)
 static int step_start_sharded(dotmi_handle *h, int nb)
 {
     const int n = h->n;
-    LbfgsArgs L0;
-    memset(&L0, 0, sizeof(L0));
     const double *ctlR = h->partR;
     if (!h->owner) {
         stage_energy(h, nb, h->gstage + n + 1);
@@ -367,13 +327,13 @@ static int step_start_sharded(dotmi_handle *h, int nb)
     }
     // early order on the sharded element pass: -g_0 (the summed gradient) into this rank's right-hand sides, the
     // first direction's solve with the start-of-step controller inside its launch, the sum over the ranks, z = u
-    launch_build_qpad(h->P, h->g, L0, nullptr, h->st, nullptr);
+    launch_build_qpad(h->P, h->g, NO_HISTORY, nullptr, h->st, nullptr);
     const CoarseMerge *co = dot_coarse(h);   // (DOTMI_FLAG_DOT_COARSE, never with the owner exchange: as in slot_merge)
     if (co) dot_coarse_restrict(h, h->zstage + n);
     CtlLaunch ca{{h->ctl, h->gstage + n, ctlR, h->alpha_dev, h->h_flags, 1, 1}, CTL_PLAIN};
     launch_gemv(h->P, nullptr, h->st, h->ctl, nullptr, nullptr, &ca, 1 << 30);
-    if (!h->owner) return merge_over_ranks(h, L0, h->zstage, RANKSUM_EARLY_FIRST, h->ctl, h->held());
-    launch_merge(h->M, h->P, L0, {.z = h->zstage, .vl = h->held()}, h->st, h->ctl);
+    if (!h->owner) return merge_over_ranks(h, NO_HISTORY, h->zstage, RANKSUM_EARLY_FIRST, h->ctl, h->held());
+    launch_merge(h->M, h->P, NO_HISTORY, {.z = h->zstage, .vl = h->held()}, h->st, h->ctl);
     if (int rc = exchange_iface(h, h->zstage, nullptr, 0)) return rc;
     // (no pair yet: no y_i . z to sum, no partials)
     launch_merge_early(h->M, h->P, {.z = h->z, .first = 1, .zsum = h->zstage, .ownMask = h->ownMask, .vl = h->held()}, h->st, h->ctl);
@@ -385,17 +345,16 @@ static int step_start_sharded(dotmi_handle *h, int nb)
 // first direction's solve
 static int enqueue_step_start(dotmi_handle *h)
 {
-    int nb = 0;
+    int nb = h->VP.nPatches;
     if (h->vpNow) {
         // energy, gradient, |g|^2 and -g_0 in the padded right-hand sides from the one launch (no step, no pair: ctl == nullptr)
         ElemVertArgs ea = elem_vertex_args(h);
         ea.x0 = h->x;
         ea.g0 = h->g;
         launch_elem_vertex(h->VP, h->mat, ea, h->st, nullptr);
-        nb = h->VP.nPatches;
     } else {
-        launch_elem_energy_grad(h->owner ? h->Mown : h->M, h->stepPT(), h->mat, h->dtSq, h->x, h->xt, h->owner ? 0 : h->v0,
-                                h->owner ? h->nV : h->v1, 1, h->partE, &nb, h->st);
+        const StepElemPass e = step_elem_pass(h, h->x, 1);
+        nb = launch_elem_pass(e.M, h->stepPT(), h->mat, h->dtSq, e.a, h->st);
     }
     GatherArgs a = gather_args(h);
     a.x = h->x;
@@ -407,14 +366,12 @@ static int enqueue_step_start(dotmi_handle *h)
     // owner exchange: the loop only touches the held vertices' entries; the trial buffer starts as a copy of the iterate
     // (the two swap roles on every accepted trial and must agree off the held set)
     if (h->owner) HIPCHECK(h, hipMemcpyAsync(h->x_trial, h->x, sizeof(double) * h->n, hipMemcpyDeviceToDevice, h->st));
-    LbfgsArgs L0;
-    memset(&L0, 0, sizeof(L0));
     if (h->earlyNow && !h->shardElems) {   // -g_0 straight into the padded right-hand sides (their padding entries stay zero)
         a.vp_ptr = h->P.vp_ptr;
         a.vp_off = h->P.vp_off;
         a.rpad = h->P.rpad;
     }
-    if (!h->vpNow) launch_vertex_gather(h->M, h->stepPT(), a, L0, h->partR, h->st);
+    if (!h->vpNow) launch_vertex_gather(h->M, h->stepPT(), a, NO_HISTORY, h->partR, h->st);
     if (h->shardElems) return step_start_sharded(h, nb);
     if (!h->earlyNow) {
         launch_loop_control(h->ctl, h->partE, nb, h->partR, h->alpha_dev, h->h_flags, h->st, 1);
@@ -428,7 +385,7 @@ static int enqueue_step_start(dotmi_handle *h)
     // (no trial to judge yet: the plain controller, which only differs in how many rows of statistics there are)
     CtlLaunch ca{{h->ctl, h->partE, h->partR, h->alpha_dev, h->h_flags, nb, 1}, h->vpNow ? CTL_VP : CTL_PLAIN};
     launch_gemv(h->P, nullptr, h->st, h->ctl, nullptr, nullptr, &ca, 1 << 30);
-    if (h->dist) return merge_over_ranks(h, L0, h->zstage, RANKSUM_EARLY_FIRST, h->ctl);
+    if (h->dist) return merge_over_ranks(h, NO_HISTORY, h->zstage, RANKSUM_EARLY_FIRST, h->ctl);
     launch_merge_early(h->M, h->P, {.z = h->z, .partials = h->partC, .partialsT = h->partCT, .first = 1, .co = co}, h->st, h->ctl);
     return 0;
 }

@@ -440,8 +440,29 @@ int apply_precond(dotmi_handle *h, const double *q, double *z, const LbfgsArgs &
 Bracket backsolve_bracket(dotmi_handle *h);
 int reduce_step_dots(dotmi_handle *h, const double **spart);
 void stage_energy(dotmi_handle *h, int nb, double *dst);
-GatherArgs gather_args(const dotmi_handle *h);
+// The operand records of the loop's launches (dotmi_internal.hpp), built from the handle once; the call sites set what differs.
+// sharded = false: the form of a handle without a sharded element pass, whatever this one is (dotmi_bench_kernel: the sharded stages
+// contain collectives, which it does not price)
+inline constexpr LbfgsArgs NO_HISTORY{};   // for the launches that take no history, or the device loop's (ctl != nullptr)
+GatherArgs gather_args(const dotmi_handle *h);         // what every gather of a step has in common
+GatherArgs early_gather_args(const dotmi_handle *h);   // the early order's gather
 ElemVertArgs elem_vertex_args(const dotmi_handle *h);
+SpmvZpArgs spmv_zp_args(const dotmi_handle *h, bool sharded = true);   // the loop's direction kernel: owner exchange / one rank / sharded rows
+StepForwardArgs step_forward_args(const dotmi_handle *h, const double *spmv_partials, double alpha = 0.0);   // x_trial = x + alpha p
+// the running step's element pass at x: the mesh (owner exchange: every vertex, with the owner's share of the mass) and the record
+struct StepElemPass {
+    const DevMesh &M;
+    ElemPassArgs a;
+};
+StepElemPass step_elem_pass(const dotmi_handle *h, const double *x, int grad, bool sharded = true);
+// the evaluation entries: the element pass at x on ALL elements, whatever the handle shards (energy partials in h->partE, their block
+// count returned) and, with grad, its plain gather into h->g_trial
+int eval_all_elements(dotmi_handle *h, const double *x, int grad);
+// E = dtSq * sum(elastic) + sum(inertia) from nb blocks of energy partials in h->h_partE, in the canonical order (chunked_sum)
+double energy_of_partials(const dotmi_handle *h, int nb);
+// sharded element pass (no owner exchange): this rank's partial gradient and energy to the staging buffer, one all-reduce, the pair and
+// its statistics from the sum (`pair`: what pair_stats reads); the controller then reads the energy at h->gstage + n as one block
+int gradient_over_ranks(dotmi_handle *h, int nb, const GatherArgs &pair);
 // dotmi_devloop.hip
 int run_device_loop(dotmi_handle *h, LoopOut &r);
 

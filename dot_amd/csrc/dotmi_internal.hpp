@@ -371,10 +371,18 @@ struct CtlLaunch {
 // Launchers with a trailing `ctl` run in device-loop mode when it is non-null: operands that change from
 // iteration to iteration come from *ctl and the kernel returns at once when the loop has ended (or, for
 // the direction kernels, when the slot is a line-search retry).
-// x = x0 + alpha * p; alpha = alpha_scale * clamp(-pg/pHp) from SpMV partials when use_partials
-void launch_step_forward(int n, const double *x0, const double *p, double *x, const double *spmv_partials,
-                         double alpha_host, int use_partials, double alpha_min, double *alpha_out,
-                         double *alpha_out_host, hipStream_t st, const DevLoop *ctl = nullptr, VList vl = VList());
+// The operands of the loop's long launchers are host-side records (never kernel parameters): defaults in the struct, the call sites
+// name what differs; the builders of dotmi_handle.hpp fill them from the handle.
+// x = x0 + alpha * p; alpha = clamp(-pg/pHp) from the SpMV partials when there are any
+struct StepForwardArgs {
+    const double *x0 = nullptr, *p = nullptr;
+    double *x = nullptr;
+    const double *spmv_partials = nullptr;   // nullptr: step with `alpha`
+    double alpha = 0.0, alpha_min = 0.0;
+    double *alpha_out = nullptr, *alpha_out_host = nullptr;
+    VList vl;                                // owner exchange: the vertices visited
+};
+void launch_step_forward(int n, const StepForwardArgs &a, hipStream_t st, const DevLoop *ctl = nullptr);
 // element pass: partial energy sums (+ inertia) and, optionally, element gradients
 // grad != 0: the per-(patch, vertex) partial gradients go to PT.gpart (read by launch_vertex_gather)
 // step (device loop only): the line-search step x_trial = x_cur + alpha p is taken inside the element pass
@@ -389,13 +397,17 @@ struct StepArgs {
     // loop's kernels showed up as time -- profiles/r05_paired_trials.txt F.)
     double alpha_min;
 };
-void launch_elem_energy_grad(const DevMesh &M, const DevPatches &PT, int mat, double dtSq, const double *x,
-                             const double *xt, int v0, int v1, int grad, double *partials, int *nblocks_out,
-                             hipStream_t st, const DevLoop *ctl = nullptr, const StepArgs *step = nullptr);
-// the PAIR instantiation of the same launch (k_element.hip): StepArgs::alpha_min < 0 makes it a paired launch
-void launch_elem_energy_grad_pair(const DevMesh &M, const DevPatches &PT, int mat, double dtSq, const double *x,
-                                  const double *xt, int v0, int v1, int grad, double *partials, int *nblocks_out,
-                                  hipStream_t st, const DevLoop *ctl = nullptr, const StepArgs *step = nullptr);
+struct ElemPassArgs {
+    const double *x = nullptr, *xt = nullptr;
+    int v0 = 0, v1 = 0;             // vertex range whose inertia term this launch adds
+    int grad = 0;
+    double *partials = nullptr;
+    const StepArgs *step = nullptr;
+    bool pair = false;              // the PAIR instantiations (a step with paired trials): StepArgs::alpha_min < 0 makes it a paired launch
+};
+// returns the blocks of energy partials written
+int launch_elem_pass(const DevMesh &M, const DevPatches &PT, int mat, double dtSq, const ElemPassArgs &a, hipStream_t st,
+                     const DevLoop *ctl = nullptr);
 // vertex gather of element gradients + inertia; optional L-BFGS pair + stats partials
 struct GatherArgs {
     const double *x, *xt, *g_old, *p, *alpha_dev;
@@ -442,12 +454,7 @@ void launch_gemv(const DevParts &P, const double *q, hipStream_t st, const DevLo
                  hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, const CtlLaunch *ca = nullptr, int spec = 0);
 // (a.alpha_min < 0: a PAIRED launch -- twice as many workgroups, the second half the energy of the full step: StepArgs::alpha_min)
 void launch_elem_vertex(const DevVPatches &VP, int mat, const ElemVertArgs &a, hipStream_t st, const DevLoop *ctl);
-// the direction kernel and the first trial's element pass at the unit step in one launch of two workgroup populations
-// (k_dirstep.hip): replaces launch_spmv_zp + launch_elem_energy_grad in the slots of a speculating step
 bool dirstep_fits(const DevPatches &PT);   // (meshes of at most 512 patches: every patch a workgroup)
-void launch_dirstep(const DevMesh &M, const DevPatches &PT, int mat, double dtSq, const double *xt, double *partE, int *nblocks_out,
-                    const double *Hval, const double *z, const double *c_partials, double *p, double *Hp, double *partS,
-                    hipStream_t st, const DevLoop *ctl, const StepArgs &sa);
 // rpad_s[k] = q[dofmap_s[k]] with q = -g - sum_j xi_j y_j formed on the fly (same operations as build_q), 0 on padding
 // spec (device loop, early back-solve): 1: rpad = -g_cur, 2: rpad = -g_trial whatever the phase; no history terms
 void launch_build_qpad(const DevParts &P, const double *g, const LbfgsArgs &L, const double *xi_host, hipStream_t st,
@@ -514,13 +521,27 @@ void launch_build_p(int n, const double *z, const LbfgsArgs &L, const double *c_
 // early order, one launch for build_p + spmv_dots: p = z + sum_j delta_j s_j (build_p's statements), H p = H z + sum_j
 // delta_j (H s_j) from the cached H s_j, and the partial sums of p.g and p.Hp -- the only sparse product is H z, which
 // does not wait for delta
-// rows [v0, v1) only for the product and the dots (sharded rows); v1 < 0: every row
-// rowMask / ownMask (owner exchange): the product on the rows of the vertices this rank holds (with ITS elements' part of H),
-// p.Hp over them, p.g over the vertices it owns
-void launch_spmv_zp(const DevMesh &M, const double *Hval, const double *z, const double *c_partials, double *p, double *Hp,
-                    double *partials, hipStream_t st, const DevLoop *ctl, int v0 = 0, int v1 = -1,
-                    const uint8_t *rowMask = nullptr, const uint8_t *ownMask = nullptr, VList vl = VList(), bool ctrans = false,
-                    double *partialsT = nullptr);   // (partialsT: p.g / p.Hp once more, column-major [2][NB_RED])
+struct SpmvZpArgs {
+    const double *Hval = nullptr, *z = nullptr;
+    const double *c_partials = nullptr;   // the y_i . z partials ...
+    bool ctrans = false;                  // ... column-major (merge_early's partialsT) instead of in rows
+    double *p = nullptr, *Hp = nullptr;
+    double *partials = nullptr;           // p.g / p.Hp
+    double *partialsT = nullptr;          // the same once more, column-major [2][NB_RED]
+    int v0 = 0, v1 = -1;                  // rows [v0, v1) only for the product and the dots (sharded rows); v1 < 0: every row
+    // owner exchange: the product on the rows of the vertices this rank holds (with ITS elements' part of H), p.Hp over them, p.g over
+    // the vertices it owns
+    const uint8_t *rowMask = nullptr, *ownMask = nullptr;
+    VList vl;
+    int wide = -1;                        // DOTMI_SPMV_WIDE: 0 / 1 forces the 256- / 1024-thread form (-1: by the number of rows)
+};
+void launch_spmv_zp(const DevMesh &M, const SpmvZpArgs &a, hipStream_t st, const DevLoop *ctl);
+// the direction kernel and the first trial's element pass at the unit step in one launch of two workgroup populations
+// (k_dirstep.hip): replaces launch_spmv_zp + launch_elem_pass in the slots of a speculating step.  Of the two records it fuses it takes
+// what its kernel has parameters for: every row, the column-major y_i . z, no twin of the p.g / p.Hp partials; the element pass at
+// the step e.step on every vertex, with gradients.  Returns the blocks of energy partials
+int launch_dirstep(const DevMesh &M, const DevPatches &PT, int mat, double dtSq, const SpmvZpArgs &d, const ElemPassArgs &e, hipStream_t st,
+                   const DevLoop *ctl);
 // Hp = H p on rows [v0,v1), partial sums of p.g and p.Hp
 void launch_spmv_dots(const DevMesh &M, const double *Hval, const double *p, const double *g, double *Hp,
                       int v0, int v1, double *partials, hipStream_t st, const DevLoop *ctl = nullptr);

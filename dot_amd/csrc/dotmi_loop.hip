@@ -53,15 +53,73 @@ void stage_energy(dotmi_handle *h, int nb, double *dst)
     hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(64), 0, h->st, h->partE, nb, 2, 2, h->dtSq, 1.0, 1, dst);
 }
 
-// what every gather of a step has in common; the call sites set what differs
-GatherArgs gather_args(const dotmi_handle *h)
+// ---- the operand records of the loop's launches, built from the handle once (dotmi_handle.hpp); the call sites set what differs ----
+GatherArgs gather_args(const dotmi_handle *h) { return {.xt = h->xt, .iv0 = h->v0, .iv1 = h->v1}; }
+
+// the early order's gather: the new pair and its statistics, H s_new = alpha H p beside s_new (the fused direction kernel's H p: the
+// owner exchange has no other), -g_trial straight into the padded right-hand sides
+GatherArgs early_gather_args(const dotmi_handle *h)
 {
-    GatherArgs a;
-    memset(&a, 0, sizeof(a));
-    a.xt = h->xt;
-    a.iv0 = h->v0;
-    a.iv1 = h->v1;
-    return a;
+    return {.xt = h->xt, .p = h->p, .alpha_dev = h->alpha_dev, .make_pair = 1, .iv0 = h->v0, .iv1 = h->v1, .vp_ptr = h->P.vp_ptr,
+            .vp_off = h->P.vp_off, .rpad = h->P.rpad, .hp = h->tune.fuseDir ? h->Hp : nullptr};
+}
+
+// the loop's direction kernel (build_p + spmv_dots in one launch, H p from the cached H s_j) in its three forms
+SpmvZpArgs spmv_zp_args(const dotmi_handle *h, bool sharded)
+{
+    if (sharded && h->owner)   // the held rows with this rank's own elements' part of H; the y_i . z came with the packet
+        return {.Hval = h->HvalOwn, .z = h->z, .c_partials = h->partGC, .p = h->p, .Hp = h->Hp, .partials = h->partS,
+                .rowMask = h->heldMask, .ownMask = h->ownMask, .vl = h->held(), .wide = h->tune.spmvWide};
+    // one rank: the y_i . z partials from their column-major twin, which merge_early writes beside the rows; partST: the twin of
+    // p.g / p.Hp that elem_vertex_kernel reads; a sharded element pass: this rank's rows
+    const bool rows = sharded && h->shardElems;
+    return {.Hval = h->Hval, .z = h->z, .c_partials = h->dist ? h->partC : h->partCT, .ctrans = !h->dist, .p = h->p, .Hp = h->Hp,
+            .partials = h->partS, .partialsT = h->partST, .v0 = rows ? h->v0 : 0, .v1 = rows ? h->v1 : -1, .wide = h->tune.spmvWide};
+}
+
+// x_trial = x + alpha p, alpha from the p.g / p.Hp partials when there are any; the step taken goes to alpha_dev
+StepForwardArgs step_forward_args(const dotmi_handle *h, const double *spmv_partials, double alpha)
+{
+    return {.x0 = h->x, .p = h->p, .x = h->x_trial, .spmv_partials = spmv_partials, .alpha = alpha, .alpha_min = h->alphaMin,
+            .alpha_out = h->alpha_dev};
+}
+
+StepElemPass step_elem_pass(const dotmi_handle *h, const double *x, int grad, bool sharded)
+{
+    const bool ow = sharded && h->owner;
+    return {ow ? h->Mown : h->M, {.x = x, .xt = h->xt, .v0 = ow ? 0 : h->v0, .v1 = ow ? h->nV : h->v1, .grad = grad, .partials = h->partE}};
+}
+
+int eval_all_elements(dotmi_handle *h, const double *x, int grad)
+{
+    const int nb = launch_elem_pass(h->M, h->PTall, h->mat, h->dtSq, {.x = x, .xt = h->xt, .v1 = h->nV, .grad = grad, .partials = h->partE}, h->st);
+    if (grad) launch_vertex_gather(h->M, h->PTall, {.x = x, .xt = h->xt, .g_new = h->g_trial, .iv1 = h->nV}, NO_HISTORY, h->partR, h->st);
+    return nb;
+}
+
+double energy_of_partials(const dotmi_handle *h, int nb)
+{
+    const double se = chunked_sum(nb, [&](int b) { return h->h_partE[2 * b]; });
+    const double si = chunked_sum(nb, [&](int b) { return h->h_partE[2 * b + 1]; });
+    return h->dtSq * se + si;
+}
+
+int gradient_over_ranks(dotmi_handle *h, int nb, const GatherArgs &pair)
+{
+    const int n = h->n;
+    GatherArgs ag = pair;   // the gather only stages this rank's part: no pair, no right-hand sides, no H s_new
+    ag.make_pair = 0;
+    ag.stage = 1;
+    ag.g_new = h->gstage;
+    ag.hp = nullptr;
+    ag.vp_ptr = ag.vp_off = nullptr;
+    ag.rpad = nullptr;
+    launch_vertex_gather(h->M, h->PT, ag, NO_HISTORY, h->partR, h->st, h->ctl);
+    stage_energy(h, nb, h->gstage + n + 1);   // [g (n) ; 0 ; E_local]
+    if (int rc = allreduce_sum(h, h->gstage, (size_t)n + 2)) return rc;
+    // (pair_stats copies the summed gradient to the trial gradient, whose address only the controller knows)
+    launch_pair_stats(n, pair, NO_HISTORY, h->partR, h->st, h->gstage, h->ctl);
+    return 0;
 }
 
 // p = D^-1 sum_s R_s^T W_s R_s q   (DOTTimeStepper.cpp:406-450); leaves y_i.z partials in partC
@@ -88,12 +146,12 @@ int apply_precond(dotmi_handle *h, const double *q, double *z, const LbfgsArgs &
 int trial(dotmi_handle *h, const double *xeval, double *gout, int make_pair, const LbfgsArgs &L, int slot,
           double *E, int evalSlot = DOTMI_T_LINESEARCH_EVAL, int gradSlot = DOTMI_T_UPDATE_HISTORY)
 {
-    int nb = 0;
     // single-GPU: the reduction partials go straight to pinned host memory (zero-copy), so one stream
     // synchronisation is the only host<->device interaction of a line-search trial
-    double *partE = h->shardElems ? h->partE : h->h_partE;
+    StepElemPass e = step_elem_pass(h, xeval, 1);
+    if (!h->shardElems) e.a.partials = h->h_partE;
     double *partR = h->shardElems ? h->partR : h->h_partR;
-    launch_elem_energy_grad(h->M, h->PT, h->mat, h->dtSq, xeval, h->xt, h->v0, h->v1, 1, partE, &nb, h->st);
+    const int nb = launch_elem_pass(e.M, h->PT, h->mat, h->dtSq, e.a, h->st);
     h->nbE = nb;
     phase_mark(h, evalSlot);
     GatherArgs a = gather_args(h);
@@ -126,13 +184,7 @@ int trial(dotmi_handle *h, const double *xeval, double *gout, int make_pair, con
     phase_mark(h, gradSlot);
     HIPCHECK(h, hipStreamSynchronize(h->st));
     phase_collect(h);
-    if (!h->shardElems) {
-        const double se = chunked_sum(nb, [&](int b) { return h->h_partE[2 * b]; });
-        const double si = chunked_sum(nb, [&](int b) { return h->h_partE[2 * b + 1]; });
-        *E = h->dtSq * se + si;
-    } else {
-        *E = h->h_partE[0];
-    }
+    *E = h->shardElems ? h->h_partE[0] : energy_of_partials(h, nb);
     if (h->world > 1) {
         // one set of control scalars for all ranks: rank 0's (energy, step length, every column of the statistics)
         h->ctrl[0] = *E;
@@ -178,6 +230,14 @@ ElemVertArgs elem_vertex_args(const dotmi_handle *h)
     return a;
 }
 
+// the host-driven loops' step: alpha also to pinned memory, where the host reads it after the trial
+static void host_step(dotmi_handle *h, const double *spmv_partials, double alpha)
+{
+    StepForwardArgs a = step_forward_args(h, spmv_partials, alpha);
+    a.alpha_out_host = h->h_alpha;
+    launch_step_forward(h->n, a, h->st);
+}
+
 // The back-tracking line search (Optimizer.cpp:806-833; c1 = 0, lower bound 0) from a first trial at *alpha with energy *E:
 // halve while the energy increases; *failed when the step length runs out.  marks: the retry's step launch is a phase of its own
 // (DOTMI_FLAG_TIME_PHASES, the L-BFGS loop only)
@@ -192,7 +252,7 @@ static int backtrack(dotmi_handle *h, const LbfgsArgs &L, int make_pair, int slo
             break;
         }
         if (marks) phase_mark(h, -1);
-        launch_step_forward(h->n, h->x, h->p, h->x_trial, nullptr, *alpha, 0, h->alphaMin, h->alpha_dev, h->h_alpha, h->st);
+        host_step(h, nullptr, *alpha);
         if (marks) phase_mark(h, DOTMI_T_LINESEARCH_OTHER);
         if (int rc = trial(h, h->x_trial, h->g_trial, make_pair, L, slot, E)) return rc;
     }
@@ -208,19 +268,17 @@ static int backtrack(dotmi_handle *h, const LbfgsArgs &L, int make_pair, int slo
 static int run_gsdd_loop(dotmi_handle *h, LoopOut &r)
 {
     const int n = h->n;
-    LbfgsArgs L0;
-    memset(&L0, 0, sizeof(L0));
     double R[RED_K];
     do {
         for (int ls = 0; ls < h->P.nParts && !r.failed; ++ls) {
-            launch_build_q(n, h->g, L0, nullptr, h->q, h->st);                     // q = -g
+            launch_build_q(n, h->g, NO_HISTORY, nullptr, h->q, h->st);                     // q = -g
             launch_gemv_part(h->P, ls, h->P.tileByPart + h->partTilePtr[ls], h->partTilePtr[ls + 1] - h->partTilePtr[ls],
                              h->P.lworkByPart + h->partLworkPtr[ls], h->partLworkPtr[ls + 1] - h->partLworkPtr[ls],
                              h->q, n, h->p, h->st);
             double alpha = 1.0, E = 0;
-            launch_step_forward(n, h->x, h->p, h->x_trial, nullptr, alpha, 0, h->alphaMin, h->alpha_dev, h->h_alpha, h->st);
-            if (int rc = trial(h, h->x_trial, h->g_trial, 0, L0, 0, &E)) return rc;
-            if (int rc = backtrack(h, L0, 0, 0, r.lastE, false, &alpha, &E, &r.failed)) return rc;
+            host_step(h, nullptr, alpha);
+            if (int rc = trial(h, h->x_trial, h->g_trial, 0, NO_HISTORY, 0, &E)) return rc;
+            if (int rc = backtrack(h, NO_HISTORY, 0, 0, r.lastE, false, &alpha, &E, &r.failed)) return rc;
             std::swap(h->x, h->x_trial);   // also on failure: the reference stays at the last trial point
             std::swap(h->g, h->g_trial);   // the gradient of the accepted point came with its energy
             r.lastE = E;
@@ -245,26 +303,24 @@ static int run_gsdd_loop(dotmi_handle *h, LoopOut &r)
 static int run_newton_loop(dotmi_handle *h, LoopOut &r, double *ms_hess, double *ms_fact)
 {
     const int n = h->n;
-    LbfgsArgs L0;
-    memset(&L0, 0, sizeof(L0));
     double R[RED_K];
     do {
         if (int rc = refactor(h, h->x, ms_hess, ms_fact)) return rc;
         if (h->newtonPcg) {
             // DOTMI_FLAG_NEWTON_PCG: p = PCG(H, -g) on any number of subdomains (dotmi_pcg.hip).  A solve that ends at its cap or in
             // breakdown hands over its iterate all the same -- every CG iterate from zero is a descent direction -- and the step goes on
-            launch_build_q(n, h->g, L0, nullptr, h->tmpn, h->st);              // b = -g
+            launch_build_q(n, h->g, NO_HISTORY, nullptr, h->tmpn, h->st);              // b = -g
             int cg = 0;
             if (int rc = pcg_solve(h, h->tmpn, h->pcgTol, h->pcgCap, h->pcgEvery, &cg, nullptr); rc < 0) return rc;
             r.applies += cg;
         } else {
-            launch_build_q(n, h->g, L0, nullptr, h->q, h->st);                 // q = -g
-            if (int rc = apply_precond(h, h->q, h->p, L0)) return rc;           // p = H^-1 q (one subdomain: no averaging)
+            launch_build_q(n, h->g, NO_HISTORY, nullptr, h->q, h->st);                 // q = -g
+            if (int rc = apply_precond(h, h->q, h->p, NO_HISTORY)) return rc;           // p = H^-1 q (one subdomain: no averaging)
         }
         double alpha = 1.0, E = 0;
-        launch_step_forward(n, h->x, h->p, h->x_trial, nullptr, alpha, 0, h->alphaMin, h->alpha_dev, h->h_alpha, h->st);
-        if (int rc = trial(h, h->x_trial, h->g_trial, 0, L0, 0, &E)) return rc;
-        if (int rc = backtrack(h, L0, 0, 0, r.lastE, false, &alpha, &E, &r.failed)) return rc;
+        host_step(h, nullptr, alpha);
+        if (int rc = trial(h, h->x_trial, h->g_trial, 0, NO_HISTORY, 0, &E)) return rc;
+        if (int rc = backtrack(h, NO_HISTORY, 0, 0, r.lastE, false, &alpha, &E, &r.failed)) return rc;
         std::swap(h->x, h->x_trial);
         std::swap(h->g, h->g_trial);
         r.lastE = E;
@@ -313,12 +369,12 @@ static int run_host_loop(dotmi_handle *h, LoopOut &r)
         // ---- alpha_0 and the first trial ---------------------------------------------------------------
         if (h->pd || h->hi) {
             // only TST_DOT estimates alpha_0 (Optimizer::initStepSize, Optimizer.cpp:1076-1093): the unit step, no H p
-            launch_step_forward(n, h->x, h->p, h->x_trial, nullptr, 1.0, 0, h->alphaMin, h->alpha_dev, h->h_alpha, h->st);
+            host_step(h, nullptr, 1.0);
         } else {
             launch_spmv_dots(h->M, h->Hval, h->p, h->g, nullptr, h->v0, h->v1, h->partS, h->st);
             const double *spart = nullptr;
             if (int rc = reduce_step_dots(h, &spart)) return rc;
-            launch_step_forward(n, h->x, h->p, h->x_trial, spart, 0.0, 1, h->alphaMin, h->alpha_dev, h->h_alpha, h->st);
+            host_step(h, spart, 0.0);
         }
         phase_mark(h, DOTMI_T_LINESEARCH_OTHER);
         const int slot = lbfgs_free_slot(h->hist, h->m, h->order);

@@ -53,12 +53,10 @@ static int pcg_alloc(dotmi_handle *h)
 static int pcg_iteration(dotmi_handle *h, bool coarse, int k, double rel_tol)
 {
     const DevPcg &C = h->pcg;
-    LbfgsArgs L0;
-    memset(&L0, 0, sizeof(L0));
     const Bracket br = backsolve_bracket(h);
     if (coarse) coarse_restrict_solve(h, C.r);                          // y = A0^-1 Z^T r (needs nothing of the block solve)
     launch_gemv(h->P, h->q, h->st, nullptr, br.ev0, br.ev1);           // the block solves of q = r (.) isd
-    launch_merge(h->M, h->P, L0, {.z = h->z}, h->st);                   // zsum = S q: no division, no dots
+    launch_merge(h->M, h->P, NO_HISTORY, {.z = h->z}, h->st);           // zsum = S q: no division, no dots
     if (coarse) coarse_prolong(h, h->z);                                // zsum += (Z y) / isd: w = M_sym r + Z y
     if (h->dist)
         if (int rc = allreduce_sum(h, h->z, (size_t)h->n)) return rc;

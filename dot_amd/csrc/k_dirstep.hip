@@ -87,30 +87,28 @@ __global__ __launch_bounds__(256, 2) void dirstep_kernel(DevPatches PT, const do
     DS_STAMP(1, wall_clock64());
 }
 
-// can a step of this handle speculate?  (every patch a workgroup of the fused step: launch_elem_energy_grad's rule)
+// can a step of this handle speculate?  (every patch a workgroup of the fused step: launch_elem_pass's rule)
 bool dirstep_fits(const DevPatches &PT)
 {
     const int cap = PT.wgCap > 0 ? PT.wgCap : 512;
     return PT.nPatches <= cap && PT.nPatches <= ELEM_NB_MAX;
 }
 
-// the launch of a speculating step's slot in place of launch_spmv_zp + launch_elem_energy_grad (one rank, fused step)
-void launch_dirstep(const DevMesh &M, const DevPatches &PT, int mat, double dtSq, const double *xt, double *partE, int *nblocks_out,
-                    const double *Hval, const double *z, const double *c_partials, double *p, double *Hp, double *partS,
-                    hipStream_t st, const DevLoop *ctl, const StepArgs &sa)
+// the launch of a speculating step's slot in place of launch_spmv_zp + launch_elem_pass (one rank, fused step)
+int launch_dirstep(const DevMesh &M, const DevPatches &PT, int mat, double dtSq, const SpmvZpArgs &d, const ElemPassArgs &e, hipStream_t st,
+                   const DevLoop *ctl)
 {
-    // the element population: as many workgroups as launch_elem_energy_grad gives the fused step (the same grouping of the energy
+    // the element population: as many workgroups as launch_elem_pass gives the fused step (the same grouping of the energy
     // partials, so the energy is the plain slot's bit for bit); every patch a workgroup (the caller has checked)
     int nb = PT.nPatches;
     const int nbv = (M.nV + 255) / 256;
     if (nb < nbv) nb = nbv;
     if (nb < 1) nb = 1;
-    *nblocks_out = nb;
     const int ept = PT.PE / 256;
     const size_t shm = sizeof(double) * ((size_t)3 * PT.PV + (size_t)12 * PT.PE) + 2 * (size_t)((PT.PV + 1 + 3) & ~3) + 4 * (size_t)PT.PV;
 #define DS_LAUNCH(MATV, EPTV)                                                                                                     \
-    hipLaunchKernelGGL((dirstep_kernel<MATV, EPTV>), dim3(NB_RED + nb + nbv), dim3(256), shm, st, PT, M.mass, xt, dtSq, partE, ctl, sa, \
-                       M.nV, M.adj_ptr, M.adj_idx, Hval, z, c_partials, p, Hp, partS, nb)
+    hipLaunchKernelGGL((dirstep_kernel<MATV, EPTV>), dim3(NB_RED + nb + nbv), dim3(256), shm, st, PT, M.mass, e.xt, dtSq, e.partials, ctl, \
+                       *e.step, M.nV, M.adj_ptr, M.adj_idx, d.Hval, d.z, d.c_partials, d.p, d.Hp, d.partials, nb)
     if (mat == 0) {
         if (ept == 1) DS_LAUNCH(0, 1);
         else DS_LAUNCH(0, 2);
@@ -119,6 +117,7 @@ void launch_dirstep(const DevMesh &M, const DevPatches &PT, int mat, double dtSq
         else DS_LAUNCH(1, 2);
     }
 #undef DS_LAUNCH
+    return nb;
 }
 
 }  // namespace dotmi

@@ -28,24 +28,24 @@ __global__ __launch_bounds__(256) void elem_patch_kernel(DevPatches PT, const do
 }
 
 template <bool PAIR>
-static void launch_elem_impl(const DevMesh &M, const DevPatches &PT, int mat, double dtSq, const double *x, const double *xt,
-                             int v0, int v1, int grad, double *partials, int *nblocks_out, hipStream_t st, const DevLoop *ctl,
-                             const StepArgs *step)
+static int launch_elem_impl(const DevMesh &M, const DevPatches &PT, int mat, double dtSq, const ElemPassArgs &a, hipStream_t st,
+                            const DevLoop *ctl)
 {
+    const int grad = a.grad;
+    const bool stepping = a.step && ctl;   // (the step inside the element pass: device loop only)
     StepArgs sa{nullptr, nullptr, nullptr, 0.0};
-    if (step && ctl) sa = *step;
+    if (stepping) sa = *a.step;
     const bool paired = PAIR && sa.p && sa.alpha_min < 0.0 && grad;
     // at most elem_wg_cap() workgroups take the patches (as many as are resident at once): beyond that a workgroup walks several
     // patches and prefetches the next one's operands (elem_patch_kernel)
     // (the instantiation with the step inside: two per CU; a handle whose loop uses it fixes 512 for all of them, PT.wgCap)
-    const int cap = PT.wgCap > 0 ? PT.wgCap : ((step && ctl) ? 512 : elem_wg_cap(mat));
+    const int cap = PT.wgCap > 0 ? PT.wgCap : (stepping ? 512 : elem_wg_cap(mat));
     const bool pipe = PT.nPatches > cap;
     int nb = pipe ? cap : PT.nPatches;
-    const int nbv = (v1 - v0 + 255) / 256;
+    const int nbv = (a.v1 - a.v0 + 255) / 256;
     if (nb < nbv && !pipe) nb = nbv;    // the inertia loop likes one vertex per thread on small meshes
     if (nb > ELEM_NB_MAX) nb = ELEM_NB_MAX;
     if (nb < 1) nb = 1;
-    *nblocks_out = nb;
     const int nbLaunch = paired ? 2 * nb : nb;
     const int ept = PT.PE / 256;
     const size_t shm = sizeof(double) * ((size_t)3 * PT.PV + (grad ? (size_t)12 * PT.PE : 0)) +
@@ -55,16 +55,16 @@ static void launch_elem_impl(const DevMesh &M, const DevPatches &PT, int mat, do
     do {                                                                                                            \
         if (sa.p && pipe)                                                                                           \
             hipLaunchKernelGGL((elem_patch_kernel<MATV, GRADV, EPTV, true, true, PAIR && GRADV>), dim3(nbLaunch), dim3(256), shm, st, \
-                               PT, M.mass, x, xt, v0, v1, dtSq, partials, ctl, sa);                                 \
+                               PT, M.mass, a.x, a.xt, a.v0, a.v1, dtSq, a.partials, ctl, sa);                   \
         else if (sa.p)                                                                                              \
             hipLaunchKernelGGL((elem_patch_kernel<MATV, GRADV, EPTV, true, false, PAIR && GRADV>), dim3(nbLaunch), dim3(256), shm, st, \
-                               PT, M.mass, x, xt, v0, v1, dtSq, partials, ctl, sa);                                 \
+                               PT, M.mass, a.x, a.xt, a.v0, a.v1, dtSq, a.partials, ctl, sa);                   \
         else if (pipe)                                                                                              \
             hipLaunchKernelGGL((elem_patch_kernel<MATV, GRADV, EPTV, false, true, false>), dim3(nbLaunch), dim3(256), shm, st, PT, \
-                               M.mass, x, xt, v0, v1, dtSq, partials, ctl, sa);                                     \
+                               M.mass, a.x, a.xt, a.v0, a.v1, dtSq, a.partials, ctl, sa);                       \
         else                                                                                                        \
             hipLaunchKernelGGL((elem_patch_kernel<MATV, GRADV, EPTV, false, false, false>), dim3(nbLaunch), dim3(256), shm, st, PT, \
-                               M.mass, x, xt, v0, v1, dtSq, partials, ctl, sa);                                     \
+                               M.mass, a.x, a.xt, a.v0, a.v1, dtSq, a.partials, ctl, sa);                       \
     } while (0)
 #define DM_LAUNCH_E(MATV, GRADV)      \
     do {                              \
@@ -80,20 +80,15 @@ static void launch_elem_impl(const DevMesh &M, const DevPatches &PT, int mat, do
     }
 #undef DM_LAUNCH_E
 #undef DM_LAUNCH
+    return nb;
 }
 
-void launch_elem_energy_grad(const DevMesh &M, const DevPatches &PT, int mat, double dtSq, const double *x,
-                             const double *xt, int v0, int v1, int grad, double *partials, int *nblocks_out,
-                             hipStream_t st, const DevLoop *ctl, const StepArgs *step)
+int launch_elem_pass(const DevMesh &M, const DevPatches &PT, int mat, double dtSq, const ElemPassArgs &a, hipStream_t st, const DevLoop *ctl)
 {
-    launch_elem_impl<false>(M, PT, mat, dtSq, x, xt, v0, v1, grad, partials, nblocks_out, st, ctl, step);
-}
-// a step with paired trials (StepArgs::alpha_min < 0 makes it a paired launch)
-void launch_elem_energy_grad_pair(const DevMesh &M, const DevPatches &PT, int mat, double dtSq, const double *x,
-                                  const double *xt, int v0, int v1, int grad, double *partials, int *nblocks_out,
-                                  hipStream_t st, const DevLoop *ctl, const StepArgs *step)
-{
-    launch_elem_impl<true>(M, PT, mat, dtSq, x, xt, v0, v1, grad, partials, nblocks_out, st, ctl, step);
+    // (the plain instantiations first: the order in which the unit's kernels are emitted, which their code depends on at the level of a
+    // padding instruction, stays what it was with two public launchers)
+    if (!a.pair) return launch_elem_impl<false>(M, PT, mat, dtSq, a, st, ctl);
+    return launch_elem_impl<true>(M, PT, mat, dtSq, a, st, ctl);
 }
 
 }  // namespace dotmi

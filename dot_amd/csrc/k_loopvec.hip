@@ -1118,24 +1118,22 @@ __global__ __launch_bounds__(1024) void spmv_zp_wide_kernel(int nV, int v0, int 
                           delta, (int)blockIdx.x, (int)gridDim.x, partialsT);
 }
 
-void launch_spmv_zp(const DevMesh &M, const double *Hval, const double *z, const double *c_partials, double *p, double *Hp,
-                    double *partials, hipStream_t st, const DevLoop *ctl, int v0, int v1, const uint8_t *rowMask,
-                    const uint8_t *ownMask, VList vl, bool ctrans, double *partialsT)
+void launch_spmv_zp(const DevMesh &M, const SpmvZpArgs &a, hipStream_t st, const DevLoop *ctl)
 {
-    if (v1 < 0) v1 = M.nV;
+    const int v1 = a.v1 < 0 ? M.nV : a.v1;
     // Rows beyond one trip of the 256-thread form (256 workgroups x 32 lane groups x 3 rows): workgroups of 1024 threads, a
     // row per lane group -- four waves per SIMD hide what the interleaving of three rows inside one wave cannot once the kernel
     // is bound by throughput (1 M tets: 76.9 -> 56.9 us; bar17K, one trip: 11.8 -> 12.9, stays on 256 threads).
-    // DOTMI_SPMV_WIDE=0 / 1 forces the form.
-    static const int wideEnv = getenv("DOTMI_SPMV_WIDE") ? atoi(getenv("DOTMI_SPMV_WIDE")) : -1;
-    const int nrows = vl.v ? vl.n : M.nV;
-    const bool wide = wideEnv >= 0 ? wideEnv != 0 : nrows > NB_RED * 32 * SPMV_R;
+    // a.wide = 0 / 1 (DOTMI_SPMV_WIDE, Tuning::spmvWide) forces the form.
+    const int nrows = a.vl.v ? a.vl.n : M.nV;
+    const bool wide = a.wide >= 0 ? a.wide != 0 : nrows > NB_RED * 32 * SPMV_R;
+    const int c_blocks = a.ctrans ? -NB_RED : NB_RED;
     if (wide)
-        hipLaunchKernelGGL(spmv_zp_wide_kernel, dim3(NB_RED), dim3(1024), 0, st, M.nV, v0, v1, rowMask, ownMask, M.adj_ptr, M.adj_idx,
-                           Hval, z, c_partials, ctrans ? -NB_RED : NB_RED, p, Hp, partials, ctl, vl, partialsT);
+        hipLaunchKernelGGL(spmv_zp_wide_kernel, dim3(NB_RED), dim3(1024), 0, st, M.nV, a.v0, v1, a.rowMask, a.ownMask, M.adj_ptr, M.adj_idx,
+                           a.Hval, a.z, a.c_partials, c_blocks, a.p, a.Hp, a.partials, ctl, a.vl, a.partialsT);
     else
-    hipLaunchKernelGGL(spmv_zp_kernel, dim3(NB_RED), dim3(256), 0, st, M.nV, v0, v1, rowMask, ownMask, M.adj_ptr, M.adj_idx, Hval,
-                       z, c_partials, ctrans ? -NB_RED : NB_RED, p, Hp, partials, ctl, vl, partialsT);
+        hipLaunchKernelGGL(spmv_zp_kernel, dim3(NB_RED), dim3(256), 0, st, M.nV, a.v0, v1, a.rowMask, a.ownMask, M.adj_ptr, M.adj_idx,
+                           a.Hval, a.z, a.c_partials, c_blocks, a.p, a.Hp, a.partials, ctl, a.vl, a.partialsT);
 }
 
 void launch_spmv_dots(const DevMesh &M, const double *Hval, const double *p, const double *g, double *Hp,
@@ -1192,15 +1190,13 @@ __global__ __launch_bounds__(256) void step_forward_kernel(int n, const double *
     }
 }
 
-void launch_step_forward(int n, const double *x0, const double *p, double *x, const double *spmv_partials,
-                         double alpha_host, int use_partials, double alpha_min, double *alpha_out,
-                         double *alpha_out_host, hipStream_t st, const DevLoop *ctl, VList vl)
+void launch_step_forward(int n, const StepForwardArgs &a, hipStream_t st, const DevLoop *ctl)
 {
-    int nb = ((vl.v ? 3 * vl.n : n) + 255) / 256;
+    int nb = ((a.vl.v ? 3 * a.vl.n : n) + 255) / 256;
     if (nb > 1024) nb = 1024;
     if (nb < 1) nb = 1;
-    hipLaunchKernelGGL(step_forward_kernel, dim3(nb), dim3(256), 0, st, n, x0, p, x, spmv_partials,
-                       alpha_host, use_partials, alpha_min, alpha_out, alpha_out_host, ctl, vl);
+    hipLaunchKernelGGL(step_forward_kernel, dim3(nb), dim3(256), 0, st, n, a.x0, a.p, a.x, a.spmv_partials, a.alpha,
+                       a.spmv_partials != nullptr ? 1 : 0, a.alpha_min, a.alpha_out, a.alpha_out_host, ctl, a.vl);
 }
 
 // ------------------------------------------------------------------------------------------------
