@@ -57,8 +57,9 @@ double host_target_gres(const dotmi_handle *h)
     Mat3 Aw;
     double Bw[3][4];
     const double S1[3] = {1, 1, 1};
-    if (h->mat == 0) spectral_blocks<0>(S1, h->mu[0], h->lam[0], 1.0, false, Aw, Bw);
-    else spectral_blocks<1>(S1, h->mu[0], h->lam[0], 1.0, false, Aw, Bw);
+#define TG_BLOCKS(MATV) spectral_blocks<MATV>(S1, h->mu[0], h->lam[0], 1.0, false, Aw, Bw)
+    DM_DISPATCH_MAT(h->mat, TG_BLOCKS)
+#undef TG_BLOCKS
     // with U = V = I the 9x9 matrix is exactly the 21 spectral entries (Energy.cpp:1183-1207)
     double sqH = 0;
     for (int i = 0; i < 3; ++i)
@@ -960,8 +961,11 @@ static int choose_loop_form(dotmi_handle *h)
     h->vpFits = false;
     // (Stable Neo-Hookean only: its element work is ~1 us of a workgroup's ~12, so carrying every element 1.9 times is free; with
     // the fixed-corotational SVD the doubled element work costs what the saved launch gives -- bunny5K 1.656 -> 1.696 ms, measured)
+    // (its log-regularised form as well: no SVD either, and elem_vertex_kernel<2, *> has the registers and LDS of <1, *> and no
+    // scratch -- DESIGN section 4)
+    const bool closedForm = h->mat == DOTMI_ENERGY_SNH || h->mat == DOTMI_ENERGY_SNH_LOG;
     if (h->earlyBs && !h->dist && h->world == 1 && h->tune.fuseStep && h->tune.fuseDir && h->tune.vertexPatches != 0 &&
-        (h->mat == DOTMI_ENERGY_SNH || h->tune.vertexPatches > 0) &&
+        (closedForm || h->tune.vertexPatches > 0) &&
         h->P.ntiles - h->P.ntilesWide + h->P.nquad > 0 && !(h->flags & (DOTMI_FLAG_GSDD | DOTMI_FLAG_NEWTON | DOTMI_FLAG_NEWTON_PCG | DOTMI_FLAG_NEWTON_PCG_DIST | DOTMI_FLAG_HOST_LOOP))) {
         const HostVPatches HV = build_vpatches(h->nV, h->nT, h->T.data(), h->Xrest.data(), 512, 85);
         // (the kernel's static LDS counts against the 64 KB of a workgroup too)
@@ -1037,7 +1041,7 @@ static int create_impl(dotmi_handle *h, const dotmi_mesh *mesh, const dotmi_para
         !mesh->lambda || !mesh->fixed || mesh->nParts < 1 || prm->dt <= 0 ||
         prm->history < 1 || prm->history > HIST_MAX || prm->world < 1 || prm->rank < 0 ||
         prm->rank >= prm->world || (prm->world > 1 && !prm->comm_id && !prm->allreduce) ||
-        (prm->energy != DOTMI_ENERGY_FCR && prm->energy != DOTMI_ENERGY_SNH)) {
+        (prm->energy != DOTMI_ENERGY_FCR && prm->energy != DOTMI_ENERGY_SNH && prm->energy != DOTMI_ENERGY_SNH_LOG)) {
         h->err = "invalid argument";
         return DOTMI_E_INVALID;
     }

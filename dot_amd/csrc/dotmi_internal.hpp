@@ -7,12 +7,30 @@
 #include "nd_layout.hpp"
 #include "tile_factor.hpp"
 #include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
 
 namespace dotmi {
 
 // workgroups of the element pass when the mesh has more patches than that: what is resident at once with the prefetching
-// instantiation's registers (Stable Neo-Hookean 158: three per CU; fixed-corotational with its SVD 190: two) x 256 CUs
+// instantiation's registers (Stable Neo-Hookean 158: three per CU; fixed-corotational with its SVD 190: two; the log-regularised
+// Stable Neo-Hookean 178, the logarithm's and the division's temporaries on top of the plain form's: two as well) x 256 CUs
 inline int elem_wg_cap(int mat) { return mat == 1 ? 768 : 512; }
+// Every launcher's dispatch on the runtime material id names the three ids (0 fixed-corotational, 1 Stable Neo-Hookean, 2 its
+// log-regularised form) and ends here on anything else: an id the kernels do not know must never run as another material's
+// instantiation.  dotmi_create admits no other id, so this is a broken invariant, not an input error.
+#define DM_DISPATCH_MAT(mat, CASE)              \
+    switch (mat) {                              \
+    case 0: CASE(0); break;                     \
+    case 1: CASE(1); break;                     \
+    case 2: CASE(2); break;                     \
+    default: ::dotmi::unknown_material(mat);    \
+    }
+[[noreturn]] inline void unknown_material(int mat)
+{
+    fprintf(stderr, "dotmi: no kernel for material id %d\n", mat);
+    abort();
+}
 constexpr int NB_RED = 256;     // blocks of every reducing kernel (fixed => run-to-run bit-identical sums)
 constexpr int RED_K = 3 * HIST_MAX + 3;  // partial values per block
 constexpr int BS_WAVE = 256;    // rows of at most that many columns: four tiles per workgroup, one wavefront each

@@ -10,7 +10,8 @@
 //   F = Ds * A                       Energy/Energy.cpp:309-321
 //   3x3 SVD conventions              Utils/IglUtils.cpp:929-1085, Utils/SVD_EFTYCHIOS/*
 //   Psi, dPsi/dsigma, d2Psi, B-left  Energy/Physics_Elasticity/FixedCoRotEnergy.cpp:83-172,
-//                                    StableNHEnergy.cpp:91-228
+//                                    StableNHEnergy.cpp:91-228 (MAT 1), :84-89, :102-114, :134-171, :204-216 (MAT 2: the
+//                                    log-regularised form the reference compiles with SNH_WITHLOG, Utils/Types.hpp:36)
 //   PSD clamps                       Utils/IglUtils.hpp:253-309
 //   dP/dF in the singular basis      Energy/Energy.cpp:1129-1270
 #pragma once
@@ -244,6 +245,11 @@ DM_HD double psi(const double (&s)[3], double mu, double lam)
         double a = s[0] - 1, b = s[1] - 1, c = s[2] - 1;
         return mu * (a * a + b * b + c * c) + lam / 2.0 * (J - 1.0) * (J - 1.0);
     }
+    if (MAT == 2) {
+        double S2 = s[0] * s[0] + s[1] * s[1] + s[2] * s[2];
+        double JmA = J - (1.0 + 3.0 * mu / 4.0 / lam);
+        return (mu * (S2 - 3.0 - log(S2 + 1.0)) + lam * JmA * JmA) / 2.0;
+    }
     double JmA = J - (1.0 + mu / lam);
     return (mu * (s[0] * s[0] + s[1] * s[1] + s[2] * s[2] - 3.0) + lam * JmA * JmA) / 2.0;
 }
@@ -257,6 +263,11 @@ DM_HD void dpsi(const double (&s)[3], double mu, double lam, double (&d)[3])
         double t = lam * (J - 1.0);
 #pragma unroll
         for (int i = 0; i < 3; ++i) d[i] = 2.0 * mu * (s[i] - 1.0) + pn[i] * t;
+    } else if (MAT == 2) {
+        double tau = mu * (1.0 - 1.0 / (s[0] * s[0] + s[1] * s[1] + s[2] * s[2] + 1.0));
+        double t = lam * (J - (1.0 + 3.0 * mu / 4.0 / lam));
+#pragma unroll
+        for (int i = 0; i < 3; ++i) d[i] = s[i] * tau + t * pn[i];
     } else {
         double t = lam * (J - (1.0 + mu / lam));
 #pragma unroll
@@ -275,6 +286,16 @@ DM_HD void d2psi(const double (&s)[3], double mu, double lam, Mat3 &A)
         A.m[0][1] = A.m[1][0] = lam * (s[2] * (J - 1.0) + pn[0] * pn[1]);
         A.m[0][2] = A.m[2][0] = lam * (s[1] * (J - 1.0) + pn[0] * pn[2]);
         A.m[1][2] = A.m[2][1] = lam * (s[0] * (J - 1.0) + pn[2] * pn[1]);
+    } else if (MAT == 2) {
+        double l2 = lam * (2.0 * J - (1.0 + 3.0 * mu / 4.0 / lam));
+        double s2[3] = {s[0] * s[0], s[1] * s[1], s[2] * s[2]};
+        double Sp1 = s2[0] + s2[1] + s2[2] + 1.0;
+        double r = mu / (Sp1 * Sp1);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) A.m[i][i] = mu + lam * pn[i] * pn[i] - (Sp1 - 2.0 * s2[i]) * r;
+        A.m[0][1] = A.m[1][0] = s[2] * l2 + 2.0 * pn[2] * r;
+        A.m[0][2] = A.m[2][0] = s[1] * l2 + 2.0 * pn[1] * r;
+        A.m[1][2] = A.m[2][1] = s[0] * l2 + 2.0 * pn[0] * r;
     } else {
         double l2 = lam * (2.0 * J - (1.0 + mu / lam));
 #pragma unroll
@@ -294,12 +315,49 @@ DM_HD void bleft(const double (&s)[3], double mu, double lam, double (&b)[3])
         b[0] = mu - h * s[2] * (J - 1.0);
         b[1] = mu - h * s[0] * (J - 1.0);
         b[2] = mu - h * s[1] * (J - 1.0);
+    } else if (MAT == 2) {
+        double t = lam * (J - (1.0 + 3.0 * mu / 4.0 / lam));
+        double tau = mu - mu / (s[0] * s[0] + s[1] * s[1] + s[2] * s[2] + 1.0);
+        b[0] = (tau - t * s[2]) / 2.0;
+        b[1] = (tau - t * s[0]) / 2.0;
+        b[2] = (tau - t * s[1]) / 2.0;
     } else {
         double t = lam * (J - (1.0 + mu / lam));
         b[0] = (mu - t * s[2]) / 2.0;
         b[1] = (mu - t * s[0]) / 2.0;
         b[2] = (mu - t * s[1]) / 2.0;
     }
+}
+
+// The log-regularised Stable Neo-Hookean material (MAT 2) in closed form: Psi = (mu (|F|^2 - 3 - log(|F|^2 + 1)) +
+// lam (J - a)^2) / 2, a = 1 + 3 mu / (4 lam) (StableNHEnergy.cpp:84-89), is a function of |F|_F^2 and det F = J only, and
+// U diag(dPsi/dsigma) V^T = tau F + lam (J - a) cof F with tau = mu (1 - 1 / (|F|^2 + 1)) (:237-243), so the element pass needs
+// no SVD (the Hessian, once per step, keeps it).  Returns Psi and, if withP, P = w dPsi/dF; |F|^2 + 1 is formed once for
+// the energy's logarithm and the stress's one reciprocal.  Every form of the element pass (elem_patch_body, elem_vertex_kernel, the speculative step) evaluates the
+// material through this text, which is what keeps them bit-identical per tet.
+DM_HD double snh_log_energy_stress(const Mat3 &F, double mu, double lam, double w, bool withP, double (&P)[3][3])
+{
+    const double J = det3(F);
+    const double ic = F.m[0][0] * F.m[0][0] + F.m[0][1] * F.m[0][1] + F.m[0][2] * F.m[0][2] +
+                      F.m[1][0] * F.m[1][0] + F.m[1][1] * F.m[1][1] + F.m[1][2] * F.m[1][2] +
+                      F.m[2][0] * F.m[2][0] + F.m[2][1] * F.m[2][1] + F.m[2][2] * F.m[2][2];
+    const double icp1 = ic + 1.0;
+    const double JmA = J - (1.0 + 3.0 * mu / 4.0 / lam);
+    if (withP) {
+        const double tau = mu * (1.0 - 1.0 / icp1);
+        const double t = lam * JmA;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const int r1 = (r + 1) % 3, r2 = (r + 2) % 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int c1 = (c + 1) % 3, c2 = (c + 2) % 3;
+                const double cof = F.m[r1][c1] * F.m[r2][c2] - F.m[r1][c2] * F.m[r2][c1];
+                P[r][c] = w * (tau * F.m[r][c] + t * cof);
+            }
+        }
+    }
+    return (mu * (ic - 3.0 - log(icp1)) + lam * JmA * JmA) / 2.0;
 }
 
 DM_HD void make_pd3(Mat3 &A)

@@ -109,13 +109,13 @@ int launch_dirstep(const DevMesh &M, const DevPatches &PT, int mat, double dtSq,
 #define DS_LAUNCH(MATV, EPTV)                                                                                                     \
     hipLaunchKernelGGL((dirstep_kernel<MATV, EPTV>), dim3(NB_RED + nb + nbv), dim3(256), shm, st, PT, M.mass, e.xt, dtSq, e.partials, ctl, \
                        *e.step, M.nV, M.adj_ptr, M.adj_idx, d.Hval, d.z, d.c_partials, d.p, d.Hp, d.partials, nb)
-    if (mat == 0) {
-        if (ept == 1) DS_LAUNCH(0, 1);
-        else DS_LAUNCH(0, 2);
-    } else {
-        if (ept == 1) DS_LAUNCH(1, 1);
-        else DS_LAUNCH(1, 2);
-    }
+#define DS_LAUNCH_M(MATV)                   \
+    do {                                    \
+        if (ept == 1) DS_LAUNCH(MATV, 1);   \
+        else DS_LAUNCH(MATV, 2);            \
+    } while (0)
+    DM_DISPATCH_MAT(mat, DS_LAUNCH_M)
+#undef DS_LAUNCH_M
 #undef DS_LAUNCH
     return nb;
 }

@@ -392,6 +392,9 @@ __device__ __forceinline__ void elem_patch_body(const DevPatches &PT, const doub
                         }
                     }
                 }
+            } else if constexpr (MAT == 2) {
+                // log-regularised Stable Neo-Hookean: closed form too, stated once for every form of the pass (elem_math.hpp)
+                acc += snh_log_energy_stress(F, m[u], l[u], w, withGrad, P) * vo[u];
             } else {
                 Mat3 U, V;
                 double S[3];

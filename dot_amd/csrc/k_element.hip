@@ -71,13 +71,13 @@ static int launch_elem_impl(const DevMesh &M, const DevPatches &PT, int mat, dou
         if (ept == 1) DM_LAUNCH(MATV, GRADV, 1); \
         else DM_LAUNCH(MATV, GRADV, 2);          \
     } while (0)
-    if (mat == 0) {
-        if (grad) DM_LAUNCH_E(0, true);
-        else DM_LAUNCH_E(0, false);
-    } else {
-        if (grad) DM_LAUNCH_E(1, true);
-        else DM_LAUNCH_E(1, false);
-    }
+#define DM_LAUNCH_M(MATV)                     \
+    do {                                      \
+        if (grad) DM_LAUNCH_E(MATV, true);    \
+        else DM_LAUNCH_E(MATV, false);        \
+    } while (0)
+    DM_DISPATCH_MAT(mat, DM_LAUNCH_M)
+#undef DM_LAUNCH_M
 #undef DM_LAUNCH_E
 #undef DM_LAUNCH
     return nb;

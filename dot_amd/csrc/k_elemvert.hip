@@ -317,6 +317,8 @@ __global__ __launch_bounds__(256) void elem_vertex_kernel(DevVPatches VP, ElemVe
                     P[r][c] = w * (mu_[u] * F.m[r][c] + t * cof);
                 }
             }
+        } else if constexpr (MAT == 2) {
+            acc += snh_log_energy_stress(F, mu_[u], la_[u], w, true, P) * voE[u];   // (elem_patch_body: the same function)
         } else {
             Mat3 U, V;
             double S[3];
@@ -451,13 +453,13 @@ void launch_elem_vertex(const DevVPatches &VP, int mat, const ElemVertArgs &a, h
         if (rec) hipLaunchKernelGGL((elem_vertex_kernel<MATV, PAIRV, true>), dim3(NWG), dim3(256), shm, st, VP, a, ctl);     \
         else hipLaunchKernelGGL((elem_vertex_kernel<MATV, PAIRV, false>), dim3(NWG), dim3(256), shm, st, VP, a, ctl);        \
     } while (0)
-    if (paired) {
-        if (mat == 0) EV_LAUNCH(0, true, 2 * VP.nPatches);
-        else EV_LAUNCH(1, true, 2 * VP.nPatches);
-    } else {
-        if (mat == 0) EV_LAUNCH(0, false, VP.nPatches);
-        else EV_LAUNCH(1, false, VP.nPatches);
-    }
+#define EV_LAUNCH_M(MATV)                                      \
+    do {                                                       \
+        if (paired) EV_LAUNCH(MATV, true, 2 * VP.nPatches);    \
+        else EV_LAUNCH(MATV, false, VP.nPatches);              \
+    } while (0)
+    DM_DISPATCH_MAT(mat, EV_LAUNCH_M)
+#undef EV_LAUNCH_M
 #undef EV_LAUNCH
 }
 

@@ -140,12 +140,11 @@ void launch_elem_hessians(const DevMesh &M, int mat, double dtSq, const double *
     const int n = elist ? nList : M.nT;
     const int nb = (n + 63) / 64;
     if (nb <= 0) return;
-    if (mat == 0)
-        hipLaunchKernelGGL((elem_hessian_kernel<0>), dim3(nb), dim3(64), 0, st, M.T, M.A, M.nTp, n, M.mu, M.lam, M.vol,
-                           x, dtSq, elist, He);
-    else
-        hipLaunchKernelGGL((elem_hessian_kernel<1>), dim3(nb), dim3(64), 0, st, M.T, M.A, M.nTp, n, M.mu, M.lam, M.vol,
-                           x, dtSq, elist, He);
+#define EH_LAUNCH(MATV)                                                                                                    \
+    hipLaunchKernelGGL((elem_hessian_kernel<MATV>), dim3(nb), dim3(64), 0, st, M.T, M.A, M.nTp, n, M.mu, M.lam, M.vol, \
+                       x, dtSq, elist, He)
+    DM_DISPATCH_MAT(mat, EH_LAUNCH)
+#undef EH_LAUNCH
 }
 
 // global block-CSR assembly in gather form: thread = (block k, entry rc)

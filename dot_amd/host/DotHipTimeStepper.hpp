@@ -38,7 +38,7 @@ struct MeshView {  // Mesh<3> fields the path reads (src/Mesh.hpp:38-60); row-ma
 };
 
 struct Options {  // the Config fields the DOT stepper reads (src/Config.hpp)
-    int energyType = DOTMI_ENERGY_FCR;  // ET_FCR / ET_SNH
+    int energyType = DOTMI_ENERGY_FCR;  // ET_FCR / ET_SNH / DOTMI_ENERGY_SNH_LOG (ET_SNH of a reference build with SNH_WITHLOG)
     bool withGravity = true;
     int partitionAmt = 4;
     const int32_t *epart = nullptr;  // METIS::partMesh result (nT)

@@ -15,7 +15,7 @@
 //
 // usage: dot_hip 100 <script.txt> [--mesh-root DIR] [--parts N] [--energy FCR|SNH] [--epart raw.i32]
 //                [--frames K] [--out DIR] [--device D] [--no-files] [--dump-scene K] [--dump-config] [--dump-formats DIR]
-//                [--echo-config FILE] [--fast] [--newton-pcg N [--pcg-coarse]] [--dot-coarse]
+//                [--echo-config FILE] [--fast] [--newton-pcg N [--pcg-coarse]] [--dot-coarse] [--snh-log]
 //        dot_hip --write-info FILE nV nT steps iters t0..t21
 #include <algorithm>
 #include <chrono>
@@ -48,7 +48,7 @@ int main(int argc, char **argv)
     }
     if (argc < 3) {
         std::fprintf(stderr, "usage: %s 100 <script.txt> [--mesh-root DIR] [--parts N] [--energy FCR|SNH] "
-                             "[--epart raw.i32] [--frames K] [--out DIR] [--device D] [--no-files] [--dump-scene K] [--dump-config] [--dump-formats DIR] [--fast] [--newton-pcg N [--pcg-coarse]] [--dot-coarse]\n", argv[0]);
+                             "[--epart raw.i32] [--frames K] [--out DIR] [--device D] [--no-files] [--dump-scene K] [--dump-config] [--dump-formats DIR] [--fast] [--newton-pcg N [--pcg-coarse]] [--dot-coarse] [--snh-log]\n", argv[0]);
         return 2;
     }
     if (std::string(argv[1]) != "100") {
@@ -58,7 +58,7 @@ int main(int argc, char **argv)
     const std::string scriptPath = argv[2];
     std::string meshRoot = ".", outDir, epartFile, energyOverride;
     int partsOverride = -1, frames = -1, device = 0, dumpScene = -1, newtonPcgParts = 0;
-    bool files = true, dumpConfig = false, fast = false, pcgCoarse = false, dotCoarse = false;
+    bool files = true, dumpConfig = false, fast = false, pcgCoarse = false, dotCoarse = false, snhLog = false;
     std::string dumpFormats, echoConfig;
     for (int i = 3; i < argc; ++i) {
         const std::string a = argv[i];
@@ -83,6 +83,10 @@ int main(int argc, char **argv)
         else if (a == "--pcg-coarse") pcgCoarse = true;
         // `timeStepper DOT` scripts: the rigid-mode coarse term in DOT's own block preconditioner (dotmi_set_dot_coarse)
         else if (a == "--dot-coarse") dotCoarse = true;
+        // `energy SNH` scripts: the log-regularised form of the material (DOTMI_ENERGY_SNH_LOG), what a reference build with
+        // SNH_WITHLOG runs for the same script.  The reference chooses it at compile time, so it is no script token and
+        // config.txt keeps echoing `energy SNH`
+        else if (a == "--snh-log") snhLog = true;
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     try {
@@ -107,6 +111,7 @@ int main(int argc, char **argv)
             return 0;
         }
         if (!energyOverride.empty()) cfg.energy = energyOverride;
+        if (snhLog && cfg.energy != "SNH") throw std::runtime_error("--snh-log is a variant of `energy SNH`: not with energy " + cfg.energy);
         if (cfg.shapePath.empty()) throw std::runtime_error("script has no `shape input <mesh>` (primitive shapes are 2-D only)");
         TetMesh mesh = load_tet_mesh(cfg.shapePath[0] == '/' ? cfg.shapePath : meshRoot + "/" + cfg.shapePath);
         normalize(mesh.V, cfg.size, cfg.rotDeg, cfg.rotAxis);
@@ -206,7 +211,7 @@ int main(int argc, char **argv)
         mv.nV = mesh.nV(); mv.nT = mesh.nT(); mv.V_rest = mesh.V.data(); mv.F = mesh.T.data();
         mv.u = u.data(); mv.lambda = lambda.data(); mv.density = cfg.rho; mv.isFixedVert = scripter.fixed.data();
         Options opt;
-        opt.energyType = cfg.energy == "SNH" ? DOTMI_ENERGY_SNH : DOTMI_ENERGY_FCR;
+        opt.energyType = cfg.energy == "SNH" ? (snhLog ? DOTMI_ENERGY_SNH_LOG : DOTMI_ENERGY_SNH) : DOTMI_ENERGY_FCR;
         opt.withGravity = cfg.withGravity; opt.partitionAmt = nParts; opt.epart = epart.data(); opt.device = device;
         // the reference keeps its timer_step running all the time; here the per-phase HIP-event brackets cost a
         // host-driven loop, so they are on whenever files are written unless --fast asks for the device-resident loop

@@ -19,6 +19,7 @@ c_up = C.POINTER(C.c_uint8)
 
 ENERGY_FCR = 0
 ENERGY_SNH = 1
+ENERGY_SNH_LOG = 2
 FLAG_TIME_BACKSOLVE = 2
 FLAG_FORCE_DIST = 4
 FLAG_HOST_LOOP = 8

@@ -20,6 +20,7 @@ import numpy as np
 
 ENERGY_FCR = 0
 ENERGY_SNH = 1
+ENERGY_SNH_LOG = 2   # the log-regularised form: `energy SNH` in a reference build with SNH_WITHLOG (StableNHEnergy.cpp:84-89)
 
 
 @dataclasses.dataclass
@@ -45,9 +46,16 @@ class Config:
     tol: Optional[List[float]] = None
     restart: bool = False          # `restart <status file>` (Config.cpp:164-167)
     status_path: str = ""
+    # Not a script token: the reference chooses the log-regularised Stable Neo-Hookean form at compile time (SNH_WITHLOG,
+    # Utils/Types.hpp:36), so it stands beside the script.  Turns `energy SNH` into ENERGY_SNH_LOG; an error with FCR.
+    snh_log: bool = False
 
     @property
     def energy_id(self) -> int:
+        if self.snh_log:
+            if self.energy != "SNH":
+                raise ValueError(f"snh_log is a variant of `energy SNH`: not with energy {self.energy}")
+            return ENERGY_SNH_LOG
         return ENERGY_SNH if self.energy == "SNH" else ENERGY_FCR
 
 

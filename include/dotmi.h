@@ -27,6 +27,10 @@ extern "C" {
 
 #define DOTMI_ENERGY_FCR 0 /* FixedCoRotEnergy   (src/Energy/Physics_Elasticity/FixedCoRotEnergy.cpp) */
 #define DOTMI_ENERGY_SNH 1 /* StableNHEnergy     (src/Energy/Physics_Elasticity/StableNHEnergy.cpp)  */
+/* the log-regularised form that StableNHEnergy.cpp holds beside the plain one and a reference build with SNH_WITHLOG
+ * (src/Utils/Types.hpp:36) runs for the script line `energy SNH`: Psi :84-89, dPsi/dsigma :102-114, d2Psi/dsigma2 :134-171,
+ * B-left :204-216, dPsi/dF :237-243.  3-D only. */
+#define DOTMI_ENERGY_SNH_LOG 2
 
 #define DOTMI_E_INVALID -1  /* bad argument */
 #define DOTMI_E_DEVICE -2   /* HIP / RCCL runtime error */
