@@ -89,6 +89,23 @@ int dotmi_refix(dotmi_handle *h, const uint8_t *fixed)
 
 int dotmi_operand_records(const dotmi_handle *h) { return h && h->vpFits ? (h->VP.orec ? 1 : 0) : -1; }
 
+// the forms this handle's loop launches: the launchers' own three functions (loop_forms.hpp) on the counts the launchers see -- every
+// vertex, or the held ones under the owner exchange --, and only for the launches the handle's loop contains
+int dotmi_loop_forms(const dotmi_handle *h)
+{
+    if (!h) return DOTMI_E_INVALID;
+    const long long nv = h->owner ? h->nHeld : h->nV;
+    int forms = 0;
+    if (h->devLoop) {
+        if (gather_is_wide(3 * nv, h->tune.wideForms)) forms |= FORM_WIDE_GATHER;
+        if (h->earlyBs && merge_early_is_wide(3 * nv, h->tune.wideForms)) forms |= FORM_WIDE_MERGE;
+        if (h->earlyBs && (h->owner || h->tune.fuseDir) && spmv_zp_is_wide(nv, h->tune.wideForms)) forms |= FORM_WIDE_SPMV;
+    }
+    if (h->P.splitMerge) forms |= FORM_SPLIT_MERGE;
+    if (h->P.tl.on && h->P.tl.nPanels > 0) forms |= twolevel_backward_code(h->P.tl.maxCols) << FORM_TWOLEVEL_CW_SHIFT;
+    return forms;
+}
+
 double dotmi_target_gres(const dotmi_handle *h) { return h ? h->targetGRes : 0.0; }
 
 int dotmi_last_iter_log(const dotmi_handle *h, int32_t cap, double *alpha, double *E, double *g2)
@@ -555,7 +572,7 @@ int dotmi_bench_kernel(dotmi_handle *h, int32_t kind, int32_t reps, double *ms_p
         live = true;
         run = [&] {
             if (!h->P.mt_ptr) launch_reduce_partial(h->P, h->st, h->ctl);
-            launch_merge_early(h->M, h->P, {.z = h->z, .partials = h->partC, .partialsT = h->dist ? nullptr : h->partCT}, h->st, h->ctl);
+            launch_merge_early(h->M, h->P, {.z = h->z, .partials = h->partC, .partialsT = h->dist ? nullptr : h->partCT, .wide = h->tune.wideForms}, h->st, h->ctl);
         };
         break;
     case DOTMI_BENCH_ELEM_STEP: {        // the element pass with the line-search step inside: + p read, trial point written

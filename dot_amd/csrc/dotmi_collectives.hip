@@ -72,7 +72,7 @@ int merge_over_ranks(dotmi_handle *h, const LbfgsArgs &L, double *packet, RankSu
     if (co) dot_coarse_solve(h, packet + h->n, ctl, 0);
     const int first = end == RANKSUM_EARLY_FIRST;
     if (end == RANKSUM_ZFINISH) launch_zfinish(h->nV, h->P.dup, L, packet, h->partC, h->st, ctl, co);
-    else launch_merge_early(h->M, h->P, {.z = h->z, .partials = h->partC, .first = first, .zsum = packet, .co = co}, h->st, ctl);
+    else launch_merge_early(h->M, h->P, {.z = h->z, .partials = h->partC, .first = first, .zsum = packet, .co = co, .wide = h->tune.wideForms}, h->st, ctl);
     return 0;
 }
 

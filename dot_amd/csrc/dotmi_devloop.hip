@@ -131,7 +131,7 @@ static void slot_backsolve(dotmi_handle *h, const Slot &s)
 static int slot_merge(dotmi_handle *h)
 {
     if (!h->dist) {
-        launch_merge_early(h->M, h->P, {.z = h->z, .partials = h->partC, .partialsT = h->partCT, .co = dot_coarse(h)}, h->st, h->ctl);
+        launch_merge_early(h->M, h->P, {.z = h->z, .partials = h->partC, .partialsT = h->partCT, .co = dot_coarse(h), .wide = h->tune.wideForms}, h->st, h->ctl);
     } else if (!h->owner) {
         // sharded subdomains: this rank's part of the sum, the one collective of the iteration (issued in every slot,
         // whatever the controller decided: every rank enqueues the same sequence), then the division and the history terms
@@ -149,10 +149,10 @@ static int slot_merge(dotmi_handle *h)
         // u_old, M y_new and the y_i . z on the vertices only this rank holds, its part of the sum (to zstage) and its share
         // of the y_i . z on the shared ones --, then the exchange, then the shared vertices
         launch_merge_early(h->M, h->P, {.z = h->z, .partials = h->partC, .ownMask = h->ownMask, .vl = h->held(), .kind = h->vkind, .pre = 1,
-                                        .zshare = h->zstage}, h->st, h->ctl);
+                                        .zshare = h->zstage, .wide = h->tune.wideForms}, h->st, h->ctl);
         if (int rc = exchange_solve_packed(h)) return rc;
         if (h->nShared > 0)
-            launch_merge_early(h->M, h->P, {.z = h->z, .zsum = h->zstage, .ownMask = h->ownMask, .vl = h->shared()}, h->st, h->ctl);
+            launch_merge_early(h->M, h->P, {.z = h->z, .zsum = h->zstage, .ownMask = h->ownMask, .vl = h->shared(), .wide = h->tune.wideForms}, h->st, h->ctl);
     }
     return 0;
 }
@@ -336,7 +336,7 @@ static int step_start_sharded(dotmi_handle *h, int nb)
     launch_merge(h->M, h->P, NO_HISTORY, {.z = h->zstage, .vl = h->held()}, h->st, h->ctl);
     if (int rc = exchange_iface(h, h->zstage, nullptr, 0)) return rc;
     // (no pair yet: no y_i . z to sum, no partials)
-    launch_merge_early(h->M, h->P, {.z = h->z, .first = 1, .zsum = h->zstage, .ownMask = h->ownMask, .vl = h->held()}, h->st, h->ctl);
+    launch_merge_early(h->M, h->P, {.z = h->z, .first = 1, .zsum = h->zstage, .ownMask = h->ownMask, .vl = h->held(), .wide = h->tune.wideForms}, h->st, h->ctl);
     HIPCHECK(h, hipMemsetAsync(h->partGC, 0, sizeof(double) * HIST_MAX, h->st));
     return 0;
 }
@@ -386,7 +386,7 @@ static int enqueue_step_start(dotmi_handle *h)
     CtlLaunch ca{{h->ctl, h->partE, h->partR, h->alpha_dev, h->h_flags, nb, 1}, h->vpNow ? CTL_VP : CTL_PLAIN};
     launch_gemv(h->P, nullptr, h->st, h->ctl, nullptr, nullptr, &ca, 1 << 30);
     if (h->dist) return merge_over_ranks(h, NO_HISTORY, h->zstage, RANKSUM_EARLY_FIRST, h->ctl);
-    launch_merge_early(h->M, h->P, {.z = h->z, .partials = h->partC, .partialsT = h->partCT, .first = 1, .co = co}, h->st, h->ctl);
+    launch_merge_early(h->M, h->P, {.z = h->z, .partials = h->partC, .partialsT = h->partCT, .first = 1, .co = co, .wide = h->tune.wideForms}, h->st, h->ctl);
     return 0;
 }
 

@@ -40,6 +40,7 @@
 #include "../../include/dotmi.h"
 #include "dotmi_internal.hpp"
 #include "elem_math.hpp"
+#include "loop_forms.hpp"
 #include "partition.hpp"
 #include "patches.hpp"
 #include "tuning.hpp"

@@ -450,6 +450,7 @@ struct GatherArgs {
     const uint8_t *kind;
     int pre;
     double *gshare;
+    int wide = -1;      // DOTMI_WIDE_FORMS (Tuning::wideForms): -1 the form by the number of dofs, else the mask whose bit 1 forces it (loop_forms.hpp)
 };
 void launch_vertex_gather(const DevMesh &M, const DevPatches &PT, const GatherArgs &a, const LbfgsArgs &L,
                           double *partials, hipStream_t st, const DevLoop *ctl = nullptr);
@@ -497,6 +498,7 @@ struct MergeEarlyArgs {
     int pre = 0;
     double *zshare = nullptr;
     const CoarseMerge *co = nullptr;    // dotmi_set_dot_coarse: u += Z y behind the division, the COARSE instantiation
+    int wide = -1;                      // DOTMI_WIDE_FORMS (Tuning::wideForms): -1 the form by the number of dofs, else the mask whose bit 2 forces it (loop_forms.hpp)
 };
 void launch_merge_early(const DevMesh &M, const DevParts &P, const MergeEarlyArgs &a, hipStream_t st, const DevLoop *ctl);
 // owner exchange: the entries of the vertices held by more than one rank, packed / unpacked (idx: their vertex ids);
@@ -551,7 +553,7 @@ struct SpmvZpArgs {
     // the vertices it owns
     const uint8_t *rowMask = nullptr, *ownMask = nullptr;
     VList vl;
-    int wide = -1;                        // DOTMI_SPMV_WIDE: 0 / 1 forces the 256- / 1024-thread form (-1: by the number of rows)
+    int wide = -1;                        // DOTMI_WIDE_FORMS (Tuning::wideForms): -1 the form by the number of rows, else the mask whose bit 4 forces it (loop_forms.hpp)
 };
 void launch_spmv_zp(const DevMesh &M, const SpmvZpArgs &a, hipStream_t st, const DevLoop *ctl);
 // the direction kernel and the first trial's element pass at the unit step in one launch of two workgroup populations

@@ -54,14 +54,14 @@ void stage_energy(dotmi_handle *h, int nb, double *dst)
 }
 
 // ---- the operand records of the loop's launches, built from the handle once (dotmi_handle.hpp); the call sites set what differs ----
-GatherArgs gather_args(const dotmi_handle *h) { return {.xt = h->xt, .iv0 = h->v0, .iv1 = h->v1}; }
+GatherArgs gather_args(const dotmi_handle *h) { return {.xt = h->xt, .iv0 = h->v0, .iv1 = h->v1, .wide = h->tune.wideForms}; }
 
 // the early order's gather: the new pair and its statistics, H s_new = alpha H p beside s_new (the fused direction kernel's H p: the
 // owner exchange has no other), -g_trial straight into the padded right-hand sides
 GatherArgs early_gather_args(const dotmi_handle *h)
 {
     return {.xt = h->xt, .p = h->p, .alpha_dev = h->alpha_dev, .make_pair = 1, .iv0 = h->v0, .iv1 = h->v1, .vp_ptr = h->P.vp_ptr,
-            .vp_off = h->P.vp_off, .rpad = h->P.rpad, .hp = h->tune.fuseDir ? h->Hp : nullptr};
+            .vp_off = h->P.vp_off, .rpad = h->P.rpad, .hp = h->tune.fuseDir ? h->Hp : nullptr, .wide = h->tune.wideForms};
 }
 
 // the loop's direction kernel (build_p + spmv_dots in one launch, H p from the cached H s_j) in its three forms
@@ -69,12 +69,12 @@ SpmvZpArgs spmv_zp_args(const dotmi_handle *h, bool sharded)
 {
     if (sharded && h->owner)   // the held rows with this rank's own elements' part of H; the y_i . z came with the packet
         return {.Hval = h->HvalOwn, .z = h->z, .c_partials = h->partGC, .p = h->p, .Hp = h->Hp, .partials = h->partS,
-                .rowMask = h->heldMask, .ownMask = h->ownMask, .vl = h->held(), .wide = h->tune.spmvWide};
+                .rowMask = h->heldMask, .ownMask = h->ownMask, .vl = h->held(), .wide = h->tune.wideForms};
     // one rank: the y_i . z partials from their column-major twin, which merge_early writes beside the rows; partST: the twin of
     // p.g / p.Hp that elem_vertex_kernel reads; a sharded element pass: this rank's rows
     const bool rows = sharded && h->shardElems;
     return {.Hval = h->Hval, .z = h->z, .c_partials = h->dist ? h->partC : h->partCT, .ctrans = !h->dist, .p = h->p, .Hp = h->Hp,
-            .partials = h->partS, .partialsT = h->partST, .v0 = rows ? h->v0 : 0, .v1 = rows ? h->v1 : -1, .wide = h->tune.spmvWide};
+            .partials = h->partS, .partialsT = h->partST, .v0 = rows ? h->v0 : 0, .v1 = rows ? h->v1 : -1, .wide = h->tune.wideForms};
 }
 
 // x_trial = x + alpha p, alpha from the p.g / p.Hp partials when there are any; the step taken goes to alpha_dev

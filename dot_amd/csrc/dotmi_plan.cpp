@@ -9,6 +9,7 @@
 #include "block_plan.hpp"
 #include "coarse_plan.hpp"
 #include "ic_plan.hpp"
+#include "loop_forms.hpp"
 #include "partition.hpp"
 #include "pd_plan.hpp"
 #include "tuning.hpp"
@@ -125,6 +126,15 @@ int dotmi_plan_shards(int32_t nParts, const int32_t *part_scalar_size, int32_t w
         c = std::min(std::max(c, first_part[r - 1]), nParts);
         first_part[r] = c;
     }
+    return 0;
+}
+
+// host-only: which of the loop's three kernels take their wide form on launches of these sizes (loop_forms.hpp: the functions the
+// launchers of k_loopvec.hip and dotmi_loop_forms call), as the mask 1 gather | 2 early merge | 4 direction kernel
+int dotmi_plan_loop_forms(int64_t ndof_gather, int64_t ndof_merge, int64_t nrows_spmv, int32_t force, int32_t *out)
+{
+    if (ndof_gather < 0 || ndof_merge < 0 || nrows_spmv < 0 || !out) return DOTMI_E_INVALID;
+    *out = loop_forms_mask(ndof_gather, ndof_merge, nrows_spmv, force);
     return 0;
 }
 

@@ -4,6 +4,7 @@
 // scalar loads of the others; every unit is compiled once.  Conventions and the reference map: k_device.hpp)
 #include "k_device.hpp"
 #include "k_loopctl.hpp"
+#include "loop_forms.hpp"
 
 namespace dotmi {
 
@@ -880,11 +881,11 @@ static void launch_gemv_impl(const DevParts &P, const double *q, hipStream_t st,
     if (P.tl.on && P.tl.nPanels > 0)   // p_D = q_D - M_GD^T p_G on the sums just formed
     {
         const size_t shm = 8 * (size_t)((P.tl.maxRows + 7) & ~7) + 16 * 256;   // (dotmi_create refuses panels beyond 7000 rows)
-        const int n2 = P.tl.maxCols / 2;
-        if (n2 <= 32)
+        const int cw = twolevel_backward_cw(P.tl.maxCols);   // (loop_forms.hpp: dotmi_loop_forms reports the same choice)
+        if (cw == 32)
             hipExtLaunchKernelGGL(twolevel_backward_kernel<32>, dim3(P.tl.nPanels), dim3(256), shm, st, (hipEvent_t) nullptr, evLast, 0,
                                   P.tl.panel, P.tl.rowBase, P.tl.rowPos, (const double *)P.tl.packed, P.psub, ctl);
-        else if (n2 <= 64)
+        else if (cw == 64)
             hipExtLaunchKernelGGL(twolevel_backward_kernel<64>, dim3(P.tl.nPanels), dim3(256), shm, st, (hipEvent_t) nullptr, evLast, 0,
                                   P.tl.panel, P.tl.rowBase, P.tl.rowPos, (const double *)P.tl.packed, P.psub, ctl);
         else

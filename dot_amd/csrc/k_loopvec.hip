@@ -3,6 +3,7 @@
 // scalar loads of the others; every unit is compiled once.  Conventions and the reference map: k_device.hpp)
 #include "k_device.hpp"
 #include "k_dirbody.hpp"
+#include "loop_forms.hpp"
 
 namespace dotmi {
 
@@ -76,8 +77,11 @@ __device__ __forceinline__ void pair_stats_accum(int k, double gn, double sn, do
 // dependent round trips of a trip (partial range -> partials) are paid once for all of them.
 constexpr int GATHER_R = 4;
 constexpr int GATHER_P = 4;   // partials requested together; a vertex with more takes further rounds
-// NT: threads per workgroup (256; 1024 for meshes whose dofs take the 256-thread form more than two trips: the same dofs per
-// workgroup with a quarter of them per lane -- four waves per SIMD instead of four dofs interleaved in one)
+static_assert(LOOP_NB_RED == NB_RED && LOOP_GATHER_R == GATHER_R && LOOP_SPMV_R == SPMV_R,
+              "loop_forms.hpp states its thresholds in the trips of these kernels");
+// NT, GR: threads per workgroup and dofs per lane and trip (256 x 4; 512 x 2 for meshes whose dofs take the 256-thread form more
+// than two trips, gather_is_wide: the same dofs per workgroup and trip with half of them per lane -- two waves per SIMD instead of
+// four dofs interleaved in one)
 template <bool DEV, int NT = 256, int GR = GATHER_R>
 __global__ __launch_bounds__(NT) void vertex_gather_kernel(
     int nV, const int2 *__restrict__ pp_rng, const double *__restrict__ gpart,
@@ -234,7 +238,7 @@ void launch_vertex_gather(const DevMesh &M, const DevPatches &PT, const GatherAr
                           double *partials, hipStream_t st, const DevLoop *ctl)
 {
     const long long ndof = a.vlist ? 3ll * a.nlist : 3ll * M.nV;
-    if (ctl && ndof > 2ll * GATHER_R * NB_RED * 256)   // (more than two trips of the 256-thread form: 1 M tets)
+    if (ctl && gather_is_wide(ndof, a.wide))   // (loop_forms.hpp: more than two trips of the 256-thread form -- 1 M tets --, or forced)
         hipLaunchKernelGGL((vertex_gather_kernel<true, 512, 2>), dim3(NB_RED), dim3(512), 0, st, M.nV, PT.pp_rng, PT.gpart,
                            M.fixed, M.mass, a, L, partials, ctl);
     else if (ctl)
@@ -911,9 +915,10 @@ static void merge_dispatch(bool first, const CoarseMerge *co, F &&f)
 void launch_merge_early(const DevMesh &M, const DevParts &P, const MergeEarlyArgs &a, hipStream_t st, const DevLoop *ctl)
 {
     const bool split = !P.mt_ptr;
-    // (a thread of the 256-thread form takes a dof per trip: beyond two trips -- 1 M tets: eight -- workgroups of 1024 threads)
+    // (a thread of the 256-thread form takes a dof per trip: beyond two trips -- 1 M tets: eight -- workgroups of 512 threads;
+    // loop_forms.hpp)
     const long long ndof = a.vl.v ? 3ll * a.vl.n : 3ll * M.nV;
-    merge_dispatch(ndof > 2ll * NB_RED * 256, a.co, [&](auto wide, auto c) {
+    merge_dispatch(merge_early_is_wide(ndof, a.wide), a.co, [&](auto wide, auto c) {
         constexpr int NT = decltype(wide)::value ? 512 : 256;
         hipLaunchKernelGGL((merge_tiles_early_kernel<NT, decltype(c)::on>), dim3(NB_RED), dim3(NT), 0, st, 3 * M.nV, P.mt_ptr, P.mt_ent,
                            P.dup, P.ppart, a.first, a.zsum, split ? P.vp_ptr : nullptr, split ? P.vp_off : nullptr,
@@ -1124,9 +1129,9 @@ void launch_spmv_zp(const DevMesh &M, const SpmvZpArgs &a, hipStream_t st, const
     // Rows beyond one trip of the 256-thread form (256 workgroups x 32 lane groups x 3 rows): workgroups of 1024 threads, a
     // row per lane group -- four waves per SIMD hide what the interleaving of three rows inside one wave cannot once the kernel
     // is bound by throughput (1 M tets: 76.9 -> 56.9 us; bar17K, one trip: 11.8 -> 12.9, stays on 256 threads).
-    // a.wide = 0 / 1 (DOTMI_SPMV_WIDE, Tuning::spmvWide) forces the form.
+    // The rule, and how a.wide (DOTMI_WIDE_FORMS, Tuning::wideForms) forces the form: loop_forms.hpp.
     const int nrows = a.vl.v ? a.vl.n : M.nV;
-    const bool wide = a.wide >= 0 ? a.wide != 0 : nrows > NB_RED * 32 * SPMV_R;
+    const bool wide = spmv_zp_is_wide(nrows, a.wide);
     const int c_blocks = a.ctrans ? -NB_RED : NB_RED;
     if (wide)
         hipLaunchKernelGGL(spmv_zp_wide_kernel, dim3(NB_RED), dim3(1024), 0, st, M.nV, a.v0, v1, a.rowMask, a.ownMask, M.adj_ptr, M.adj_idx,

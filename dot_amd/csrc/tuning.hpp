@@ -47,8 +47,11 @@ struct Tuning {
     int tileEagerMinRmul = -1; // DOTMI_TILE_EAGER_MIN_RMUL early products the last task of a Q tile may keep (-1: as the others; 0: none)
     bool tileEagerMinRmulByUser = false;   //           (unset: one up to 64 subdomains, as the others above)
     bool fuseDir = true;      // DOTMI_FUSE_DIR=0     (early order) build_p and spmv_dots as two launches instead of one on cached H s_j
-    int spmvWide = -1;        // DOTMI_SPMV_WIDE      0 / 1: force the 256- / 1024-thread form of the direction kernel (-1: by the number of
-                              //                      rows, launch_spmv_zp; reaches it as SpmvZpArgs::wide)
+    int wideForms = -1;       // DOTMI_WIDE_FORMS     -1 (default): the vertex gather, the early merge and the direction kernel choose their
+                              //                      narrow or wide form by the size of the mesh (loop_forms.hpp); any other value is a bit
+                              //                      mask -- 1 gather, 2 early merge, 4 direction kernel -- whose set bits force the wide form
+                              //                      (512 / 512 / 1024 threads) and whose clear bits force the narrow one (0: all narrow,
+                              //                      7: all wide); reaches the launchers as GatherArgs / MergeEarlyArgs / SpmvZpArgs::wide
     bool fuseStep = true;     // DOTMI_FUSE_STEP=0    (early order) step_forward as a launch of its own instead of inside the element pass
     int pairTrials = -1;      // DOTMI_PAIR_TRIALS    -1 (default): paired line-search trials (StepArgs::pairBlocks) in a step whose predecessor
                               //                      halved in at least a quarter of its iterations; 1: in every step; 0: never
@@ -109,7 +112,8 @@ struct Tuning {
         t.vertexPatches = geti("DOTMI_VERTEX_PATCHES", -1);
         t.fuseStep = geti("DOTMI_FUSE_STEP", 1) != 0;
         t.fuseDir = geti("DOTMI_FUSE_DIR", 1) != 0;
-        t.spmvWide = geti("DOTMI_SPMV_WIDE", -1);
+        t.wideForms = geti("DOTMI_WIDE_FORMS", -1);
+        if (t.wideForms < -1) t.wideForms = -1;
         t.operandRecords = geti("DOTMI_OPERAND_RECORDS", 1) & 1;
         return t;
     }

@@ -371,6 +371,12 @@ class DOTTimeStepper:
         """0: explicit inverse in one pass; 1: two-level form (dotmi_backsolve_form)"""
         return int(self._L.dotmi_backsolve_form(self._h))
 
+    def loopForms(self) -> int:
+        """which forms of its kernels this handle's loop launches, as a bit mask (dotmi_loop_forms): 1 / 2 / 4 = the vertex gather, the
+        early merge and the direction kernel in their wide form (by size, or forced with DOTMI_WIDE_FORMS); 8 = split merge; bits
+        16-17 = the two-level backward kernel's width (0 none, 1 / 2 / 3 = 32 / 64 / 128)"""
+        return int(self._L.dotmi_loop_forms(self._h))
+
     def benchPrecond(self, reps: int = 50):
         ms = C.c_double(); nb = C.c_int64()
         self._check(self._L.dotmi_bench_precond(self._h, reps, C.cast(C.byref(ms), _lib.c_dp), C.byref(nb)),

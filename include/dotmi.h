@@ -310,6 +310,19 @@ int dotmi_plan_vpatches(int32_t nV, int32_t nT, const int32_t *T, const double *
 /* (round 9) which loads the handle's one-launch element pass + gather (elem_vertex_kernel) uses: 1 = the operand records
  * (DOTMI_OPERAND_RECORDS, default, where their LDS fits), 0 = the flat arrays, -1 = the handle has no vertex patches */
 int dotmi_operand_records(const dotmi_handle *h);
+/* Which forms of its kernels the handle's loop launches, as a bit mask.  Bits 1 / 2 / 4: the vertex gather, the early merge and the
+ * direction kernel in their wide form (512 / 512 / 1024 threads per workgroup) instead of the 256-thread one -- chosen by the number of
+ * dofs / rows the launch visits (beyond 524 288 dofs, 131 072 dofs and 24 576 rows; under DOTMI_FLAG_OWNER_EXCHANGE those of the held
+ * vertices), or forced: the environment variable DOTMI_WIDE_FORMS, read by dotmi_create, is unset or -1 for the rule by size and
+ * otherwise this same mask of bits 1 | 2 | 4, a set bit forcing the wide form and a clear bit the narrow one (0: all narrow, 7: all
+ * wide; the results agree to rounding).  A bit is only set for a launch the handle's loop contains (the gather's on a device-resident
+ * loop, which launches it in the steps that do not run on vertex patches; the other two in the early order).  Bit 8: the merge is
+ * split (per-subdomain sums, then a gather: DOTMI_SPLIT_MERGE).  Bits 16-17: the column width of the two-level back-solve's backward
+ * kernel, 0 none (one-pass form, or no panels), 1 / 2 / 3 = 32 / 64 / 128 column pairs.  < 0: h is NULL */
+int dotmi_loop_forms(const dotmi_handle *h);
+/* (host only) the low three bits of dotmi_loop_forms for a launch of ndof_gather and ndof_merge scalar dofs and nrows_spmv block rows
+ * under the force value `force` (DOTMI_WIDE_FORMS: -1 by size, else the mask) -- the launchers' own rule, no device touched */
+int dotmi_plan_loop_forms(int64_t ndof_gather, int64_t ndof_merge, int64_t nrows_spmv, int32_t force, int32_t *out);
 /* (host only, round 9) the static operands of the owned vertices in PATCH order (vpatches.hpp: VpOwnRec, DOTMI_OPERAND_RECORDS), built
  * from the caller's flat arrays as dotmi_create builds them from its own: mass[nV], fixed[nV] and the CSR vp_ptr[nV + 1] / vp_off of a
  * vertex' copies in the padded right-hand sides.  hdr as dotmi_plan_vpatches; with pv_gid != NULL also pv_gid[patches * PV] (touched

@@ -91,6 +91,8 @@ def test_invalid_arguments_are_rejected_before_touching_a_device():
     assert L.dotmi_create(None, None, None, None) == -1
     assert L.dotmi_step(None, None) == -1
     assert L.dotmi_target_gres(None) == 0.0
+    assert L.dotmi_loop_forms(None) == -1
+    assert "dotmi_loop_forms" in dl.EXPORTS and "dotmi_plan_loop_forms" in dl.EXPORTS
 
 
 def test_cpp_adapter_builds_links_and_fails_loudly_or_steps(tmp_path):

@@ -25,20 +25,35 @@ def _with_env(env, fn):
             os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
 
 
+# twolevel_backward_kernel<CW> by the widest panel's columns in use (loop_forms.hpp; DOTTimeStepper.loopForms() bits 16-17: 1 / 2 / 3 =
+# CW 32 / 64 / 128 column pairs).  The workloads' leaves are regions of 192 - 768 padded columns, of which a panel uses those from the
+# leaf's first live column on: up to 128 on bar17K, bunny5K and the monkey (CW 64), more on kingkong (CW 128).  CW 32 needs leaves of at
+# most 64 columns, which the host-only planner (dot_amd.sharding.plan_layout, searched over small bars and part counts) gives only
+# under DOTMI_ND_MIN=128, the smallest split threshold the switch admits: synbar:10x4x4:3 (seven regions, leaves of 64 columns); with
+# it synbar:10x4x4:2, whose leaves are 128 columns wide.  Per workload: the switches both forms' handles take, the CW code
+ND_ENV = {"synbar:10x4x4:2": {"DOTMI_ND_MIN": "128"}, "synbar:10x4x4:3": {"DOTMI_ND_MIN": "128"}}
+CW_CODE = {"bar17K_twist": 2, "bunny5K_LTSS": 2, "monkey18K_stiff": 2, "kingkong18K_SS_1K": 3, "synbar:10x4x4:2": 2, "synbar:10x4x4:3": 1}
+
+
 @pytest.mark.parametrize("workload,steps,chaotic", [("bar17K_twist", 3, False), ("bunny5K_LTSS", 4, False),
-                                                    ("monkey18K_stiff", 1, True), ("kingkong18K_SS_1K", 2, False)])
+                                                    ("monkey18K_stiff", 1, True), ("kingkong18K_SS_1K", 2, False),
+                                                    ("synbar:10x4x4:2", 3, False), ("synbar:10x4x4:3", 3, False)])
 def test_two_level_form_applies_the_same_preconditioner_and_takes_the_same_steps(workload, steps, chaotic):
     """DOTMI_TWO_LEVEL=1 against =0 on the same mesh: M r on a random right-hand side agrees to rounding (1e-11 of its size) and
     with the oracle's block solve to 1e-9; the time steps take the same iterations and halvings and end at the same positions
     (1e-9; Stable Neo-Hookean and fixed-corotational meshes, deep and shallow trees, few and many subdomains).  The stiff monkey's
     107 back-tracking iterations follow the factors' last bits (tests/test_gpu_parity.py: only a prefix is comparable): there both
     forms must converge, to the same energy."""
+    nd_env, cw_code = ND_ENV.get(workload, {}), CW_CODE[workload]
     out = {}
     for tag, v in (("one", "0"), ("two", "1")):
         def run():
             sc, ep, n = load_workload(workload)
             ts = DOTTimeStepper(sc, ep, n)
             assert ts.backsolveForm() == int(v)
+            cw = (ts.loopForms() >> 16) & 3
+            print(f"{workload} DOTMI_TWO_LEVEL={v}: backward kernel width code {cw}")
+            assert cw == (0 if v == "0" else cw_code)
             rng = np.random.default_rng(5)
             r = rng.standard_normal((sc.V_rest.shape[0], 3)) * (1 - sc.fixed[:, None])
             p = ts.applyPrecond(r)
@@ -52,7 +67,7 @@ def test_two_level_form_applies_the_same_preconditioner_and_takes_the_same_steps
             nbytes, E = st.precond_bytes, st.E
             ts.close()
             return r, p, log, x, nbytes, E
-        out[tag] = _with_env({"DOTMI_TWO_LEVEL": v}, run)
+        out[tag] = _with_env({"DOTMI_TWO_LEVEL": v, **nd_env}, run)
     (r, p1, log1, x1, b1, E1), (_, p2, log2, x2, b2, E2) = out["one"], out["two"]
     assert np.abs(p1 - p2).max() <= 1e-11 * np.abs(p1).max()
     assert all(s[0] == 0 for s in log1 + log2)
@@ -62,8 +77,9 @@ def test_two_level_form_applies_the_same_preconditioner_and_takes_the_same_steps
         assert log1 == log2
         assert np.abs(x1 - x2).max() < 1e-9
     assert b2 != b1      # (another count of bytes: leaves + separator complement once, panels twice)
-    sc, ep, n, ts, orc = _with_env({"DOTMI_TWO_LEVEL": "1"}, lambda: make_pair(workload))
+    sc, ep, n, ts, orc = _with_env({"DOTMI_TWO_LEVEL": "1", **nd_env}, lambda: make_pair(workload))
     try:
+        assert (ts.loopForms() >> 16) & 3 == cw_code
         po = orc.apply_precond(r)
         assert np.abs(ts.applyPrecond(r) - po).max() <= 1e-9 * np.abs(po).max()
     finally:

@@ -15,9 +15,11 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _worker(rank, world, initfile, outdir, workload, shard_elems, steps, material=None):
-    """material: optional (kind, seed) of a per-element Lame field of tests/materials.py, rebuilt here from its name"""
+def _worker(rank, world, initfile, outdir, workload, shard_elems, steps, material=None, rank_env=None):
+    """material: optional (kind, seed) of a per-element Lame field of tests/materials.py, rebuilt here from its name
+    rank_env: environment switches of the ranks' handles only (the single-GPU run they are compared with keeps the caller's)"""
     sys.path.insert(0, ROOT)
+    os.environ.update(rank_env or {})
     owner = shard_elems.startswith("owner")   # DOTMI_FLAG_OWNER_EXCHANGE: interface-only exchange, owner-summed dot products
     if owner:
         shard_elems = "1"
@@ -57,7 +59,7 @@ def _worker(rank, world, initfile, outdir, workload, shard_elems, steps, materia
     r = np.random.default_rng(3).standard_normal(sc.x0.shape) * (1 - sc.fixed[:, None])
     z = ts.applyPrecond(r)
     np.savez(os.path.join(outdir, f"rank{rank}.npz"), x=ts.getResult(), v=ts.getState()[1], its=its, halv=halv, E=Es,
-             z=z, calls=loop_calls, bytes=loop_bytes)
+             z=z, calls=loop_calls, bytes=loop_bytes, forms=ts.loopForms())
     ts.close()
     dist.barrier()
     dist.destroy_process_group()
@@ -91,7 +93,8 @@ def test_ranks_with_per_element_materials_reproduce_the_single_gpu_run():
     _ranks_reproduce_the_single_gpu_run("bunny5K_LTSS", 4, "1", 2, material=("random", 0))
 
 
-def _ranks_reproduce_the_single_gpu_run(workload, steps, shard_elems, world, material=None):
+def _ranks_reproduce_the_single_gpu_run(workload, steps, shard_elems, world, material=None, rank_env=None):
+    """-> per rank, what its handle's loop launched (DOTTimeStepper.loopForms)"""
     import torch.multiprocessing as mp
     from tests.workloads import load_workload
     from dot_amd.timestepper import DOTTimeStepper
@@ -99,7 +102,7 @@ def _ranks_reproduce_the_single_gpu_run(workload, steps, shard_elems, world, mat
     ctx = mp.get_context("spawn")
     with tempfile.TemporaryDirectory() as d:
         initfile = os.path.join(d, "init")
-        procs = [ctx.Process(target=_worker, args=(r, world, initfile, d, workload, shard_elems, steps, material))
+        procs = [ctx.Process(target=_worker, args=(r, world, initfile, d, workload, shard_elems, steps, material, rank_env))
                  for r in range(world)]
         for p in procs:
             p.start()
@@ -111,6 +114,7 @@ def _ranks_reproduce_the_single_gpu_run(workload, steps, shard_elems, world, mat
         assert not alive, "a rank hung (ranks branched apart?)"
         assert all(p.exitcode == 0 for p in procs), [p.exitcode for p in procs]
         R = [np.load(os.path.join(d, f"rank{r}.npz")) for r in range(world)]
+    forms = [int(R[r]["forms"]) for r in range(world)]
     # the ranks hold the same replicated state, bit for bit
     for r in range(1, world):
         for k in ("x", "v", "its", "halv", "E", "z"):
@@ -147,7 +151,7 @@ def _ranks_reproduce_the_single_gpu_run(workload, steps, shard_elems, world, mat
         # tolerance reached, iteration count in the same range
         assert all(abs(a - b) <= 0.25 * b for a, b in zip(R[0]["its"].tolist(), its))
         ts.close()
-        return
+        return forms
     assert its == R[0]["its"].tolist() and halv == R[0]["halv"].tolist()
     assert np.abs(ts.getResult() - R[0]["x"]).max() < 1e-9
     r = np.random.default_rng(3).standard_normal(sc.x0.shape) * (1 - sc.fixed[:, None])
@@ -156,6 +160,7 @@ def _ranks_reproduce_the_single_gpu_run(workload, steps, shard_elems, world, mat
     # conditioning of the subdomain matrices
     assert np.abs(z - R[0]["z"]).max() <= 1e-6 * np.abs(z).max()
     ts.close()
+    return forms
 
 
 def _worker_disagree(rank, world, initfile, outdir):
