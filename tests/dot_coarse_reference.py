@@ -58,9 +58,11 @@ class DotStepper:
         self.xn = orc.state()[0].copy()
         self.snapshots = []
 
-    def step(self, precond=None, keep=False):
-        """one time step -> dict(iters, halvings, status, E, g2); precond: r (nV, 3) -> (nV, 3), default the oracle's block
-        preconditioner.  keep: self.snapshots[k] = (x, S, Y) in front of iteration k"""
+    def step(self, precond=None, keep=False, hist=HIST, iter_cap=ITER_CAP):
+        """one time step -> dict(iters, halvings, status, E, g2, no_pair, log); precond: r (nV, 3) -> (nV, 3), default the oracle's
+        block preconditioner.  keep: self.snapshots[k] = (x, S, Y) in front of iteration k.  hist: pairs kept; iter_cap: the step stops
+        after that many iterations (status 2).  no_pair: the iterations, counted from 1, whose accepted trial stored no pair
+        (y . s <= 0); log: per iteration (alpha, E, |g|^2) as arrays"""
         orc = self.orc
         M = orc.apply_precond if precond is None else precond
         x, v, _ = orc.state()
@@ -72,6 +74,7 @@ class DotStepper:
         it = halvings = 0
         failed = False
         self.snapshots = []
+        no_pair, log = [], []
         tol = orc.target_gres
         while True:
             if keep:
@@ -94,24 +97,28 @@ class DotStepper:
             y_new = g_new - g
             g = g_new
             if float(np.vdot(y_new, s_new)) > 0.0:
-                if len(S) == HIST:
+                if len(S) == hist:
                     S.pop(0)
                     Y.pop(0)
                 S.append(s_new)
                 Y.append(y_new)
+            elif not failed:
+                no_pair.append(it + 1)
             if failed:
                 break
             g2 = float(np.vdot(g, g))
             it += 1
-            if it >= ITER_CAP or not g2 > tol:
+            log.append((alpha, E, g2))
+            if it >= iter_cap or not g2 > tol:
                 break
-        status = 2 if (failed or it >= ITER_CAP) else 0
+        status = 2 if (failed or it >= iter_cap) else 0
         if not failed:
             orc.refactor(x)
         v = (x - self.xn) / self.dt
         self.xn = x.copy()
         orc.set_state(x, v, x)
-        return dict(iters=it, halvings=halvings, status=status, E=lastE, g2=g2)
+        return dict(iters=it, halvings=halvings, status=status, E=lastE, g2=g2, no_pair=no_pair,
+                    log=tuple(np.array(c) for c in zip(*log)) if log else (np.zeros(0),) * 3)
 
 
 def m_prime(orc, dup, part_verts, fixed):
