@@ -1,5 +1,6 @@
 // dotmi_loop.hip -- one time step (DOTTimeStepper::fullyImplicit / solve_oneStep, DOTTimeStepper.cpp:273-504; Optimizer::lineSearch, Optimizer.cpp:752-881): dotmi_step, the pieces every loop driver shares, the host-driven L-BFGS-H loop and its GSDD and Newton siblings (the device-resident loop: dotmi_devloop.hip)
 #include "dotmi_handle.hpp"
+#include "loop_verdict.hpp"   // the back-tracking test, the stopped-launch count
 
 namespace dotmi {
 
@@ -244,7 +245,7 @@ static void host_step(dotmi_handle *h, const double *spmv_partials, double alpha
 static int backtrack(dotmi_handle *h, const LbfgsArgs &L, int make_pair, int slot, double lastE, bool marks, double *alpha,
                      double *E, bool *failed)
 {
-    while (*E > lastE && *alpha > 0.0) {
+    while (ls_rejects(*E, lastE, *alpha)) {
         *alpha /= 2.0;
         h->numLineSearch++;
         if (*alpha == 0.0) {
@@ -425,10 +426,10 @@ static void fill_step_stats(dotmi_handle *h, dotmi_step_stats *st, const LoopOut
     st->precond_bytes = h->precond_bytes;
     st->factor_flops = h->factorFlops;
     st->backsolve_launches = h->newtonPcg ? r.applies : r.it;   // (Newton-PCG: one block-solve application per CG iteration)
-    st->backsolve_stopped = (h->devLoop && h->earlyNow) ? halvings + 1 : 0;
-    // (a paired slot whose full step was rejected takes a halving without a stopped launch; one that is redone stops without one)
-    if (h->devLoop && h->pairNow) st->backsolve_stopped += 2 * h->pairRedo - h->pairSlots;
-    if (h->devLoop && h->specNow) st->backsolve_stopped += h->specRedo;   // (a redone slot's back-solve stops without a halving)
+    // (only a step in the early order pairs or speculates: choose_step_forms)
+    st->backsolve_stopped = (h->devLoop && h->earlyNow) ? loop_stopped_launches(halvings, h->pairNow ? h->pairSlots : 0,
+                                                                                h->pairNow ? h->pairRedo : 0, h->specNow ? h->specRedo : 0)
+                                                        : 0;
     st->spec_slots = (h->devLoop && h->specNow) ? h->specSlots : 0;
     st->spec_redone = (h->devLoop && h->specNow) ? h->specRedo : 0;
     st->backsolve_held = (h->devLoop && h->earlyNow) ? h->heldSlots : 0;

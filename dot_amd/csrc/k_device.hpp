@@ -36,6 +36,7 @@
 //   dense_fill_kernel         DOTTimeStepper.cpp:619-797 (== principal sub-matrix of the global H)
 #pragma once
 #include "dotmi_internal.hpp"
+#include "loop_verdict.hpp"   // the line search's policy: alpha_0 (the step and element kernels), the controller's decision (k_loopctl.hpp)
 #include <hip/hip_ext.h>
 #include "elem_math.hpp"
 

@@ -179,7 +179,7 @@ __device__ __forceinline__ void elem_patch_body(const DevPatches &PT, const doub
                 }
                 pg = __shfl(wave_sum(pg), 0, 64);
                 pHp = __shfl(wave_sum(pHp), 0, 64);
-                a = fmax(alphaMin, fmin(1.0, -pg / pHp));  // Optimizer.cpp:1085
+                a = ls_first_step(pg, pHp, alphaMin);
             }
             if (threadIdx.x == 0) {
                 if constexpr (PAIR) {

@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256) void elem_vertex_kernel(DevVPatches VP, ElemVe
             }
             pg = __shfl(wave_sum(pg), 0, 64);
             pHp = __shfl(wave_sum(pHp), 0, 64);
-            al = fmax(alphaMin, fmin(1.0, -pg / pHp));  // Optimizer.cpp:1085
+            al = ls_first_step(pg, pHp, alphaMin);
         }
         if (tid == 0) {
             if constexpr (PAIR) {

@@ -1175,7 +1175,7 @@ __global__ __launch_bounds__(256) void step_forward_kernel(int n, const double *
             }
             pg = __shfl(wave_sum(pg), 0, 64);
             pHp = __shfl(wave_sum(pHp), 0, 64);
-            alpha = fmax(alpha_min, fmin(1.0, -pg / pHp));  // Optimizer.cpp:1085
+            alpha = ls_first_step(pg, pHp, alpha_min);
         }
         if (threadIdx.x == 0) {
             sh_alpha = alpha;
