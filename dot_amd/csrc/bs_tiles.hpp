@@ -41,11 +41,8 @@ struct BsTilePlan {
 
 inline int bs_tile_len(const int4 &t) { return t.y + (t.z >> 16) - t.w; }
 // A tile beyond BS_LONG columns goes to the two-phase kernel in column chunks of BS_LONG_CHUNK: the width backsolve_long_kernel gives
-// its workgroups (BSL_CW, k_backsolve.hip: 512 threads x 4 x 2), NOT the register tile BS_LONG of the single-pass kernel.  The two
-// were one number until the register tile grew from 4096 to 5120 columns; counted in units of 5120, a tile of more than 8192 columns
-// got a work item too few, its last columns were never visited and the kernel's second phase summed chunk partials nobody had
-// written (the whole mesh as one subdomain: bunny5K, 14 976 columns, |H M r - r| / |r| = 2)
-constexpr int BS_LONG_CHUNK = 4096;
+// its workgroups, NOT the register tile BS_LONG of the single-pass kernel (bs_forms.hpp: the one statement of both, and what happened
+// when they were one number)
 inline int bs_long_chunks(int len) { return (((len + 15) & ~15) + BS_LONG_CHUNK - 1) / BS_LONG_CHUNK; }
 
 // usedRows(nd, ls) = live scalar rows of tree node nd (its leaf block / separator) in owned subdomain ls

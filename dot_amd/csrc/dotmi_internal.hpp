@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "bs_forms.hpp"        // the capacities of the back-solve's form families
 #include "lbfgs_history.hpp"   // HIST_MAX
 #include "merge_sum.hpp"       // MT_PAD
 #include "nd_layout.hpp"
@@ -33,10 +34,12 @@ inline int elem_wg_cap(int mat) { return mat == 1 ? 768 : 512; }
 }
 constexpr int NB_RED = 256;     // blocks of every reducing kernel (fixed => run-to-run bit-identical sums)
 constexpr int RED_K = 3 * HIST_MAX + 3;  // partial values per block
-constexpr int BS_WAVE = 256;    // rows of at most that many columns: four tiles per workgroup, one wavefront each
-constexpr int BS_NARROW = 3072; // longest row the 256-thread form of that kernel takes (two workgroups per CU; round 5: 2560 -> 3072 with the
-                                // right-hand side of the sixth chunk's rows in LDS); longer rows go to the 512-thread form in a launch of their own
-constexpr int BS_LONG = 5120;   // longest row (columns) the single-pass back-solve kernel holds in registers (512 threads x 5 x 2)
+// the longest row each family of back-solve forms takes (bs_forms.hpp: the last entry of its table)
+constexpr int BS_WAVE = bs_family_capacity(BSF_PACK);   // 256: rows of at most that many columns: four tiles per workgroup, one wavefront each
+constexpr int BS_NARROW = bs_family_capacity(BSF_NARROW);   // 3072: longest row the 256-thread form of that kernel takes (two workgroups per
+                                // CU; round 5: 2560 -> 3072 with the right-hand side of the sixth chunk's rows in LDS); longer rows go to the
+                                // 512-thread form in a launch of their own
+constexpr int BS_LONG = bs_family_capacity(BSF_WIDE);   // 5120: longest row (columns) the single-pass back-solve kernel holds in registers
 constexpr int ELEM_NB_MAX = 8192; // most workgroups (= partial energy rows) of the element pass; beyond, workgroups loop over patches
 constexpr int CHOL_NB = 64;     // tile of the inverse-Cholesky factorisation (LDS resident)
 

@@ -138,6 +138,26 @@ int dotmi_plan_loop_forms(int64_t ndof_gather, int64_t ndof_merge, int64_t nrows
     return 0;
 }
 
+// host-only: the back-solve's form tables (bs_forms.hpp: what k_backsolve.hip instantiates and dispatches on), family after family
+int dotmi_plan_backsolve_forms(int32_t cap, int32_t *forms, int32_t *counts)
+{
+    if (!counts || cap < 0 || (cap > 0 && !forms)) return DOTMI_E_INVALID;
+    int n = 0;
+    for (int fam : {BSF_PACK, BSF_NARROW, BSF_WIDE})
+        for (int i = 0; i < bs_form_count(fam); ++i, ++n) {
+            if (!forms) continue;
+            if (n >= cap) return DOTMI_E_INVALID;
+            const BsForm f = bs_form(fam, i);
+            const int32_t row[6] = {fam, BSF_LANES[fam], f.chunks, f.sub, f.rlds, bs_form_capacity(fam, i)};
+            // (the table's own map puts a row of that length on this form, and one column more on the next)
+            if (bs_form_index(fam, row[5]) != i || bs_form_index(fam, row[5] + 1) != i + 1) return DOTMI_E_INVALID;
+            std::copy(row, row + 6, forms + 6 * (size_t)n);
+        }
+    const int32_t c[4] = {n, BSL_THREADS, BSL_SUB, BS_LONG_CHUNK};
+    std::copy(c, c + 4, counts);
+    return 0;
+}
+
 // host-only: the element patches of patches.hpp for all elements of a mesh.  First call with elem == NULL for the sizes
 // (n_patches, pv, n_slots), then with arrays of nPatches*PE (elem), 4*nPatches*PE (tl, epos: uint16), nPatches*PV (pv_gid,
 // pv_slot), nPatches (pv_cnt), nPatches*(PV+1) (c_ptr: uint16) and 2*nV (pp_rng).  tests/test_patches.py checks the

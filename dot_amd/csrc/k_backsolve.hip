@@ -2,6 +2,7 @@
 // a launch of its own, or workgroup 0 of the back-solve launch
 // (one translation unit per kernel family since round 6: an edit to one family no longer moves the register allocation and
 // scalar loads of the others; every unit is compiled once.  Conventions and the reference map: k_device.hpp)
+#include "bs_forms.hpp"
 #include "k_device.hpp"
 #include "k_loopctl.hpp"
 #include "loop_forms.hpp"
@@ -55,6 +56,91 @@ __global__ __launch_bounds__(256) void gather_pad_kernel(int total, const int *_
 constexpr int BS_ROWS = 64;   // memory rows per workgroup
 typedef double nt_double2 __attribute__((ext_vector_type(2)));
 
+// ---- the tile walk, stated once for the three tile bodies (workgroup tile, wavefront tile, two-phase kernel) -----------------
+// The geometry of a tile, from its job record (bs_tiles.hpp: part, first row, tile index in the part | rows << 16, first column)
+struct BsTile {
+    int s, i0, tileIdx, cb;
+    int ns;      // one past the last live row of this tile
+    int ncol;    // columns cb <= k < ns can be non-zero in these rows (nested dissection: everything left of the tile's node is
+                 // structurally zero); whole 128-byte lines are loaded
+    // the tile's rows lie in ONE 64-row block of the factor storage (dotmi_internal.hpp RowTile): row i, column c is at
+    // W[rt.off + (i - first row of the block) * rt.ld + (c - rt.c0)] = Ws[i * ldw + c]
+    int ldw;
+    const double *Ws, *rp;   // rp: the right-hand side in padded order (zeros on the padding)
+    const int *dm;
+    double *ppart;
+    int nmax, nbmax;
+    __device__ __forceinline__ double *out() const { return ppart + ((size_t)s * nbmax + tileIdx) * nmax; }   // the tile's partial result
+};
+__device__ __forceinline__ BsTile bs_tile(const int4 jb, int nmax, const RowTile *rt, const double *W, const int *dofmap, const double *q,
+                                          double *ppart, int nbmax)
+{
+    BsTile g;
+    g.s = jb.x, g.i0 = jb.y, g.tileIdx = jb.z & 0xffff, g.cb = jb.w;
+    g.ns = g.i0 + (jb.z >> 16);
+    g.ncol = min((g.ns + 15) & ~15, nmax);
+    const RowTile rb = rt[(size_t)g.s * (nmax >> 6) + (g.i0 >> 6)];
+    g.ldw = rb.ld;
+    g.Ws = W + (rb.off - (long long)(g.i0 & ~63) * g.ldw - rb.c0);
+    g.dm = dofmap + (size_t)g.s * nmax;
+    g.rp = q + (size_t)g.s * nmax;
+    g.ppart = ppart, g.nmax = nmax, g.nbmax = nbmax;
+    return g;
+}
+// The first column a lane's pair at column c is NOT loaded for: c itself, or never when both columns are identity padding -- padding
+// columns of live rows hold zeros (separator rows span the padding of every region): not read.  rhs: also the right-hand side pair.
+// (PAIR: the dofmap pair with one 8-byte load; the two-phase kernel keeps its two 4-byte loads)
+template <bool PAIR = true>
+__device__ __forceinline__ int bs_pair_end(const BsTile &g, int c, double2 *rhs)
+{
+    int d0, d1;
+    if constexpr (PAIR) {
+        const int2 dd = (c < g.ncol) ? *reinterpret_cast<const int2 *>(g.dm + c) : make_int2(-1, -1);
+        d0 = dd.x, d1 = dd.y;
+    } else {
+        d0 = (c < g.ncol) ? g.dm[c] : -1, d1 = (c < g.ncol) ? g.dm[c + 1] : -1;
+    }
+    if (rhs) *rhs = (c < g.ncol) ? *reinterpret_cast<const double2 *>(g.rp + c) : make_double2(0.0, 0.0);
+    return (d0 >= 0 || d1 >= 0) ? c : 0x7fffffff;
+}
+// the first column of pair m of lane `lane` of LANES, from column c0 on
+template <int LANES>
+__device__ __forceinline__ int bs_col(int c0, int lane, int m) { return c0 + 2 * lane + 2 * LANES * m; }
+// SUB rows from row ib on into the registers y[SUB][CH] of the enclosing tile body (its g, ib, cend): the lane's CH pairs, zeros past the
+// tile's last row.  A row is zero right of its diagonal: loads stop at the end of its own 128-byte line, not of the tile.
+// NT: streamed once per launch by exactly one workgroup: non-temporal, so the 229 MB of factors do not push the small hot arrays of
+// the other loop kernels out of the 256 MB Infinity Cache (the two-phase kernel reads its rows twice: plain loads).
+// (A macro: from an inlined function the same loads came out with other address arithmetic -- the 256-thread kernels at 256 VGPRs
+// instead of 254 with one spilled, the 512-thread kernel with 18 spilled instead of 1.)
+#define BS_LOAD_ROWS(SUB_, CH_, LANES_, NT_, c0_, lane_)                                                                     \
+    _Pragma("unroll") for (int rr = 0; rr < SUB_; ++rr)                                                                      \
+    {                                                                                                                        \
+        const double *row = g.Ws + (long long)min(ib + rr, g.ns - 1) * g.ldw;                                                \
+        const int rend = ((ib + rr) < g.ns) ? min(g.ncol, (ib + rr + 16) & ~15) : 0;                                         \
+        _Pragma("unroll") for (int m = 0; m < CH_; ++m)                                                                      \
+        {                                                                                                                    \
+            const int c = bs_col<LANES_>(c0_, lane_, m);                                                                     \
+            if (cend[m] >= rend) {                                                                                           \
+                y[rr][m] = make_double2(0.0, 0.0);                                                                           \
+            } else if constexpr (NT_) {                                                                                      \
+                const nt_double2 v = __builtin_nontemporal_load(reinterpret_cast<const nt_double2 *>(row + c));              \
+                y[rr][m] = make_double2(v.x, v.y);                                                                           \
+            } else {                                                                                                         \
+                y[rr][m] = *reinterpret_cast<const double2 *>(row + c);                                                      \
+            }                                                                                                                \
+        }                                                                                                                    \
+    }
+template <int CH, int LANES>
+__device__ __forceinline__ void bs_store(const BsTile &g, int c0, int lane, const double2 (&pacc)[CH])
+{
+    double *out = g.out();
+#pragma unroll
+    for (int m = 0; m < CH; ++m) {
+        const int c = bs_col<LANES>(c0, lane, m);
+        if (c < g.ncol) *reinterpret_cast<double2 *>(out + c) = pacc[m];
+    }
+}
+
 // One tile with rows of at most 2*THREADS*MAXCH columns, SUB rows in registers at a time.  Short rows
 // (the leaves of the dissection) take many rows per pass, long rows few, so that every pass has about
 // the same number of bytes in flight: the pass count of a tile -- a chain of HBM latency, butterfly
@@ -62,36 +148,23 @@ typedef double nt_double2 __attribute__((ext_vector_type(2)));
 // RLDS (round 5, rows of 2561 .. 3072 columns on the 256-thread kernel): the thread's right-hand side entries live in LDS
 // (rs: each thread reads back only what it wrote -- a manual spill of 24 registers) so that six chunks of rows fit the
 // register tile at two workgroups per CU; the dot products keep their order of additions (chunk after chunk).
-template <int THREADS, int MAXCH, int SUB, bool RLDS = false>
-__device__ __forceinline__ void backsolve_tile(const int4 jb, const int *__restrict__ dofmap,
-                                               const double *__restrict__ W, int nmax, const RowTile *__restrict__ rt,
-                                               const double *__restrict__ q, double *__restrict__ ppart,
-                                               int nbmax, double (*sm)[THREADS / 64][32],
-                                               const int *__restrict__ abortp = nullptr, int epoch = 0,
-                                               int *s_abort = nullptr, double2 *__restrict__ rs = nullptr)
+// (The dot products are one statement for both storage kinds, chunk after chunk into each of eight sums.  The update is not: in the
+// RLDS branch's order -- all row sums first -- the 512-thread kernel goes from 1 spilled VGPR to 13, so its two branches stay.)
+template <int THREADS, int MAXCH, int SUB, bool RLDS>
+__device__ __forceinline__ void backsolve_tile(const int4 jb, const int *__restrict__ dofmap, const double *__restrict__ W, int nmax,
+                                               const RowTile *__restrict__ rt, const double *__restrict__ q, double *__restrict__ ppart,
+                                               int nbmax, double (*sm)[THREADS / 64][32], const int *__restrict__ abortp, int epoch,
+                                               int *s_abort, double2 *__restrict__ rs)
 {
     constexpr int NW = THREADS / 64;
-    const int s = jb.x, i0 = jb.y, tileIdx = jb.z & 0xffff, cb = jb.w;
-    const int ns = i0 + (jb.z >> 16);          // one past the last live row of this tile
-    // columns cb <= k < ns can be non-zero in these rows (nested dissection: everything left of the
-    // tile's node is structurally zero); whole 128-byte lines are loaded
-    const int ncol = min((ns + 15) & ~15, nmax);
+    const BsTile g = bs_tile(jb, nmax, rt, W, dofmap, q, ppart, nbmax);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    // the tile's rows lie in ONE 64-row block of the factor storage (dotmi_internal.hpp RowTile): row i, column c is at
-    // W[rt.off + (i - first row of the block) * rt.ld + (c - rt.c0)]
-    const RowTile rb = rt[(size_t)s * (nmax >> 6) + (i0 >> 6)];
-    const int ldw = rb.ld;
-    const double *Ws = W + (rb.off - (long long)(i0 & ~63) * ldw - rb.c0);
-    const int *dm = dofmap + (size_t)s * nmax;
-    const double *rp = q + (size_t)s * nmax;   // right-hand side in padded order (zeros on the padding)
-    double2 r[RLDS ? 1 : MAXCH], pacc[RLDS ? 1 : MAXCH];   // (RLDS: both in LDS, rs[.] and rs[THREADS * MAXCH + .])
+    double2 r[RLDS ? 1 : MAXCH], pacc[MAXCH];   // (RLDS: both in LDS, rs[.] and rs[THREADS * MAXCH + .])
     int cend[MAXCH];  // first column this thread's pair of chunk m is NOT loaded for: 0 for identity-padding columns
 #pragma unroll
     for (int m = 0; m < MAXCH; ++m) {
-        const int c = cb + 2 * tid + 2 * THREADS * m;
-        const int2 dd = (c < ncol) ? *reinterpret_cast<const int2 *>(dm + c) : make_int2(-1, -1);
-        const int d0 = dd.x, d1 = dd.y;
-        const double2 rv = (c < ncol) ? *reinterpret_cast<const double2 *>(rp + c) : make_double2(0.0, 0.0);
+        double2 rv;
+        cend[m] = bs_pair_end(g, bs_col<THREADS>(g.cb, tid, m), &rv);
         if constexpr (RLDS) {
             rs[tid + THREADS * m] = rv;
             rs[THREADS * MAXCH + tid + THREADS * m] = make_double2(0.0, 0.0);
@@ -99,13 +172,11 @@ __device__ __forceinline__ void backsolve_tile(const int4 jb, const int *__restr
             r[m] = rv;
             pacc[m] = make_double2(0.0, 0.0);
         }
-        // padding columns of live rows hold zeros (separator rows span the padding of every region): not read
-        cend[m] = (d0 >= 0 || d1 >= 0) ? c : 0x7fffffff;
     }
 #pragma unroll 1
     for (int sb = 0; sb < BS_ROWS / SUB; ++sb) {
-        const int ib = i0 + sb * SUB;
-        if (ib >= ns) break;
+        const int ib = g.i0 + sb * SUB;
+        if (ib >= g.ns) break;
         // speculative launch: has the controller (workgroup 0 of the launch) rejected the trial meanwhile?  One thread asks,
         // the answer is shared through LDS behind this pass' barrier (double-buffered like sm), so the whole workgroup
         // leaves together
@@ -114,74 +185,23 @@ __device__ __forceinline__ void backsolve_tile(const int4 jb, const int *__restr
         int abortSeen = 0;
         if (abortp && tid == 0) abortSeen = __hip_atomic_load(abortp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         double2 y[SUB][MAXCH];
-#pragma unroll
-        for (int rr = 0; rr < SUB; ++rr) {
-            const double *row = Ws + (long long)min(ib + rr, ns - 1) * ldw;
-            // a row is zero right of its diagonal: stop at the end of its own 128-byte line, not of the tile
-            const int rend = ((ib + rr) < ns) ? min(ncol, (ib + rr + 16) & ~15) : 0;
-#pragma unroll
-            for (int m = 0; m < MAXCH; ++m) {
-                const int c = cb + 2 * tid + 2 * THREADS * m;
-                if (cend[m] < rend) {
-                    // streamed once per launch by exactly one workgroup: non-temporal, so the 229 MB of factors do not
-                    // push the small hot arrays of the other loop kernels out of the 256 MB Infinity Cache
-                    const nt_double2 v = __builtin_nontemporal_load(reinterpret_cast<const nt_double2 *>(row + c));
-                    y[rr][m] = make_double2(v.x, v.y);
-                } else {
-                    y[rr][m] = make_double2(0.0, 0.0);
-                }
-            }
-        }
+        BS_LOAD_ROWS(SUB, MAXCH, THREADS, true, g.cb, tid);
         const int buf = sb & 1;
 #pragma unroll
-        for (int g = 0; g < SUB / 8; ++g) {
+        for (int gr = 0; gr < SUB / 8; ++gr) {
             double d[8];
-            if constexpr (RLDS) {
 #pragma unroll
-                for (int rr = 0; rr < 8; ++rr) d[rr] = 0.0;
+            for (int rr = 0; rr < 8; ++rr) d[rr] = 0.0;
 #pragma unroll
-                for (int m = 0; m < MAXCH; ++m) {
-                    const double2 rv = rs[tid + THREADS * m];
+            for (int m = 0; m < MAXCH; ++m) {
+                const double2 rv = RLDS ? rs[tid + THREADS * m] : r[m];
 #pragma unroll
-                    for (int rr = 0; rr < 8; ++rr) d[rr] += y[8 * g + rr][m].x * rv.x + y[8 * g + rr][m].y * rv.y;
-                }
-            } else {
-#pragma unroll
-            for (int rr = 0; rr < 8; ++rr) {
-                double acc = 0.0;
-#pragma unroll
-                for (int m = 0; m < MAXCH; ++m) acc += y[8 * g + rr][m].x * r[m].x + y[8 * g + rr][m].y * r[m].y;
-                d[rr] = acc;
-            }
+                for (int rr = 0; rr < 8; ++rr) d[rr] += y[8 * gr + rr][m].x * rv.x + y[8 * gr + rr][m].y * rv.y;
             }
             // transposed butterfly: 8 values over 64 lanes -> lane group lane>>3 holds one row's wave sum
-            double e4[4], e2[2], e1;
-            {
-                const bool hi = lane & 32;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const double keep = hi ? d[k + 4] : d[k], send = hi ? d[k] : d[k + 4];
-                    e4[k] = keep + __shfl_xor(send, 32, 64);
-                }
-            }
-            {
-                const bool hi = lane & 16;
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    const double keep = hi ? e4[k + 2] : e4[k], send = hi ? e4[k] : e4[k + 2];
-                    e2[k] = keep + __shfl_xor(send, 16, 64);
-                }
-            }
-            {
-                const bool hi = lane & 8;
-                const double keep = hi ? e2[1] : e2[0], send = hi ? e2[0] : e2[1];
-                e1 = keep + __shfl_xor(send, 8, 64);
-            }
-            e1 += __shfl_xor(e1, 4, 64);
-            e1 += __shfl_xor(e1, 2, 64);
-            e1 += __shfl_xor(e1, 1, 64);
+            const double e1 = wave_sum8_transposed(d, tid);
             // lane bits (5,4,3) = (b2,b1,b0): row index = 4*b2 + 2*b1 + b0
-            if ((lane & 7) == 0) sm[buf][wv][8 * g + (lane >> 3)] = e1;
+            if ((lane & 7) == 0) sm[buf][wv][8 * gr + (lane >> 3)] = e1;
         }
         if (abortp && tid == 0) s_abort[sb & 1] = abortSeen;
         __syncthreads();
@@ -220,21 +240,40 @@ __device__ __forceinline__ void backsolve_tile(const int4 jb, const int *__restr
         }
         }
     }
-    double *out = ppart + ((size_t)s * nbmax + tileIdx) * nmax;
+    if constexpr (RLDS) {
 #pragma unroll
-    for (int m = 0; m < MAXCH; ++m) {
-        const int c = cb + 2 * tid + 2 * THREADS * m;
-        if (c < ncol) {
-            if constexpr (RLDS) *reinterpret_cast<double2 *>(out + c) = rs[THREADS * MAXCH + tid + THREADS * m];
-            else *reinterpret_cast<double2 *>(out + c) = pacc[m];
-        }
+        for (int m = 0; m < MAXCH; ++m) pacc[m] = rs[THREADS * MAXCH + tid + THREADS * m];
     }
+    bs_store<MAXCH, THREADS>(g, g.cb, tid, pacc);
 }
 
-
+// -DBS_PROFILE (tools/prof_backsolve.sh): per job of the launch its start, end, longest row, rows (negative: a pack; the rows of its
+// first tile) and the hardware and XCC id (of a pack: wavefront 0's)
 #ifdef BS_PROFILE
 __device__ long long g_bs_prof[8192][5];
+extern "C" int dotmi_debug_bs_prof(long long *out, int n) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bs_prof), sizeof(long long) * 5 * (size_t)n); }
 #endif
+__device__ __forceinline__ void bs_prof_begin(int jobIdx, const int4 jb, bool pack)
+{
+#ifdef BS_PROFILE
+    if (threadIdx.x == 0 && jobIdx < 8192) {
+        unsigned hw, xcc;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        g_bs_prof[jobIdx][0] = wall_clock64();
+        g_bs_prof[jobIdx][2] = jb.y + (jb.z >> 16) - jb.w;
+        g_bs_prof[jobIdx][3] = pack ? -(jb.z >> 16) : jb.z >> 16;
+        g_bs_prof[jobIdx][4] = (long long)hw | ((long long)(xcc & 15) << 32);
+    }
+#endif
+}
+__device__ __forceinline__ void bs_prof_end(int jobIdx, bool pack)   // (a pack: wavefront 0 of the four)
+{
+#ifdef BS_PROFILE
+    if (!pack) __syncthreads();
+    if (threadIdx.x == 0 && jobIdx < 8192) g_bs_prof[jobIdx][1] = wall_clock64();
+#endif
+}
 
 // ---- small tiles, one WAVEFRONT each (round 5) -----------------------------------------------------------------------------
 // On a deep dissection most tiles are small: bar17K on three levels has 1163 tiles of which 796 have rows of at most 256
@@ -265,57 +304,32 @@ __device__ __forceinline__ void backsolve_wave_tile_t(const int4 jb, const int *
                                                       double *__restrict__ ppart, int nbmax, const int *__restrict__ abortp,
                                                       int epoch)
 {
-    const int rows = jb.z >> 16;
-    const int s = jb.x, i0 = jb.y, tileIdx = jb.z & 0xffff, cb = jb.w;
-    const int ns = i0 + rows;
-    const int ncol = min((ns + 15) & ~15, nmax);
+    const BsTile g = bs_tile(jb, nmax, rt, W, dofmap, q, ppart, nbmax);
     const int lane = threadIdx.x & 63;
-    const RowTile rb = rt[(size_t)s * (nmax >> 6) + (i0 >> 6)];
-    const int ldw = rb.ld;
-    const double *Ws = W + (rb.off - (long long)(i0 & ~63) * ldw - rb.c0);
-    const int *dm = dofmap + (size_t)s * nmax;
-    const double *rp = q + (size_t)s * nmax;
     double2 r[WCH], pacc[WCH];
     int cend[WCH];
 #pragma unroll
     for (int m = 0; m < WCH; ++m) {
-        const int c = cb + 2 * lane + 128 * m;
-        const int2 dd = (c < ncol) ? *reinterpret_cast<const int2 *>(dm + c) : make_int2(-1, -1);
-        r[m] = (c < ncol) ? *reinterpret_cast<const double2 *>(rp + c) : make_double2(0.0, 0.0);
+        cend[m] = bs_pair_end(g, bs_col<64>(g.cb, lane, m), &r[m]);
         pacc[m] = make_double2(0.0, 0.0);
-        cend[m] = (dd.x >= 0 || dd.y >= 0) ? c : 0x7fffffff;
     }
 #pragma unroll 1
-    for (int ib = i0; ib < ns; ib += WSUB) {
+    for (int ib = g.i0; ib < g.ns; ib += WSUB) {
         int ab = 0;
         if (abortp) ab = __hip_atomic_load(abortp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (answer used behind the loads)
         double2 y[WSUB][WCH];
-#pragma unroll
-        for (int rr = 0; rr < WSUB; ++rr) {
-            const double *row = Ws + (long long)min(ib + rr, ns - 1) * ldw;
-            const int rend = ((ib + rr) < ns) ? min(ncol, (ib + rr + 16) & ~15) : 0;
-#pragma unroll
-            for (int m = 0; m < WCH; ++m) {
-                const int c = cb + 2 * lane + 128 * m;
-                if (cend[m] < rend) {
-                    const nt_double2 v = __builtin_nontemporal_load(reinterpret_cast<const nt_double2 *>(row + c));
-                    y[rr][m] = make_double2(v.x, v.y);
-                } else {
-                    y[rr][m] = make_double2(0.0, 0.0);
-                }
-            }
-        }
+        BS_LOAD_ROWS(WSUB, WCH, 64, true, g.cb, lane);
         if (abortp && __builtin_amdgcn_readfirstlane(ab) == epoch) return;   // the result would not be used
         // eight rows at a time: their dot products, the wave sums, and at once their rank-8 update (rows ascending into every
         // accumulator, as in the block form) -- only eight row sums are alive
 #pragma unroll
-        for (int g = 0; g < WSUB / 8; ++g) {
+        for (int gr = 0; gr < WSUB / 8; ++gr) {
             double d[8];
 #pragma unroll
             for (int rr = 0; rr < 8; ++rr) {
                 double acc = 0.0;
 #pragma unroll
-                for (int m = 0; m < WCH; ++m) acc += y[8 * g + rr][m].x * r[m].x + y[8 * g + rr][m].y * r[m].y;
+                for (int m = 0; m < WCH; ++m) acc += y[8 * gr + rr][m].x * r[m].x + y[8 * gr + rr][m].y * r[m].y;
                 d[rr] = acc;
             }
             const double e1 = wave_sum8_transposed(d, lane);   // lane 8 k holds the wave sum of row k of the group
@@ -324,42 +338,47 @@ __device__ __forceinline__ void backsolve_wave_tile_t(const int4 jb, const int *
                 const double t = bs_readlane(e1, 8 * rr);
 #pragma unroll
                 for (int m = 0; m < WCH; ++m) {
-                    pacc[m].x += t * y[8 * g + rr][m].x;
-                    pacc[m].y += t * y[8 * g + rr][m].y;
+                    pacc[m].x += t * y[8 * gr + rr][m].x;
+                    pacc[m].y += t * y[8 * gr + rr][m].y;
                 }
             }
         }
     }
-    double *out = ppart + ((size_t)s * nbmax + tileIdx) * nmax;
-#pragma unroll
-    for (int m = 0; m < WCH; ++m) {
-        const int c = cb + 2 * lane + 128 * m;
-        if (c < ncol) *reinterpret_cast<double2 *>(out + c) = pacc[m];
-    }
+    bs_store<WCH, 64>(g, g.cb, lane, pacc);
 }
-__device__ __forceinline__ void backsolve_wave_tile(const int4 jb, const int *__restrict__ dofmap, const double *__restrict__ W,
-                                                    int nmax, const RowTile *__restrict__ rt, const double *__restrict__ q,
-                                                    double *__restrict__ ppart, int nbmax, const int *__restrict__ abortp,
-                                                    int epoch)
+
+// job jobIdx >= nBig of the 256-thread launch is a pack of four small tiles: the calling wavefront's
+__device__ __forceinline__ int4 bs_pack_job(const int4 *__restrict__ job, int nBig, int jobIdx) { return job[nBig + 4 * (jobIdx - nBig) + (threadIdx.x >> 6)]; }
+// that tile in the pack family's form
+__device__ __forceinline__ void backsolve_pack(int jobIdx, const int4 jb, const int *__restrict__ dofmap,
+                                               const double *__restrict__ W, int nmax, const RowTile *__restrict__ rt,
+                                               const double *__restrict__ q, double *__restrict__ ppart, int nbmax,
+                                               const int *__restrict__ abortp, int epoch)
 {
     const int rows = jb.z >> 16;
     if (rows == 0) return;              // padding of the last pack
     if (abortp && __builtin_amdgcn_readfirstlane(__hip_atomic_load(abortp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == epoch)
         return;
+    bs_prof_begin(jobIdx, jb, true);
     // (wave-uniform: a tile is one wavefront's)
-    if (jb.y + rows - jb.w <= 128) backsolve_wave_tile_t<1, 32>(jb, dofmap, W, nmax, rt, q, ppart, nbmax, abortp, epoch);
-    else backsolve_wave_tile_t<2, 16>(jb, dofmap, W, nmax, rt, q, ppart, nbmax, abortp, epoch);
+    bs_select_form<BSF_PACK>(jb.y + rows - jb.w, [&](auto I) __attribute__((always_inline)) {
+        constexpr BsForm F = bs_form(BSF_PACK, I);
+        backsolve_wave_tile_t<F.chunks, F.sub>(jb, dofmap, W, nmax, rt, q, ppart, nbmax, abortp, epoch);
+    });
+    bs_prof_end(jobIdx, true);
 }
 
-
-// the tile of job[jobIdx] by the calling workgroup
+// the tile of job[jobIdx] by the calling workgroup: the form of the workgroup's family (256 threads: narrow, 512: wide) that holds
+// its longest row
 template <int THREADS>
 __device__ __forceinline__ void backsolve_block(int jobIdx, const int4 *__restrict__ job, const int *__restrict__ dofmap,
                                                 const double *__restrict__ W, int nmax, const RowTile *__restrict__ rt,
                                                 const double *__restrict__ q, double *__restrict__ ppart, int nbmax,
-                                                double (*sm)[THREADS / 64][32], const int *__restrict__ abortp = nullptr,
-                                                int epoch = 0, int *s_abort = nullptr, double2 *__restrict__ rs = nullptr)
+                                                double (*sm)[THREADS / 64][32], const int *__restrict__ abortp, int epoch,
+                                                int *s_abort, double2 *__restrict__ rs)
 {
+    constexpr int FAM = THREADS == BSF_LANES[BSF_NARROW] ? BSF_NARROW : BSF_WIDE;
+    static_assert(THREADS == BSF_LANES[FAM], "a workgroup is one of the two block families");
     if (abortp) {   // workgroups that start after the verdict leave at once (one thread asks: a uniform answer)
         if (threadIdx.x == 0) s_abort[2] = __hip_atomic_load(abortp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __syncthreads();
@@ -367,71 +386,38 @@ __device__ __forceinline__ void backsolve_block(int jobIdx, const int4 *__restri
     }
     const int4 jb = job[jobIdx];
     const int len = jb.y + (jb.z >> 16) - jb.w;   // longest row of the tile
-#ifdef BS_PROFILE
-    if (threadIdx.x == 0 && jobIdx < 8192) {
-        unsigned hw;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        g_bs_prof[jobIdx][0] = wall_clock64();
-        g_bs_prof[jobIdx][2] = len;
-        g_bs_prof[jobIdx][3] = jb.z >> 16;
-        g_bs_prof[jobIdx][4] = (long long)hw | ((long long)(xcc & 15) << 32);
-    }
-#endif
-    if constexpr (THREADS == 256) {
-        if (len <= 512) backsolve_tile<256, 1, 32>(jb, dofmap, W, nmax, rt, q, ppart, nbmax, sm, abortp, epoch, s_abort);
-        else if (len <= 1024) backsolve_tile<256, 2, 16>(jb, dofmap, W, nmax, rt, q, ppart, nbmax, sm, abortp, epoch, s_abort);
-        else if (len <= 1536) backsolve_tile<256, 3, 8>(jb, dofmap, W, nmax, rt, q, ppart, nbmax, sm, abortp, epoch, s_abort);
-        else if (len <= 2560) backsolve_tile<256, 5, 8>(jb, dofmap, W, nmax, rt, q, ppart, nbmax, sm, abortp, epoch, s_abort);
-        else backsolve_tile<256, 6, 8, true>(jb, dofmap, W, nmax, rt, q, ppart, nbmax, sm, abortp, epoch, s_abort, rs);   // <= BS_NARROW
-    } else {
-        if (len <= 1024) backsolve_tile<512, 1, 32>(jb, dofmap, W, nmax, rt, q, ppart, nbmax, sm, abortp, epoch, s_abort);
-        else if (len <= 2048) backsolve_tile<512, 2, 16>(jb, dofmap, W, nmax, rt, q, ppart, nbmax, sm, abortp, epoch, s_abort);
-        else if (len <= 4096) backsolve_tile<512, 4, 8>(jb, dofmap, W, nmax, rt, q, ppart, nbmax, sm, abortp, epoch, s_abort);
-        else backsolve_tile<512, 5, 8>(jb, dofmap, W, nmax, rt, q, ppart, nbmax, sm, abortp, epoch, s_abort);   // <= BS_LONG = 5120
-    }
-#ifdef BS_PROFILE
-    __syncthreads();
-    if (threadIdx.x == 0 && jobIdx < 8192) g_bs_prof[jobIdx][1] = wall_clock64();
-#endif
+    bs_prof_begin(jobIdx, jb, false);
+    bs_select_form<FAM>(len, [&](auto I) __attribute__((always_inline)) {
+        constexpr BsForm F = bs_form(FAM, I);
+        backsolve_tile<THREADS, F.chunks, F.sub, F.rlds>(jb, dofmap, W, nmax, rt, q, ppart, nbmax, sm, abortp, epoch, s_abort, rs);
+    });
+    bs_prof_end(jobIdx, false);
+}
+// LDS slots of a workgroup family's RLDS forms: a right-hand side pair and an accumulator pair per lane and chunk of the longest such
+// form, which is as many as it has columns (1: the family has none)
+constexpr int bs_rlds_slots(int fam, int i = 0)
+{
+    return i == bs_form_count(fam) ? 1 : std::max(bs_form(fam, i).rlds ? bs_form_capacity(fam, i) : 1, bs_rlds_slots(fam, i + 1));
 }
 
 // spec: the launch is speculative (early back-solve, enqueue_loop_slot): it runs on the trial gradient before the
 // controller has decided about the trial, so the retry phase does not gate it
 template <int THREADS>
-__global__ __launch_bounds__(THREADS, 2) void backsolve_kernel(const int4 *__restrict__ job,
-                                                            const int *__restrict__ dofmap,
-                                                            const double *__restrict__ W, int nmax,
-                                                            const RowTile *__restrict__ rt,
-                                                            const double *__restrict__ q,
-                                                            double *__restrict__ ppart, int nbmax,
+__global__ __launch_bounds__(THREADS, 2) void backsolve_kernel(const int4 *__restrict__ job, const int *__restrict__ dofmap,
+                                                            const double *__restrict__ W, int nmax, const RowTile *__restrict__ rt,
+                                                            const double *__restrict__ q, double *__restrict__ ppart, int nbmax,
                                                             const DevLoop *__restrict__ ctl, int spec, int nBig)
 {
     __shared__ double sm[2][THREADS / 64][32];
     __shared__ int s_abort[3];
-    __shared__ double2 rs[THREADS == 256 ? 2 * 256 * 6 : 1];   // (256 threads: right-hand side + accumulators of rows beyond 2560 columns)
+    __shared__ double2 rs[bs_rlds_slots(THREADS == 256 ? BSF_NARROW : BSF_WIDE)];   // (256 threads: rows beyond 2560 columns)
     if (ctl && (ctl->status != 0 || (ctl->phase != 0 && !spec))) return;
     // spec > 0: the slot's epoch (its 1-based index in the step); the controller, which runs meanwhile, publishes the epoch
     // of a slot whose trial it rejects or that ends the loop (DevLoop::abortEpoch)
     const int *abortp = (ctl && spec > 0 && spec < (1 << 30)) ? &ctl->abortEpoch : nullptr;
     if constexpr (THREADS == 256) {
-        if ((int)blockIdx.x >= nBig) {   // a pack of four small tiles, one wavefront each (backsolve_wave_tile)
-            const int4 jq = job[nBig + 4 * ((int)blockIdx.x - nBig) + (threadIdx.x >> 6)];
-#ifdef BS_PROFILE
-            if (threadIdx.x == 0 && blockIdx.x < 8192) {
-                g_bs_prof[blockIdx.x][0] = wall_clock64();
-                g_bs_prof[blockIdx.x][2] = jq.y + (jq.z >> 16) - jq.w;
-                g_bs_prof[blockIdx.x][3] = -(jq.z >> 16);
-                g_bs_prof[blockIdx.x][4] = 0;
-            }
-#endif
-            backsolve_wave_tile(jq, dofmap, W, nmax, rt, q, ppart, nbmax, abortp, spec);
-#ifdef BS_PROFILE
-            if (threadIdx.x == 0 && blockIdx.x < 8192) g_bs_prof[blockIdx.x][1] = wall_clock64();
-#endif
-            return;
-        }
+        if ((int)blockIdx.x >= nBig)
+            return backsolve_pack(blockIdx.x, bs_pack_job(job, nBig, blockIdx.x), dofmap, W, nmax, rt, q, ppart, nbmax, abortp, spec);
     }
     backsolve_block<THREADS>(blockIdx.x, job, dofmap, W, nmax, rt, q, ppart, nbmax, sm, abortp, spec, s_abort, rs);
 }
@@ -449,7 +435,7 @@ __global__ __launch_bounds__(256, 2) void backsolve_ctl_kernel(const int4 *__res
 {
     __shared__ double sm[2][4][32];
     __shared__ int s_abort[3];
-    __shared__ double2 rs[2 * 256 * 6];
+    __shared__ double2 rs[bs_rlds_slots(BSF_NARROW)];
     // (which workgroup hosts the controller makes no difference: index 0 / 256 / 520 / last measured 47.0-47.5 us)
     if (blockIdx.x == 0) {
         if constexpr (CTL == CTL_PAIR || CTL == CTL_PAIR_VP)
@@ -481,32 +467,12 @@ __global__ __launch_bounds__(256, 2) void backsolve_ctl_kernel(const int4 *__res
         __syncthreads();
     }
     const int jobIdx = (int)blockIdx.x - 1;
-    if (jobIdx >= nBig) {   // a pack of four small tiles, one wavefront each
-        const int4 jq = job[nBig + 4 * (jobIdx - nBig) + (threadIdx.x >> 6)];
-#ifdef BS_PROFILE
-        if (threadIdx.x == 0 && jobIdx < 8192) {
-            g_bs_prof[jobIdx][0] = wall_clock64();
-            g_bs_prof[jobIdx][2] = jq.y + (jq.z >> 16) - jq.w;
-            g_bs_prof[jobIdx][3] = -(jq.z >> 16);   // (negative: a pack; rows of its first tile)
-            g_bs_prof[jobIdx][4] = 0;
-        }
-#endif
-        backsolve_wave_tile(jq, dofmap, W, nmax, rt, q, ppart, nbmax, epoch < (1 << 30) ? &ca.ctl->abortEpoch : nullptr, epoch);
-#ifdef BS_PROFILE
-        if (threadIdx.x == 0 && jobIdx < 8192) g_bs_prof[jobIdx][1] = wall_clock64();   // (wavefront 0 of the four)
-#endif
-        return;
-    }
-    backsolve_block<256>(jobIdx, job, dofmap, W, nmax, rt, q, ppart, nbmax, sm,
-                         epoch < (1 << 30) ? &ca.ctl->abortEpoch : nullptr, epoch, s_abort, rs);
+    if (jobIdx >= nBig)
+        return backsolve_pack(jobIdx, bs_pack_job(job, nBig, jobIdx), dofmap, W, nmax, rt, q, ppart, nbmax,
+                              epoch < (1 << 30) ? &ca.ctl->abortEpoch : nullptr, epoch);
+    backsolve_block<256>(jobIdx, job, dofmap, W, nmax, rt, q, ppart, nbmax, sm, epoch < (1 << 30) ? &ca.ctl->abortEpoch : nullptr, epoch,
+                         s_abort, rs);
 }
-#ifdef BS_PROFILE
-extern "C" int dotmi_debug_bs_prof(long long *out, int n)
-{
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bs_prof), sizeof(long long) * 5 * (size_t)n);
-}
-#endif
-
 
 // psub_s[k] = sum over the row tiles b of the part whose column range holds k of ppart[s][b][k]
 //   (fixed order b = 0, 1, ..., coalesced in k)
@@ -570,17 +536,14 @@ __global__ __launch_bounds__(256) void reduce_partial_p_kernel(const int *__rest
 //                                                                                  (streams it a second time)
 // so these rows cost 2x their bytes.  Only the separator rows of the upper tree levels of big subdomains are that
 // long; everything else stays on the single-pass kernel above.
-constexpr int BSL_THREADS = 512, BSL_CH = 4, BSL_CW = 2 * BSL_THREADS * BSL_CH;   // 4096 columns per chunk
-
+// (BSL_THREADS x BSL_CH pairs = BS_LONG_CHUNK columns per workgroup, BSL_SUB rows per pass: bs_forms.hpp, where the job table counts
+// its work items in the same chunk)
 template <int PHASE>
-__global__ __launch_bounds__(BSL_THREADS) void backsolve_long_kernel(const int4 *__restrict__ ljob,
-                                                                     const int2 *__restrict__ lwork,
-                                                                     const int *__restrict__ dofmap,
-                                                                     const double *__restrict__ W, int nmax,
-                                                                     const RowTile *__restrict__ rt,
-                                                                     const double *__restrict__ q,
-                                                                     double *__restrict__ tdots, int maxChunks,
-                                                                     double *__restrict__ ppart, int nbmax,
+__global__ __launch_bounds__(BSL_THREADS) void backsolve_long_kernel(const int4 *__restrict__ ljob, const int2 *__restrict__ lwork,
+                                                                     const int *__restrict__ dofmap, const double *__restrict__ W,
+                                                                     int nmax, const RowTile *__restrict__ rt,
+                                                                     const double *__restrict__ q, double *__restrict__ tdots,
+                                                                     int maxChunks, double *__restrict__ ppart, int nbmax,
                                                                      const DevLoop *__restrict__ ctl, int spec)
 {
     constexpr int NW = BSL_THREADS / 64;
@@ -588,29 +551,19 @@ __global__ __launch_bounds__(BSL_THREADS) void backsolve_long_kernel(const int4 
     __shared__ double tsh[BS_ROWS];
     if (ctl && (ctl->status != 0 || (ctl->phase != 0 && !spec))) return;
     const int2 wk = lwork[blockIdx.x];          // (long-tile index, chunk)
-    const int4 jb = ljob[wk.x];
-    const int s = jb.x, i0 = jb.y, tileIdx = jb.z & 0xffff, cb = jb.w;
-    const int ns = i0 + (jb.z >> 16);
-    const int ncol = min((ns + 15) & ~15, nmax);
-    const int c0 = cb + wk.y * BSL_CW;           // this workgroup's columns [c0, c0 + BSL_CW) ∩ [cb, ncol)
+    const BsTile g = bs_tile(ljob[wk.x], nmax, rt, W, dofmap, q, ppart, nbmax);
+    const int c0 = g.cb + wk.y * BS_LONG_CHUNK;           // this workgroup's columns [c0, c0 + BS_LONG_CHUNK) ∩ [cb, ncol)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const RowTile rb = rt[(size_t)s * (nmax >> 6) + (i0 >> 6)];
-    const int ldw = rb.ld;
-    const double *Ws = W + (rb.off - (long long)(i0 & ~63) * ldw - rb.c0);
-    const int *dm = dofmap + (size_t)s * nmax;
     int cend[BSL_CH];
     double2 r[BSL_CH], pacc[BSL_CH];
 #pragma unroll
     for (int m = 0; m < BSL_CH; ++m) {
-        const int c = c0 + 2 * tid + 2 * BSL_THREADS * m;
-        const int d0 = (c < ncol) ? dm[c] : -1, d1 = (c < ncol) ? dm[c + 1] : -1;
-        if (PHASE == 0) r[m] = (c < ncol) ? *reinterpret_cast<const double2 *>(q + (size_t)s * nmax + c) : make_double2(0.0, 0.0);
+        cend[m] = bs_pair_end<false>(g, bs_col<BSL_THREADS>(c0, tid, m), PHASE == 0 ? &r[m] : nullptr);
         pacc[m] = make_double2(0.0, 0.0);
-        cend[m] = (d0 >= 0 || d1 >= 0) ? c : 0x7fffffff;
     }
     if (PHASE == 1) {
         // t_row: the chunk partials of phase 0 in chunk order
-        const int nch = (ncol - cb + BSL_CW - 1) / BSL_CW;
+        const int nch = (g.ncol - g.cb + BS_LONG_CHUNK - 1) / BS_LONG_CHUNK;
         if (tid < BS_ROWS) {
             double t = 0.0;
             for (int c = 0; c < nch; ++c) t += tdots[((size_t)wk.x * maxChunks + c) * BS_ROWS + tid];
@@ -620,19 +573,10 @@ __global__ __launch_bounds__(BSL_THREADS) void backsolve_long_kernel(const int4 
     }
 #pragma unroll 1
     for (int sb = 0; sb < BS_ROWS / 8; ++sb) {
-        const int ib = i0 + sb * 8;
-        if (ib >= ns) break;
+        const int ib = g.i0 + sb * 8;
+        if (ib >= g.ns) break;
         double2 y[8][BSL_CH];
-#pragma unroll
-        for (int rr = 0; rr < 8; ++rr) {
-            const double *row = Ws + (long long)min(ib + rr, ns - 1) * ldw;
-            const int rend = ((ib + rr) < ns) ? min(ncol, (ib + rr + 16) & ~15) : 0;
-#pragma unroll
-            for (int m = 0; m < BSL_CH; ++m) {
-                const int c = c0 + 2 * tid + 2 * BSL_THREADS * m;
-                y[rr][m] = (cend[m] < rend) ? *reinterpret_cast<const double2 *>(row + c) : make_double2(0.0, 0.0);
-            }
-        }
+        BS_LOAD_ROWS(8, BSL_CH, BSL_THREADS, false, c0, tid);
         if (PHASE == 0) {
             const int buf = sb & 1;
             double d[8];
@@ -666,14 +610,7 @@ __global__ __launch_bounds__(BSL_THREADS) void backsolve_long_kernel(const int4 
             }
         }
     }
-    if (PHASE == 1) {
-        double *out = ppart + ((size_t)s * nbmax + tileIdx) * nmax;
-#pragma unroll
-        for (int m = 0; m < BSL_CH; ++m) {
-            const int c = c0 + 2 * tid + 2 * BSL_THREADS * m;
-            if (c < ncol) *reinterpret_cast<double2 *>(out + c) = pacc[m];
-        }
-    }
+    if (PHASE == 1) bs_store<BSL_CH, BSL_THREADS>(g, c0, tid, pacc);
 }
 
 // ---- two-level form (DevTwoLevel, dotmi_internal.hpp): the three kernels around the tile kernels -------------------------------
@@ -805,6 +742,28 @@ __global__ __launch_bounds__(256) void twolevel_backward_kernel(const int4 *__re
     }
 }
 
+// A launch with the dispatch's own begin / end time stamps in e0 / e1 (either may be null) when `timed`, a plain launch otherwise.
+// Optional events time the streaming kernel alone (the roofline entry of bench.py is about that kernel): they are attached to the
+// dispatch itself (hipExtLaunchKernelGGL: the packet's own time stamps, what rocprofv3 reports as the kernel's duration) -- two
+// hipEventRecord calls around the launch add ~5 us of barrier packets
+// (common_type: the arguments take the kernel's parameter types, not types deduced a second time)
+template <class... A>
+static void launch_bs(bool timed, hipEvent_t e0, hipEvent_t e1, void (*kernel)(A...), dim3 grid, dim3 block, hipStream_t st,
+                      std::common_type_t<A>... args)
+{
+    if (timed) hipExtLaunchKernelGGL(kernel, grid, block, 0, st, e0, e1, 0, args...);
+    else hipLaunchKernelGGL(kernel, grid, block, 0, st, args...);
+}
+// rows beyond the register tile: the two-phase kernel on (tile, column chunk) work items
+static void launch_long(const DevParts &P, const int4 *ltile, const int2 *lwork, int nlwork, const double *rhs, const DevLoop *ctl,
+                        int spec, hipStream_t st)
+{
+    hipLaunchKernelGGL((backsolve_long_kernel<0>), dim3(nlwork), dim3(BSL_THREADS), 0, st, ltile, lwork, P.dofmap, P.W, P.nmax, P.rt,
+                       rhs, P.tdots, P.maxChunks, P.ppart, P.nbmax, ctl, spec);
+    hipLaunchKernelGGL((backsolve_long_kernel<1>), dim3(nlwork), dim3(BSL_THREADS), 0, st, ltile, lwork, P.dofmap, P.W, P.nmax, P.rt,
+                       rhs, P.tdots, P.maxChunks, P.ppart, P.nbmax, ctl, spec);
+}
+
 template <int CTL>
 static void launch_gemv_impl(const DevParts &P, const double *q, hipStream_t st, const DevLoop *ctl, hipEvent_t ev0, hipEvent_t ev1,
                              const CtlArgs *ca, int spec)
@@ -820,25 +779,19 @@ static void launch_gemv_impl(const DevParts &P, const double *q, hipStream_t st,
     hipEvent_t evLast = nullptr;   // two-level form: the timed region runs from the forward kernel to the backward kernel
     if (P.tl.on) {   // two-level form: t_G = r_G - M_GD r_D in front of the tile kernels
         if (P.tl.nPanels > 0) {
+            launch_bs(ev0 && ev1, ev0, nullptr, twolevel_forward_kernel, dim3((P.tl.nItems + 3) / 4), dim3(256), st, P.tl.nItems,
+                      P.tl.item, P.tl.panel, P.tl.rowBase, P.tl.packed, P.rpad, P.tl.cbuf, ctl);
             if (ev0 && ev1) {
-                hipExtLaunchKernelGGL(twolevel_forward_kernel, dim3((P.tl.nItems + 3) / 4), dim3(256), 0, st, ev0, (hipEvent_t) nullptr, 0,
-                                      P.tl.nItems, P.tl.item, P.tl.panel, P.tl.rowBase, (const double *)P.tl.packed,
-                                      (const double *)P.rpad, P.tl.cbuf, ctl);
                 evLast = ev1;
                 ev0 = ev1 = nullptr;
-            } else
-                hipLaunchKernelGGL(twolevel_forward_kernel, dim3((P.tl.nItems + 3) / 4), dim3(256), 0, st, P.tl.nItems, P.tl.item,
-                                   P.tl.panel, P.tl.rowBase, (const double *)P.tl.packed, (const double *)P.rpad, P.tl.cbuf, ctl);
+            }
         }
         const int total = P.nParts * P.nmax;
         hipLaunchKernelGGL(twolevel_rhs_kernel, dim3(std::min((total + 255) / 256, 4096)), dim3(256), 0, st, total, P.tl.gPtr, P.tl.gIdx,
                            (const double *)P.rpad, (const double *)P.tl.cbuf, P.tl.rpad2, ctl);
         rhs = P.tl.rpad2;
     }
-    // optional events time the streaming kernel alone (the roofline entry of bench.py is about that kernel): they are
-    // attached to the dispatch itself (hipExtLaunchKernelGGL: the packet's own begin / end time stamps, what rocprofv3
-    // reports as the kernel's duration) -- two hipEventRecord calls around the launch add ~5 us of barrier packets
-    // wide tiles (rows of 2561..4096 columns) on the 512-thread kernel, the rest on the 256-thread one (two workgroups per
+    // wide tiles (rows of 3073..5120 columns) on the 512-thread kernel, the rest on the 256-thread one (two workgroups per
     // CU instead of one); the events (if any) span both launches: start of the first, stop of the last
     // P.tile = [wide tiles | narrow tiles of more than 256 columns | packs of four small tiles]: job k < nN of the narrow launch
     // is one tile, job nN + k the four tiles P.tile[ntiles + 4 k ..] (one wavefront each, backsolve_wave_tile)
@@ -847,50 +800,24 @@ static void launch_gemv_impl(const DevParts &P, const double *q, hipStream_t st,
     if (ca && spec <= 0) spec = 1;   // (callers pass the slot's epoch: > 0)
     if (ca && nG == 0)   // no launch of the 256-thread kernel to host it: the controller on its own, in front
         launch_loop_control(ca->ctl, ca->partE, ca->nbE, ca->partR, ca->alpha_dev, ca->flags_host, st, ca->init & 1);
-    if (nW > 0) {
-        if (timed)
-            hipExtLaunchKernelGGL((backsolve_kernel<512>), dim3(nW), dim3(512), 0, st, ev0, nG > 0 ? (hipEvent_t) nullptr : ev1, 0,
-                                  P.tile, P.dofmap, P.W, P.nmax, P.rt, rhs, P.ppart, P.nbmax, ctl, spec, nW);
-        else
-            hipLaunchKernelGGL((backsolve_kernel<512>), dim3(nW), dim3(512), 0, st, P.tile, P.dofmap, P.W, P.nmax, P.rt, rhs,
-                               P.ppart, P.nbmax, ctl, spec, nW);
-    }
-    if (nG > 0 && ca) {
-        // one workgroup more: the controller (backsolve_ctl_kernel)
-        if (timed)
-            hipExtLaunchKernelGGL(backsolve_ctl_kernel<CTL>, dim3(nG + 1), dim3(256), 0, st, nW > 0 ? (hipEvent_t) nullptr : ev0, ev1, 0,
-                                  P.tile + nW, P.dofmap, P.W, P.nmax, P.rt, rhs, P.ppart, P.nbmax, *ca, spec, nN);
-        else
-            hipLaunchKernelGGL(backsolve_ctl_kernel<CTL>, dim3(nG + 1), dim3(256), 0, st, P.tile + nW, P.dofmap, P.W, P.nmax, P.rt,
-                               rhs, P.ppart, P.nbmax, *ca, spec, nN);
-    } else if (nG > 0) {
-        if (timed)
-            hipExtLaunchKernelGGL((backsolve_kernel<256>), dim3(nG), dim3(256), 0, st, nW > 0 ? (hipEvent_t) nullptr : ev0, ev1, 0,
-                                  P.tile + nW, P.dofmap, P.W, P.nmax, P.rt, rhs, P.ppart, P.nbmax, ctl, spec, nN);
-        else
-            hipLaunchKernelGGL((backsolve_kernel<256>), dim3(nG), dim3(256), 0, st, P.tile + nW, P.dofmap, P.W, P.nmax, P.rt,
-                               rhs, P.ppart, P.nbmax, ctl, spec, nN);
-    }
-    if (P.nltiles > 0) {
-        hipLaunchKernelGGL((backsolve_long_kernel<0>), dim3(P.nlwork), dim3(BSL_THREADS), 0, st, P.ltile, P.lwork, P.dofmap,
-                           P.W, P.nmax, P.rt, rhs, P.tdots, P.maxChunks, P.ppart, P.nbmax, ctl, spec);
-        hipLaunchKernelGGL((backsolve_long_kernel<1>), dim3(P.nlwork), dim3(BSL_THREADS), 0, st, P.ltile, P.lwork, P.dofmap,
-                           P.W, P.nmax, P.rt, rhs, P.tdots, P.maxChunks, P.ppart, P.nbmax, ctl, spec);
-    }
+    if (nW > 0)
+        launch_bs(timed, ev0, nG > 0 ? nullptr : ev1, backsolve_kernel<512>, dim3(nW), dim3(512), st, P.tile, P.dofmap, P.W, P.nmax,
+                  P.rt, rhs, P.ppart, P.nbmax, ctl, spec, nW);
+    if (nG > 0 && ca)   // one workgroup more: the controller (backsolve_ctl_kernel)
+        launch_bs(timed, nW > 0 ? nullptr : ev0, ev1, backsolve_ctl_kernel<CTL>, dim3(nG + 1), dim3(256), st, P.tile + nW, P.dofmap,
+                  P.W, P.nmax, P.rt, rhs, P.ppart, P.nbmax, *ca, spec, nN);
+    else if (nG > 0)
+        launch_bs(timed, nW > 0 ? nullptr : ev0, ev1, backsolve_kernel<256>, dim3(nG), dim3(256), st, P.tile + nW, P.dofmap, P.W,
+                  P.nmax, P.rt, rhs, P.ppart, P.nbmax, ctl, spec, nN);
+    if (P.nltiles > 0) launch_long(P, P.ltile, P.lwork, P.nlwork, rhs, ctl, spec, st);
     if (!P.mt_ptr) launch_reduce_partial(P, st, ctl);   // (merge_tiles_kernel sums the tile partials itself)
     if (P.tl.on && P.tl.nPanels > 0)   // p_D = q_D - M_GD^T p_G on the sums just formed
     {
         const size_t shm = 8 * (size_t)((P.tl.maxRows + 7) & ~7) + 16 * 256;   // (dotmi_create refuses panels beyond 7000 rows)
         const int cw = twolevel_backward_cw(P.tl.maxCols);   // (loop_forms.hpp: dotmi_loop_forms reports the same choice)
-        if (cw == 32)
-            hipExtLaunchKernelGGL(twolevel_backward_kernel<32>, dim3(P.tl.nPanels), dim3(256), shm, st, (hipEvent_t) nullptr, evLast, 0,
-                                  P.tl.panel, P.tl.rowBase, P.tl.rowPos, (const double *)P.tl.packed, P.psub, ctl);
-        else if (cw == 64)
-            hipExtLaunchKernelGGL(twolevel_backward_kernel<64>, dim3(P.tl.nPanels), dim3(256), shm, st, (hipEvent_t) nullptr, evLast, 0,
-                                  P.tl.panel, P.tl.rowBase, P.tl.rowPos, (const double *)P.tl.packed, P.psub, ctl);
-        else
-            hipExtLaunchKernelGGL(twolevel_backward_kernel<128>, dim3(P.tl.nPanels), dim3(256), shm, st, (hipEvent_t) nullptr, evLast, 0,
-                                  P.tl.panel, P.tl.rowBase, P.tl.rowPos, (const double *)P.tl.packed, P.psub, ctl);
+        const auto backward = cw == 32 ? twolevel_backward_kernel<32> : cw == 64 ? twolevel_backward_kernel<64> : twolevel_backward_kernel<128>;
+        hipExtLaunchKernelGGL(backward, dim3(P.tl.nPanels), dim3(256), shm, st, (hipEvent_t) nullptr, evLast, 0, P.tl.panel, P.tl.rowBase,
+                              P.tl.rowPos, (const double *)P.tl.packed, P.psub, ctl);
     }
 }
 // one instantiation per form of the controller (without a controller the form plays no part)
@@ -931,20 +858,12 @@ void launch_gemv_part(const DevParts &P, int ls, const int4 *job, int njobs, con
     if (njobs <= 0 && nlwork <= 0) return;
     hipLaunchKernelGGL(gather_pad_kernel, dim3((P.nmax + 255) / 256), dim3(256), 0, st, P.nmax, P.dofmap + (size_t)ls * P.nmax,
                        q, P.rpad + (size_t)ls * P.nmax);
-    if (njobs > 0) {
-        if (P.maxTileLen <= BS_NARROW)
-            hipLaunchKernelGGL((backsolve_kernel<256>), dim3(njobs), dim3(256), 0, st, job, P.dofmap, P.W, P.nmax, P.rt, P.rpad,
-                               P.ppart, P.nbmax, (const DevLoop *)nullptr, 0, njobs);
-        else
-            hipLaunchKernelGGL((backsolve_kernel<512>), dim3(njobs), dim3(512), 0, st, job, P.dofmap, P.W, P.nmax, P.rt, P.rpad,
-                               P.ppart, P.nbmax, (const DevLoop *)nullptr, 0, njobs);
+    if (njobs > 0) {   // all tiles in one launch: the 256-thread kernel if one of its forms holds the longest row, else the 512-thread one
+        const bool narrow = bs_form_index(BSF_NARROW, P.maxTileLen) < bs_form_count(BSF_NARROW);
+        launch_bs(false, nullptr, nullptr, narrow ? backsolve_kernel<256> : backsolve_kernel<512>, dim3(njobs),
+                  dim3(BSF_LANES[narrow ? BSF_NARROW : BSF_WIDE]), st, job, P.dofmap, P.W, P.nmax, P.rt, P.rpad, P.ppart, P.nbmax, nullptr, 0, njobs);
     }
-    if (nlwork > 0) {   // rows beyond the register tile: the two-phase kernel on this part's work items
-        hipLaunchKernelGGL((backsolve_long_kernel<0>), dim3(nlwork), dim3(BSL_THREADS), 0, st, P.ltileByPart, lwork, P.dofmap,
-                           P.W, P.nmax, P.rt, P.rpad, P.tdots, P.maxChunks, P.ppart, P.nbmax, (const DevLoop *)nullptr, 0);
-        hipLaunchKernelGGL((backsolve_long_kernel<1>), dim3(nlwork), dim3(BSL_THREADS), 0, st, P.ltileByPart, lwork, P.dofmap,
-                           P.W, P.nmax, P.rt, P.rpad, P.tdots, P.maxChunks, P.ppart, P.nbmax, (const DevLoop *)nullptr, 0);
-    }
+    if (nlwork > 0) launch_long(P, P.ltileByPart, lwork, nlwork, P.rpad, nullptr, 0, st);
     hipLaunchKernelGGL(reduce_partial_p_kernel, dim3((P.nmax + 255) / 256, 1), dim3(256), 0, st, P.rp_ptr, P.rp_idx, P.ppart,
                        P.nmax, P.nbmax, P.psub, (const DevLoop *)nullptr, ls);
     hipLaunchKernelGGL(fill_part_kernel, dim3((P.nmax + 255) / 256), dim3(256), 0, st, P.dofmap, P.psub, P.nmax, ls, p);

@@ -246,6 +246,17 @@ void check_mesh(Mesh &M, int nParts)
         say(E);
     }
     unsetenv("DOTMI_TILE_ROWS");
+    {   // dotmi_plan_backsolve_forms
+        const char *E = "dotmi_plan_backsolve_forms";
+        int32_t c[4];
+        expect(E, "sizes", dotmi_plan_backsolve_forms(0, nullptr, c), 0);
+        I32 forms(6 * (size_t)c[0]);
+        expect(E, "arrays", dotmi_plan_backsolve_forms(c[0], forms, c), 0);
+        invalid(E, dotmi_plan_backsolve_forms(c[0] - 1, forms, c));   // (too small a table)
+        invalid(E, dotmi_plan_backsolve_forms(0, nullptr, nullptr));
+        std::snprintf(line, sizeof line, "%d forms, two-phase kernel %d lanes x %d rows on chunks of %d columns", (int)c[0], (int)c[1], (int)c[2], (int)c[3]);
+        say(E);
+    }
 
     {   // dotmi_plan_backsolve_form
         int32_t form = -1;

@@ -80,7 +80,7 @@ EXPORTS = [
     "dotmi_get_state", "dotmi_set_dirichlet", "dotmi_refix", "dotmi_step", "dotmi_last_iter_log",
     "dotmi_target_gres", "dotmi_eval_energy", "dotmi_eval_gradient", "dotmi_eval_elem_hessians",
     "dotmi_refactor", "dotmi_apply_precond", "dotmi_spmv", "dotmi_get_features", "dotmi_part_size", "dotmi_padded_size",
-    "dotmi_part_matrix", "dotmi_factor_storage_bytes", "dotmi_factor_kind", "dotmi_factor_groups", "dotmi_backsolve_form", "dotmi_plan_backsolve_form", "dotmi_probe_direction", "dotmi_bench_precond", "dotmi_bench_energy", "dotmi_bench_kernel", "dotmi_plan_shards", "dotmi_plan_layout", "dotmi_plan_tile_schedule", "dotmi_plan_tile_schedule_two_level", "dotmi_plan_tile_deps", "dotmi_plan_tile_groups", "dotmi_plan_grouped_tile_schedule", "dotmi_plan_tile_fill", "dotmi_plan_tile_fill_mesh", "dotmi_plan_backsolve_tiles", "dotmi_plan_patches", "dotmi_plan_vpatches", "dotmi_plan_vpatch_records", "dotmi_operand_records", "dotmi_loop_forms", "dotmi_plan_loop_forms", "dotmi_plan_rank", "dotmi_partition",
+    "dotmi_part_matrix", "dotmi_factor_storage_bytes", "dotmi_factor_kind", "dotmi_factor_groups", "dotmi_backsolve_form", "dotmi_plan_backsolve_form", "dotmi_probe_direction", "dotmi_bench_precond", "dotmi_bench_energy", "dotmi_bench_kernel", "dotmi_plan_shards", "dotmi_plan_layout", "dotmi_plan_tile_schedule", "dotmi_plan_tile_schedule_two_level", "dotmi_plan_tile_deps", "dotmi_plan_tile_groups", "dotmi_plan_grouped_tile_schedule", "dotmi_plan_tile_fill", "dotmi_plan_tile_fill_mesh", "dotmi_plan_backsolve_tiles", "dotmi_plan_backsolve_forms", "dotmi_plan_patches", "dotmi_plan_vpatches", "dotmi_plan_vpatch_records", "dotmi_operand_records", "dotmi_loop_forms", "dotmi_plan_loop_forms", "dotmi_plan_rank", "dotmi_partition",
     "dotmi_plan_pd",
     "dotmi_plan_ic", "dotmi_ic_info", "dotmi_ic_factor",
     "dotmi_set_rel_tol", "dotmi_set_time_step", "dotmi_set_lame",
@@ -188,6 +188,8 @@ def load() -> C.CDLL:
     if hasattr(L, "dotmi_plan_backsolve_tiles"):   # (round 5 entry; guarded like the two above -- ADVICE r05)
         L.dotmi_plan_backsolve_tiles.argtypes = [C.c_int32, C.c_int32, c_ip, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32,
                                                  C.c_int32, c_ip, c_ip]
+    if hasattr(L, "dotmi_plan_backsolve_forms"):   # (guarded like the ones around it: a DOTMI_LIBRARY build from before the entry)
+        L.dotmi_plan_backsolve_forms.argtypes = [C.c_int32, c_ip, c_ip]
     for name in EXPORTS:
         fn = getattr(L, name, None)
         if fn is None:

@@ -391,6 +391,12 @@ int dotmi_plan_tile_fill_mesh(int32_t nV, int32_t nT, const int32_t *T, const do
  * tiles may be NULL (counts only).  tests/test_host_logic.py */
 int dotmi_plan_backsolve_tiles(int32_t nV, int32_t nT, const int32_t *T, const double *Xrest, const int32_t *epart, int32_t nParts,
                                int32_t p0, int32_t p1, int32_t cap, int32_t *tiles, int32_t *counts);
+/* (host only) the kernel forms those tiles run on, from the table the kernels are instantiated from (dot_amd/csrc/bs_forms.hpp): up to
+ * cap rows of 6 int32 {family, lanes, chunks, rows per pass, RLDS, longest row}, family 0 = a wavefront of a pack, 1 = the 256-thread
+ * workgroup, 2 = the 512-thread one; a family's forms ascend and a tile takes the first that holds its longest row.
+ * counts[4] = {forms, and of the two-phase kernel: lanes, rows per pass, columns per chunk}.  forms may be NULL (counts only).
+ * tests/backsolve_cases.py */
+int dotmi_plan_backsolve_forms(int32_t cap, int32_t *forms, int32_t *counts);
 int dotmi_plan_layout(int32_t nV, int32_t nT, const int32_t *T, const double *Xrest, const int32_t *epart,
                       int32_t nParts, int32_t p0, int32_t p1, int32_t levels, int32_t min_split,
                       int32_t node_cap, int32_t *nodes, int32_t *n_nodes, int32_t *nmax, int32_t *pos);

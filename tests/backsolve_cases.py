@@ -1,17 +1,35 @@
 """The cases of tests/test_gpu_backsolve_forms.py and what the host-only planner says about them (no GPU): which instantiation of
 the back-solve kernels (dot_amd/csrc/k_backsolve.hip) every tile of a case's job table goes to, and the rows whose unit vectors the
-GPU test applies.  tests/test_backsolve_reference.py pins the forms per case on the CPU, so a threshold change that takes a form out
-of the GPU test's reach fails there."""
+GPU test applies.  The forms -- their names, the longest row each takes and its rows per pass -- are read from the table the kernels
+are instantiated from (dot_amd/csrc/bs_forms.hpp, through the host-only entry dotmi_plan_backsolve_forms); the forms per case are
+pinned in CASES below and checked on the CPU by tests/test_backsolve_reference.py, so a change of that table that takes a form out of
+the GPU test's reach, or renames one, fails there."""
+import ctypes as C
+
 import numpy as np
 
-# form -> (longest row it takes, rows per pass); the dispatch of backsolve_wave_tile, backsolve_block<256> / <512> and the two-phase
-# kernel, restated: a change there has to be made here too, and then shows in the pinned table below
-PACK_FORMS = [("wave<1,32>", 128, 32), ("wave<2,16>", 256, 16)]
-NARROW_FORMS = [("tile<256,1,32>", 512, 32), ("tile<256,2,16>", 1024, 16), ("tile<256,3,8>", 1536, 8), ("tile<256,5,8>", 2560, 8),
-                ("tile<256,6,8,RLDS>", 3072, 8)]
-WIDE_FORMS = [("tile<512,4,8>", 4096, 8), ("tile<512,5,8>", 5120, 8)]
-LONG_FORM = ("long", 1 << 30, 8)
-LONG_CHUNK = 4096
+from dot_amd import lib as dl
+
+
+def _forms():
+    """per family [(name, longest row it takes, rows per pass)] in the table's order, and the two-phase kernel's (rows per pass,
+    columns per chunk)"""
+    L = dl.load()
+    counts = np.zeros(4, dtype=np.int32)
+    assert L.dotmi_plan_backsolve_forms(0, None, dl.ip(counts)) == 0
+    rows = np.zeros((int(counts[0]), 6), dtype=np.int32)
+    assert L.dotmi_plan_backsolve_forms(rows.shape[0], dl.ip(rows), dl.ip(counts)) == 0
+    fams = [[], [], []]
+    for fam, lanes, chunks, sub, rlds, longest in rows.tolist():
+        name = f"wave<{chunks},{sub}>" if fam == 0 else f"tile<{lanes},{chunks},{sub}{',RLDS' if rlds else ''}>"
+        fams[fam].append((name, longest, sub))
+    return fams, int(counts[2]), int(counts[3])
+
+
+(PACK_FORMS, NARROW_FORMS, _WIDE_ALL), _LONG_SUB, LONG_CHUNK = _forms()
+# the 512-thread forms whose rows the 256-thread family holds as well take tiles only in GSDD's per-part launch (below)
+WIDE_FORMS = [f for f in _WIDE_ALL if f[1] > NARROW_FORMS[-1][1]]
+LONG_FORM = ("long", 1 << 30, _LONG_SUB)
 ROWS_PER_PASS = dict((f[0], f[2]) for f in PACK_FORMS + NARROW_FORMS + WIDE_FORMS + [LONG_FORM])
 # every instantiation the all-parts launch (launch_gemv) can reach.  backsolve_tile<512,1,32> and <512,2,16> take tiles only in GSDD's
 # per-part launch (launch_gemv_part with maxTileLen > 3072), which no entry applies on its own: out of scope
