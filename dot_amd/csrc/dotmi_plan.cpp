@@ -446,6 +446,12 @@ int dotmi_plan_tile_fill_mesh(int32_t nV, int32_t nT, const int32_t *T, const do
     double *const W2 = W + (long long)F.wTotal;
     FactorSchedule FS;
     ScheduleRules SR;
+    {   // the eager rules dotmi_create reads from the environment (DOTMI_TILE_EAGER_MIN, DOTMI_TILE_EAGER_MIN_RMUL)
+        const Tuning tune = Tuning::from_env();
+        SR.eagerMin = tune.tileEagerMin;
+        SR.eagerMinRmul = tune.tileEagerMinRmul;
+        SR.eagerMinRmulByUser = tune.tileEagerMinRmulByUser;
+    }
     SR.tileFlow = 0;
     SR.groups = groups;
     SR.hfill = true;

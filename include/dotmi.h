@@ -377,7 +377,8 @@ int dotmi_plan_tile_fill(int32_t n_blocks, int32_t nt, const uint8_t *live, cons
                          int32_t eager_chunk, int32_t groups, int64_t n_fill, const int64_t *fill_dst, const int32_t *fill_src,
                          int64_t n_pad, const int64_t *pad_dst, int64_t *counts, int64_t *tasks, int64_t *clear, int32_t *entry_pos,
                          int32_t *entry_src);
-/* (host only) the same for all parts of a mesh through dotmi_create's own planning stages (two_level: the leaves-first form); also
+/* (host only) the same for all parts of a mesh through dotmi_create's own planning stages (two_level: the leaves-first form; the
+ * eager rules from DOTMI_TILE_EAGER_MIN / DOTMI_TILE_EAGER_MIN_RMUL, as dotmi_create reads them); also
  * returns the fill lists the entry lists come from: fill_dst[9 counts[3]], fill_src[counts[3]], pad_dst[counts[4]] */
 int dotmi_plan_tile_fill_mesh(int32_t nV, int32_t nT, const int32_t *T, const double *Xrest, const int32_t *epart, int32_t nParts,
                               int32_t groups, int32_t two_level, int64_t *counts, int64_t *tasks, int64_t *clear, int32_t *entry_pos,

@@ -13,7 +13,8 @@ Which forms each case reaches is pinned on the CPU in tests/test_backsolve_refer
 
 Out of scope: the two-level form (no explicit X_s; tests/test_gpu_two_level.py), the in-loop backsolve_ctl_kernel (same tile bodies,
 held to the host loop by the bit-identity tests), GSDD's per-part launch -- the only way to backsolve_tile<512,1,32> and <512,2,16>
---, and the factorisation's accuracy: nothing here asks whether X^T X = H^-1."""
+--, and the factorisation's accuracy: nothing here asks whether X^T X = H^-1; tests/test_gpu_factor_accuracy.py does, on the
+H_s the device assembled, with a bound derived the same way."""
 import numpy as np
 import pytest
 

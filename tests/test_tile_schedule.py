@@ -57,24 +57,37 @@ def nd_pattern(nt, leaves, seps, rng, drop=0.0):
     return pat, c0
 
 
-def run_schedule(nt, live, pat, c0, eager_min, eager_chunk, seed):
-    rng = np.random.default_rng(seed)
-    tasks, prods, nlev, storage, roff, rld = plan(nt, live, pat, c0, eager_min, eager_chunk)
-    n = 64 * nt
-    # an SPD matrix with exactly this tile pattern (symmetric), identity on the rows of non-live tiles
-    H = np.zeros((n, n))
-    for i in range(nt):
-        for j in range(i, nt):
-            if pat[i, j] and live[i] and live[j]:
-                B = rng.standard_normal((64, 64)) * 0.05
-                H[64 * i:64 * i + 64, 64 * j:64 * j + 64] = B
-    H = np.triu(H) + np.triu(H, 1).T
-    H += np.diag(np.abs(H).sum(1) + 1.0)
-    for j in range(nt):
-        if not live[j]:
-            H[64 * j:64 * j + 64, :] = 0
-            H[:, 64 * j:64 * j + 64] = 0
-            H[64 * j:64 * j + 64, 64 * j:64 * j + 64] = np.eye(64)
+class Hooks:
+    """What a caller of execute_levels may vary (tests/factor_reference.py: summation orders, the kernels' own diagonal recursion,
+    mutations); the defaults are the plain execution run_schedule checks."""
+
+    def products(self, t, plist):
+        """the product indices task t applies, in order"""
+        return plist
+
+    def add(self, acc, terms):
+        """acc plus the signed products, in the list's order"""
+        for P in terms:
+            acc = acc + P
+        return acc
+
+    def diag(self, t, acc):
+        """Q_jj (upper) of a TP_DIAG task: acc = R^T R, Q = R^-1"""
+        return np.linalg.inv(np.linalg.cholesky(acc).T)
+
+    def rmul_sign(self, t):
+        return -1.0
+
+    def done(self, t, terms, out):
+        pass
+
+
+def execute_levels(plan_out, nt, live, pat, c0, H, hooks=None):
+    """The tasks of `plan_out` (what plan() returns) executed in numpy on the matrix H (64 nt square, identity on the rows of non-live
+    tiles), level after level, every task of a level on the state the levels before it left; asserts that no two tasks of a level
+    write the same tile and that none reads a tile its level writes.  Returns tile(off, ld): the 64 x 64 view of the buffers."""
+    hooks = hooks or Hooks()
+    tasks, prods, nlev, storage, roff, rld = plan_out
     # everything starts as NaN: only the tiles the fill writes into (the pattern of H, in the work buffer) are cleared and
     # filled on the device; pure fill-in tiles and every tile of the factor buffer must be written before they are read
     M = np.full(2 * storage + 4096, np.nan)
@@ -109,26 +122,28 @@ def run_schedule(nt, live, pat, c0, eager_min, eager_chunk, seed):
             acc = stile(coff, ldc) if init else np.zeros((64, 64))
             if init:
                 read.add(coff)
-            for p in range(first, first + nprod):
+            terms = []
+            for p in hooks.products(int(t), list(range(first, first + nprod))):
                 a, b, lda, ldb = prods[p]
                 A, Bm = stile(a, lda), stile(b, ldb)
                 read.update((a, b))
-                acc = acc - A.T @ Bm if form == TF_FACT else acc + A @ Bm
+                terms.append(-(A.T @ Bm) if form == TF_FACT else A @ Bm)
+            acc = hooks.add(acc, terms)
             if post == TP_DIAG:
-                R = np.linalg.cholesky(acc).T          # acc = R^T R
-                out = np.linalg.inv(R)                  # Q_jj (upper)
+                out = hooks.diag(int(t), acc)           # Q_jj (upper): acc = R^T R
             elif post == TP_ROW:
                 read.add(qoff)
                 out = stile(qoff, ldq).T @ acc
             elif post == TP_RMUL:
                 read.add(qoff)
-                out = -acc @ np.triu(stile(qoff, ldq))
+                out = hooks.rmul_sign(int(t)) * (acc @ np.triu(stile(qoff, ldq)))
             elif post == TP_NEG:
                 out = -acc
             else:
                 out = acc
             assert ooff not in written, "two tasks of one level write the same tile"
             written.add(ooff)
+            hooks.done(int(t), terms, out)
             tile(ooff, ldc)[:, :] = out
         # a tile written in this level may only be read by the task that writes it (its own init)
         for t in group:
@@ -140,6 +155,28 @@ def run_schedule(nt, live, pat, c0, eager_min, eager_chunk, seed):
             if init:
                 ops.add(coff)
             assert not (ops & others) and ooff not in (ops - {coff}), "a task reads a tile that is written in its own level"
+    return tile
+
+
+def run_schedule(nt, live, pat, c0, eager_min, eager_chunk, seed):
+    rng = np.random.default_rng(seed)
+    tasks, prods, nlev, storage, roff, rld = plan(nt, live, pat, c0, eager_min, eager_chunk)
+    n = 64 * nt
+    # an SPD matrix with exactly this tile pattern (symmetric), identity on the rows of non-live tiles
+    H = np.zeros((n, n))
+    for i in range(nt):
+        for j in range(i, nt):
+            if pat[i, j] and live[i] and live[j]:
+                B = rng.standard_normal((64, 64)) * 0.05
+                H[64 * i:64 * i + 64, 64 * j:64 * j + 64] = B
+    H = np.triu(H) + np.triu(H, 1).T
+    H += np.diag(np.abs(H).sum(1) + 1.0)
+    for j in range(nt):
+        if not live[j]:
+            H[64 * j:64 * j + 64, :] = 0
+            H[:, 64 * j:64 * j + 64] = 0
+            H[64 * j:64 * j + 64, 64 * j:64 * j + 64] = np.eye(64)
+    tile = execute_levels((tasks, prods, nlev, storage, roff, rld), nt, live, pat, c0, H)
     # compare with the dense inverse factor: H = R^T R, Q = R^-1 (upper), stored tile (i, j) = Q[64 i.., 64 j..]
     Q = np.linalg.inv(np.linalg.cholesky(H).T)
     worst = 0.0
