@@ -8,6 +8,7 @@
 // No device call here (exported as dotmi_plan_coarse; tests/test_coarse_host.py).
 #pragma once
 #include <algorithm>
+#include <utility>
 #include <vector>
 
 namespace dotmi {
@@ -76,6 +77,54 @@ inline void coarse_plan(int nV, int nT, const int *T, const int *epart, int nPar
             for (int s : vs[i])
                 for (int t : vs[adj_idx[k]])
                     if (s <= t) P.pairBlk[at[(size_t)s * nParts + t]++] = k;
+}
+
+// The lists of W = H Z for the balanced form of DOT's coarse term (dotmi_set_dot_coarse_mode, mode 2): W has a 3 x 6 block W[i, t] for every
+// vertex i and subdomain t that an H block (i, j) with j in t couples,
+//     W[i, t] = sum over the H blocks (i, j), j in t, of H_ij Z_tj.
+// Per vertex the subdomains of its entries ascending, per entry its H blocks ascending (indices into adj_idx: the summation order
+// of coarse_hz_kernel), and the transposed index: per subdomain its entries in ascending vertex, which c = W^T u walks.
+// No device call here (exported as dotmi_plan_coarse_hz; tests/test_dot_coarse_balanced_host.py).
+struct CoarseHzPlan {
+    std::vector<int> hzPtr, hzSub;      // per vertex: the subdomains t of its entries (i, t), ascending (CSR over nV)
+    std::vector<int> hzVert;            // per entry: its vertex i
+    std::vector<int> hzBlkPtr, hzBlk;   // per entry: the H blocks (i, j), j in t, ascending (CSR over the entries)
+    std::vector<int> hzTPtr, hzTEnt;    // per subdomain: its entries, ascending in the vertex (CSR over nParts)
+};
+
+// vsPtr / vsIdx: the subdomains of a vertex, ascending (CoarsePlan)
+inline void coarse_hz_plan(int nV, int nParts, const std::vector<int> &vsPtr, const std::vector<int> &vsIdx, const std::vector<int> &adj_ptr,
+                           const std::vector<int> &adj_idx, CoarseHzPlan &P)
+{
+    P.hzPtr.assign(nV + 1, 0);
+    P.hzSub.clear();
+    P.hzVert.clear();
+    P.hzBlkPtr.assign(1, 0);
+    P.hzBlk.clear();
+    std::vector<std::pair<int, int>> tk;   // (subdomain, block) of one vertex
+    for (int i = 0; i < nV; ++i) {
+        tk.clear();
+        for (int k = adj_ptr[i]; k < adj_ptr[i + 1]; ++k)
+            for (int a = vsPtr[adj_idx[k]]; a < vsPtr[adj_idx[k] + 1]; ++a) tk.emplace_back(vsIdx[a], k);
+        std::sort(tk.begin(), tk.end());
+        for (size_t e = 0; e < tk.size(); ++e) {
+            if (e == 0 || tk[e].first != tk[e - 1].first) {
+                if (e != 0) P.hzBlkPtr.push_back((int)P.hzBlk.size());
+                P.hzSub.push_back(tk[e].first);
+                P.hzVert.push_back(i);
+            }
+            P.hzBlk.push_back(tk[e].second);
+        }
+        if (!tk.empty()) P.hzBlkPtr.push_back((int)P.hzBlk.size());
+        P.hzPtr[i + 1] = (int)P.hzSub.size();
+    }
+    // the transposed index: a counting sort by subdomain keeps the entries' ascending vertex order
+    P.hzTPtr.assign(nParts + 1, 0);
+    for (int t : P.hzSub) ++P.hzTPtr[t + 1];
+    for (int t = 0; t < nParts; ++t) P.hzTPtr[t + 1] += P.hzTPtr[t];
+    P.hzTEnt.assign(P.hzSub.size(), 0);
+    std::vector<int> cur(P.hzTPtr.begin(), P.hzTPtr.end() - 1);
+    for (int e = 0; e < (int)P.hzSub.size(); ++e) P.hzTEnt[cur[P.hzSub[e]]++] = e;
 }
 
 }  // namespace dotmi

@@ -19,6 +19,10 @@
 // doubles per refresh makes pairA whole (disjoint contributions: the sum is exact).  Fill and factorisation of the one dense block run
 // on every rank.  Per application c = Z^T r rides in the tail of the vector the iteration all-reduces anyway and the solve runs on
 // every rank behind that collective (dot_coarse_restrict / dot_coarse_solve).
+// Mode 2 (dotmi_set_dot_coarse_mode) is the balanced form  M'' = C + (I - C H) M (I - H C),  C = Z A0^-1 Z^T: the same Z, A0 and factor,
+// and W = H Z as a sparse table of 3 x 6 blocks (coarse_hz_setup, coarse_hz_kernel behind the centroids of every build with the mode
+// on).  Per application three launches in front of the block solve (dot_coarse_deflate) and two behind the merge, which then leaves its
+// division, the prolongation and the y_i . z to the sharded merge's finishing kernel (dot_coarse_balance).  One rank, the q-based order.
 #include "coarse_plan.hpp"
 #include "dotmi_handle.hpp"
 
@@ -129,10 +133,50 @@ static int coarse_setup(dotmi_handle *h)
     return 0;
 }
 
+// mode 2: the lists of W = H Z and its buffers, at the first switch to mode 2; kept
+static int coarse_hz_setup(dotmi_handle *h)
+{
+    dotmi_handle::Coarse &K = h->coarse;
+    if (K.hzPlanned) return 0;
+    DevCoarse &D = K.D;
+    const int nP = h->nPartsAll, nV = h->nV;
+    std::vector<int> adj_ptr, adj_idx;
+    build_adjacency(nV, h->nT, h->T.data(), adj_ptr, adj_idx);
+    CoarsePlan P;
+    coarse_plan(nV, h->nT, h->T.data(), h->epart.data(), nP, adj_ptr, adj_idx, P);
+    CoarseHzPlan Z;
+    coarse_hz_plan(nV, nP, P.vsPtr, P.vsIdx, adj_ptr, adj_idx, Z);
+    D.nHz = (int)Z.hzSub.size();
+    if (Z.hzSub.empty()) {   // (no vertex in any subdomain: the launches over the entries are skipped, the lists stay addressable)
+        Z.hzSub.push_back(0);
+        Z.hzVert.push_back(0);
+        Z.hzTEnt.push_back(0);
+    }
+    if (Z.hzBlk.empty()) Z.hzBlk.push_back(0);
+    if (int rc = upload(h, &D.hzPtr, Z.hzPtr)) return rc;
+    if (int rc = upload(h, &D.hzSub, Z.hzSub)) return rc;
+    if (int rc = upload(h, &D.hzVert, Z.hzVert)) return rc;
+    if (int rc = upload(h, &D.hzBlkPtr, Z.hzBlkPtr)) return rc;
+    if (int rc = upload(h, &D.hzBlk, Z.hzBlk)) return rc;
+    if (int rc = upload(h, &D.hzTPtr, Z.hzTPtr)) return rc;
+    if (int rc = upload(h, &D.hzTEnt, Z.hzTEnt)) return rc;
+    if (int rc = dalloc(h, &D.hz, (size_t)18 * std::max(D.nHz, 1))) return rc;
+    if (int rc = dalloc(h, &D.cd, (size_t)D.ncp)) return rc;
+    if (int rc = dalloc(h, &D.r1, (size_t)h->n)) return rc;
+    HIPCHECK(h, hipMemset(D.hz, 0, sizeof(double) * 18 * std::max(D.nHz, 1)));
+    HIPCHECK(h, hipMemset(D.cd, 0, sizeof(double) * D.ncp));
+    if (h->tune.fuseLog)
+        fprintf(stderr, "dotmi: balanced coarse term: W = H Z in %d blocks of 3 x 6 over %zu H blocks\n", D.nHz, Z.hzBlk.size());
+    K.hzPlanned = true;
+    return 0;
+}
+
 int coarse_issue(dotmi_handle *h, const double *x)
 {
     dotmi_handle::Coarse &K = h->coarse;
     if (int rc = coarse_setup(h)) return rc;
+    if (K.dotMode == 2)
+        if (int rc = coarse_hz_setup(h)) return rc;
     DevCoarse &D = K.D;
     // weights and dropped subdomains from the handle's current fixed set (dotmi_refix changes it); uploaded when they change
     std::vector<double> wgt(h->nV);
@@ -155,6 +199,8 @@ int coarse_issue(dotmi_handle *h, const double *x)
     HIPCHECK(h, hipEventRecord(K.ev0, h->st));
     HIPCHECK(h, hipMemcpyAsync(D.xf, x, sizeof(double) * h->n, hipMemcpyDeviceToDevice, h->st));   // frozen with this build
     launch_coarse_centroid(D, h->st);
+    K.hzIssued = K.dotMode == 2;
+    if (K.hzIssued) launch_coarse_hz(D, h->M, h->Hval, h->st);   // W = H Z of this H, Z and these centroids (mode 2 only)
     launch_coarse_rtab(D, h->st);
     launch_coarse_assemble(D, h->M, h->Hval, h->st);
     // sharded Hessian refresh: every pair's block was assembled by exactly one rank, the owner of s, and is zero elsewhere
@@ -181,6 +227,7 @@ void coarse_finish(dotmi_handle *h)
     hipEventElapsedTime(&ms, K.ev0, K.ev1);
     K.lastBuildMs = ms;
     K.stale = false;
+    K.hzBuilt = K.hzIssued;
     K.builds++;
     K.active = K.h_info[0] == 0;   // a non-positive pivot: Z is rank deficient -- the applications go on without the coarse term
     if (h->tune.fuseLog)
@@ -215,6 +262,24 @@ void dot_coarse_restrict_solve(dotmi_handle *h, const DevLoop *ctl, int spec)
 {
     dot_coarse_restrict(h, nullptr, ctl, spec);
     dot_coarse_solve(h, nullptr, ctl, spec);
+}
+
+const double *dot_coarse_deflate(dotmi_handle *h, const double *q, const DevLoop *ctl)
+{
+    const DevCoarse &D = h->coarse.D;
+    if (ctl) launch_coarse_restrict_loop(D, q, h->st, ctl);   // c1 = Z^T q
+    else launch_coarse_restrict(D, q, h->st);
+    dot_coarse_solve(h, nullptr, ctl, 0);                      // y1 = A0^-1 c1
+    launch_coarse_deflate(D, h->n, q, D.r1, h->st, ctl);       // r1 = q - W y1
+    return D.r1;
+}
+
+void dot_coarse_balance(dotmi_handle *h, double *z, const LbfgsArgs &L, const DevLoop *ctl)
+{
+    const DevCoarse &D = h->coarse.D;
+    launch_coarse_restrict_hz(D, h->P.dup, z, h->st, ctl);     // cd = c1 - W^T u, u = z / dup
+    dot_coarse_solve(h, D.cd, ctl, 0);                         // y1 - y2 = A0^-1 cd
+    launch_zfinish(h->nV, h->P.dup, L, z, h->partC, h->st, ctl, &h->coarse.cm);   // z = u + Z (y1 - y2), the y_i . z
 }
 
 void coarse_restrict_solve(dotmi_handle *h, const double *r)
@@ -253,9 +318,12 @@ int dotmi_set_pcg_coarse(dotmi_handle *h, int32_t mode)
     return 0;
 }
 
-int dotmi_set_dot_coarse(dotmi_handle *h, int32_t mode)
+// the two setters of DOT's coarse term: dotmi_set_dot_coarse takes 0 and 1 as it always has (a caller that passes anything else is told
+// so, as before); dotmi_set_dot_coarse_mode takes 0, 1 and 2 -- 2 the balanced form.  One handle state, one set of refusals, one stale /
+// rebuild rule behind both
+static int set_dot_coarse_mode(dotmi_handle *h, int32_t mode, bool balanced)
 {
-    if (!h) return DOTMI_E_INVALID;
+    const std::string entry = balanced ? "dotmi_set_dot_coarse_mode: " : "dotmi_set_dot_coarse: ";
     const char *why = (h->world > 1 || h->dist) ? "single-rank handles only (the subdomains of this one are sharded)"
                       : h->owner                ? "not with the owner exchange"
                       : h->gsdd                 ? "a GSDD handle solves one subdomain at a time"
@@ -267,33 +335,43 @@ int dotmi_set_dot_coarse(dotmi_handle *h, int32_t mode)
                       : !h->vpart.empty() ? "the subdomains of this handle are vertex sets (vpart), the coarse plan works on an element partition"
                                           : nullptr;
     if (why) {
-        h->err = std::string("dotmi_set_dot_coarse: ") + why;
+        h->err = entry + why;
         return DOTMI_E_INVALID;
     }
-    if (mode != 0 && mode != 1) {
-        h->err = "dotmi_set_dot_coarse: mode must be 0 (off) or 1 (rigid modes)";
+    if (mode != 0 && mode != 1 && !(balanced && mode == 2)) {
+        h->err = entry + (balanced ? "mode must be 0 (off), 1 (rigid modes, additive) or 2 (rigid modes, balanced)"
+                                   : "mode must be 0 (off) or 1 (rigid modes)");
         return DOTMI_E_INVALID;
     }
-    if (mode == 1 && h->nPartsAll > COARSE_MAX_PARTS) {
-        h->err = "dotmi_set_dot_coarse: at most " + std::to_string(COARSE_MAX_PARTS) + " subdomains (the coarse matrix is applied through a dense "
+    if (mode != 0 && h->nPartsAll > COARSE_MAX_PARTS) {
+        h->err = entry + "at most " + std::to_string(COARSE_MAX_PARTS) + " subdomains (the coarse matrix is applied through a dense "
                  "inverse factor); this handle has " + std::to_string(h->nPartsAll);
         return DOTMI_E_INVALID;
     }
-    if (mode == h->coarse.dotMode) return 0;
+    const int prev = h->coarse.dotMode;
+    if (mode == prev) return 0;
     h->coarse.dotMode = mode;
     if (mode == 0) return 0;
     // the refreshes of H that ran while the mode was off built nothing: build now, from the H and the positions of the last one
+    // (mode 2 after a build that ran without it: that build left no W = H Z -- it is rebuilt with A0; 2 -> 1 keeps the build)
+    if (mode == 2 && !h->coarse.hzBuilt) h->coarse.stale = true;
     HIPCHECK(h, hipSetDevice(h->device));
     if (int rc = enter_with_factors(h)) {
-        h->coarse.dotMode = 0;
+        h->coarse.dotMode = prev;
         return rc;
     }
     if (int rc = coarse_refresh(h)) {
-        h->coarse.dotMode = 0;
+        h->coarse.dotMode = prev;
         return rc;
     }
     return 0;
 }
+
+int dotmi_set_dot_coarse(dotmi_handle *h, int32_t mode) { return h ? set_dot_coarse_mode(h, mode, false) : DOTMI_E_INVALID; }
+
+int dotmi_set_dot_coarse_mode(dotmi_handle *h, int32_t mode) { return h ? set_dot_coarse_mode(h, mode, true) : DOTMI_E_INVALID; }
+
+int32_t dotmi_dot_coarse_mode(const dotmi_handle *h) { return h ? h->coarse.dotMode : 0; }
 
 int dotmi_dot_coarse_info(const dotmi_handle *h, int32_t *dim, int32_t *dropped_subdomains, int32_t *active, int64_t *builds,
                           double *last_build_ms)
@@ -302,7 +380,7 @@ int dotmi_dot_coarse_info(const dotmi_handle *h, int32_t *dim, int32_t *dropped_
     const dotmi_handle::Coarse &K = h->coarse;
     if (dim) *dim = K.dotMode ? 6 * h->nPartsAll : 0;
     if (dropped_subdomains) *dropped_subdomains = K.dotMode ? K.dropped : 0;
-    if (active) *active = dot_coarse(h) != nullptr;
+    if (active) *active = dot_coarse(h) != nullptr || dot_coarse_balanced(h) != nullptr;
     if (builds) *builds = K.builds;
     if (last_build_ms) *last_build_ms = K.lastBuildMs;
     return 0;

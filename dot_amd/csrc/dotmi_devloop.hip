@@ -182,7 +182,18 @@ static int enqueue_loop_slot(dotmi_handle *h)
 {
     if (h->earlyNow) return enqueue_loop_slot_early(h);
     const int n = h->n;
-    launch_build_qpad(h->P, h->g, NO_HISTORY, nullptr, h->st, h->ctl);   // q, straight into the padded right-hand sides
+    // dotmi_set_dot_coarse_mode, mode 2 (the balanced form, one rank): q as a global vector, y1 = A0^-1 Z^T q and r1 = q - W y1 between
+    // build_q and the gather into the padded right-hand sides (launch_gemv's); behind the merge -- the sum over the subdomains only --
+    // c1 - W^T u, the second coarse solve and the finishing kernel with the division, Z (y1 - y2) and the y_i . z.  All gated like
+    // the back-solve of this order
+    const CoarseMerge *bal = dot_coarse_balanced(h);
+    const double *r1 = nullptr;
+    if (bal) {
+        launch_build_q(n, h->g, NO_HISTORY, nullptr, h->q, h->st, h->ctl);
+        r1 = dot_coarse_deflate(h, h->q, h->ctl);
+    } else {
+        launch_build_qpad(h->P, h->g, NO_HISTORY, nullptr, h->st, h->ctl);   // q, straight into the padded right-hand sides
+    }
     const CoarseMerge *co = dot_coarse(h);
     // dotmi_set_dot_coarse: y = A0^-1 Z^T q, gated like the back-solve (sharded subdomains: the restriction into the tail of z's
     // packet here, the solve behind the collective below)
@@ -190,8 +201,11 @@ static int enqueue_loop_slot(dotmi_handle *h)
     else if (co) dot_coarse_restrict_solve(h, h->ctl, 0);
     const Bracket br = backsolve_bracket(h);
     h->slotTimed.push_back(br.at);
-    launch_gemv(h->P, nullptr, h->st, h->ctl, br.ev0, br.ev1);
-    if (!h->dist) {
+    launch_gemv(h->P, r1, h->st, h->ctl, br.ev0, br.ev1);
+    if (bal) {
+        launch_merge(h->M, h->P, NO_HISTORY, {.z = h->z}, h->st, h->ctl);
+        dot_coarse_balance(h, h->z, NO_HISTORY, h->ctl);
+    } else if (!h->dist) {
         launch_merge(h->M, h->P, NO_HISTORY, {.z = h->z, .partials = h->partC, .dots = true, .divide = true, .co = co}, h->st, h->ctl);
     } else {
         // sharded subdomains: the one collective of an iteration, enqueued like a kernel.  It runs in every slot (also
@@ -230,7 +244,9 @@ static void choose_step_forms(dotmi_handle *h)
     // nothing per rejected trial and once at the end of the step, which the controller tells to stop (DevLoop::abortEpoch).
     // (Round 3's per-step rule from the previous step's counts, DOTMI_EARLY_BACKSOLVE=1, is gone: with the stop and the held
     // launches the early order is at least as fast on every workload, and the owner exchange has no other order -- ADVICE r04.)
-    h->earlyNow = h->earlyBs;
+    // (not in a step with the balanced coarse term active: the early order's merge forms z, M y_new and the y_i . z from u inside its
+    // own launch, before the second coarse solution can exist -- such a step runs the q-based order)
+    h->earlyNow = h->earlyBs && !dot_coarse_balanced(h);
     // paired trials: one rank, the fused step inside the element pass, the early order with held launches (the tiles of a paired
     // slot wait for the verdict); -1: only in steps that follow a step with halvings in at least a quarter of its iterations
     h->pairNow = h->earlyNow && !h->dist && h->tune.fuseStep && h->tune.fuseDir && h->tune.earlyHold &&

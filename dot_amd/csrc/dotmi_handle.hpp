@@ -258,7 +258,10 @@ struct dotmi_handle {
     // with the stream synchronisation the refresh takes anyway
     struct Coarse {
         int mode = 0;                 // dotmi_set_pcg_coarse: 0 off, 1 rigid modes
-        int dotMode = 0;              // dotmi_set_dot_coarse: 0 off, 1 rigid modes
+        int dotMode = 0;              // dotmi_set_dot_coarse: 0 off, 1 rigid modes (additive), 2 rigid modes (balanced: deflation around the block solve)
+        bool hzPlanned = false;       // mode 2's lists and buffers exist (the first switch to mode 2)
+        bool hzIssued = false;        // the build that is enqueued writes W (coarse_issue -> coarse_finish)
+        bool hzBuilt = false;         // the last build also wrote the table W = H Z (it ran with mode 2 on)
         bool pending = false;         // a build is enqueued, its pivot flag not yet read (coarse_issue -> coarse_finish)
         bool uploaded = false;        // the device's weights and live flags are those of wgt / live below
         CoarseMerge cm{};             // the merge kernels' view of the last build (launch_merge / launch_merge_early)
@@ -397,8 +400,20 @@ void coarse_finish(dotmi_handle *h);                  // ... and, after one, tak
 inline const CoarseMerge *dot_coarse(const dotmi_handle *h)
 {
     const dotmi_handle::Coarse &K = h->coarse;
-    return (K.dotMode != 0 && K.active && !K.stale) ? &K.cm : nullptr;
+    return (K.dotMode == 1 && K.active && !K.stale) ? &K.cm : nullptr;
 }
+// mode 2, the balanced form M'' = C + (I - C H) M (I - H C): the same record, for the prolongation behind the merge (nullptr: another
+// mode, or the last build met a bad pivot -- then plain M, in the early order).  One rank only (dotmi_set_dot_coarse refuses others)
+inline const CoarseMerge *dot_coarse_balanced(const dotmi_handle *h)
+{
+    const dotmi_handle::Coarse &K = h->coarse;
+    return (K.dotMode == 2 && K.active && !K.stale && K.hzBuilt) ? &K.cm : nullptr;
+}
+// its two halves around the block solve: y1 = A0^-1 Z^T q and the deflated right-hand side r1 = q - W y1 (returned: a buffer of the
+// coarse space's own) in front; behind the merge WITHOUT the division (z = the sum over the subdomains), z = z / dup + Z A0^-1 (Z^T q -
+// W^T (z / dup)) and the y_i . z partials of L into partC.  ctl: as kernels of the device loop's q-based order
+const double *dot_coarse_deflate(dotmi_handle *h, const double *q, const DevLoop *ctl = nullptr);
+void dot_coarse_balance(dotmi_handle *h, double *z, const LbfgsArgs &L, const DevLoop *ctl = nullptr);
 // the build that a refresh with the mode off has left undone (dotmi_set_dot_coarse only: the PCG builds in its solves)
 inline int dot_coarse_refresh(dotmi_handle *h) { return h->coarse.dotMode != 0 ? coarse_refresh(h) : 0; }
 // c = Z^T r from the padded right-hand sides, y = A0^-1 c (ctl: as kernels of the device-resident loop; spec: the early order)

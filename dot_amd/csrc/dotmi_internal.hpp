@@ -680,6 +680,16 @@ struct DevCoarse {
     // the pairs (s, t), s <= t, this handle assembles: those with s in [as0, as1) -- every pair, unless the Hessian refresh is sharded
     // (then [p0, p0 + nOwn), and pairA is summed over the ranks)
     int as0 = 0, as1 = 0;
+    // dotmi_set_dot_coarse_mode, mode 2 (the balanced form): W = H Z as a table of 3 x 6 blocks, one per (vertex, subdomain) entry of
+    // coarse_plan.hpp's CoarseHzPlan; nothing of it exists until mode 2 is switched on for the first time
+    int nHz = 0;                                        // entries
+    int *hzPtr = nullptr, *hzSub = nullptr;             // per vertex: the subdomains of its entries, ascending
+    int *hzVert = nullptr;                              // per entry: its vertex
+    int *hzBlkPtr = nullptr, *hzBlk = nullptr;          // per entry: its H blocks, ascending (the summation order of coarse_hz_kernel)
+    int *hzTPtr = nullptr, *hzTEnt = nullptr;           // per subdomain: its entries in ascending vertex
+    double *hz = nullptr;                               // 18 per entry: W[i, t], row-major 3 x 6, rebuilt with A0
+    double *cd = nullptr;                               // ncp: Z^T r - W^T u, what the second solve of an application reads
+    double *r1 = nullptr;                               // n: the deflated right-hand side r - W y1
 };
 // what a merge kernel's COARSE instantiation needs for the prolongation  u_v += w_v sum_{s holds v} (t_s + omega_s x (x_v - c_s))
 struct CoarseMerge {
@@ -701,6 +711,13 @@ void launch_coarse_rtab(const DevCoarse &C, hipStream_t st);
 void launch_coarse_restrict_pad(const DevCoarse &C, const double *rpad, hipStream_t st, const DevLoop *ctl = nullptr, int spec = 0,
                                 double *c = nullptr);
 void launch_coarse_solve_loop(const DevCoarse &C, hipStream_t st, const DevLoop *ctl, int spec, const double *c = nullptr);
+// dotmi_set_dot_coarse_mode, mode 2: the table W = H Z (once per build, behind the centroids); c = Z^T r on a global vector as a kernel of
+// the device loop's q-based order; r1 = r - W y with y the parts DevCoarse::y holds; DevCoarse::cd = c - W^T (zsum / dup).  ctl != nullptr:
+// gated by the loop's status and its retry phase
+void launch_coarse_hz(const DevCoarse &C, const DevMesh &M, const double *Hval, hipStream_t st);
+void launch_coarse_restrict_loop(const DevCoarse &C, const double *r, hipStream_t st, const DevLoop *ctl);
+void launch_coarse_deflate(const DevCoarse &C, int n, const double *r, double *r1, hipStream_t st, const DevLoop *ctl = nullptr);
+void launch_coarse_restrict_hz(const DevCoarse &C, const int *dup, const double *zsum, hipStream_t st, const DevLoop *ctl = nullptr);
 // host: the dense nc x nc matrix from the pairs' blocks, entry by entry as the fill kernel writes it
 void coarse_dense_host(int nc, int nParts, const int *pairAt, const int *live, const double *pairA, double *A0);
 

@@ -127,8 +127,19 @@ int gradient_over_ranks(dotmi_handle *h, int nb, const GatherArgs &pair)
 // dotmi_set_dot_coarse with an active term: + Z A0^-1 Z^T q -- the restriction from the padded right-hand sides (where launch_gemv has
 // put q, or build_qpad before it) and the coarse solve behind the back-solve, the prolongation inside the merge (sharded subdomains,
 // DOTMI_FLAG_DOT_COARSE: the restriction in the tail of z's packet, the solve behind the collective, the prolongation in zfinish)
+// Mode 2 with an active term, the balanced form M'' = C + (I - C H) M (I - H C): q (a global vector: the gather into the padded
+// right-hand sides is launch_gemv's) is deflated in front of the block solve, the merge leaves its division to the finishing kernel
+// behind the second coarse solve, which adds Z (y1 - y2) and forms the y_i . z on the corrected vector (dot_coarse_deflate / _balance)
 int apply_precond(dotmi_handle *h, const double *q, double *z, const LbfgsArgs &L)
 {
+    if (dot_coarse_balanced(h)) {
+        const double *r1 = dot_coarse_deflate(h, q);
+        const Bracket br = backsolve_bracket(h);
+        launch_gemv(h->P, r1, h->st, nullptr, br.ev0, br.ev1);
+        launch_merge(h->M, h->P, L, {.z = z}, h->st);   // the sum over the subdomains: no division, no coarse term, no dots
+        dot_coarse_balance(h, z, L);
+        return 0;
+    }
     const Bracket br = backsolve_bracket(h);
     launch_gemv(h->P, q, h->st, nullptr, br.ev0, br.ev1);
     const CoarseMerge *co = dot_coarse(h);
@@ -359,10 +370,13 @@ static int run_host_loop(dotmi_handle *h, LoopOut &r)
             phase_mark(h, DOTMI_T_MODIFY_GRAD);
             if (int rc = ic_apply(h, h->q, h->z, L)) return rc;
         } else {
-            launch_build_qpad(h->P, h->g, L, xi, h->st);   // q, straight into the padded right-hand sides
+            // q, straight into the padded right-hand sides (the balanced coarse term deflates the global vector first)
+            const bool balanced = dot_coarse_balanced(h) != nullptr;
+            if (balanced) launch_build_q(n, h->g, L, xi, h->q, h->st);
+            else launch_build_qpad(h->P, h->g, L, xi, h->st);
             phase_mark(h, DOTMI_T_MODIFY_GRAD);
             // ---- subdomain back-solve, merge, second half ------------------------------------------------
-            if (int rc = apply_precond(h, nullptr, h->z, L)) return rc;
+            if (int rc = apply_precond(h, balanced ? h->q : nullptr, h->z, L)) return rc;
         }
         phase_mark(h, DOTMI_T_BACKSOLVE);
         launch_build_p(n, h->z, L, h->partC, xi, h->p, h->st);

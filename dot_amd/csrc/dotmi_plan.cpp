@@ -670,6 +670,30 @@ int dotmi_plan_coarse(int32_t nV, int32_t nT, const int32_t *T, const int32_t *e
     return 0;
 }
 
+// host-only: the lists of W = H Z for the balanced coarse term (dotmi_set_dot_coarse_mode, mode 2).  sizes[2] = {(vertex, subdomain) entries,
+// H blocks over all entries} always; the arrays (any may be NULL) as in coarse_plan.hpp (CoarseHzPlan)
+int dotmi_plan_coarse_hz(int32_t nV, int32_t nT, const int32_t *T, const int32_t *epart, int32_t nParts, int32_t *sizes, int32_t *hzPtr,
+                         int32_t *hzSub, int32_t *hzVert, int32_t *hzBlkPtr, int32_t *hzBlk, int32_t *hzTPtr, int32_t *hzTEnt)
+{
+    if (nV < 1 || nT < 1 || !T || !epart || !sizes || nParts < 1 || nParts > COARSE_MAX_PARTS || !mesh_is_valid(nV, nT, T, epart, nParts))
+        return DOTMI_E_INVALID;
+    const MeshGraph G = mesh_graph(nV, nT, T, nullptr);
+    CoarsePlan P;
+    coarse_plan(nV, nT, T, epart, nParts, G.adj_ptr, G.adj_idx, P);
+    CoarseHzPlan Z;
+    coarse_hz_plan(nV, nParts, P.vsPtr, P.vsIdx, G.adj_ptr, G.adj_idx, Z);
+    const int32_t n[2] = {(int32_t)Z.hzSub.size(), (int32_t)Z.hzBlk.size()};
+    std::copy(n, n + 2, sizes);
+    out(hzPtr, Z.hzPtr);
+    out(hzSub, Z.hzSub);
+    out(hzVert, Z.hzVert);
+    out(hzBlkPtr, Z.hzBlkPtr);
+    out(hzBlk, Z.hzBlk);
+    out(hzTPtr, Z.hzTPtr);
+    out(hzTEnt, Z.hzTEnt);
+    return 0;
+}
+
 // host-only: the scalar layout's padded size and the bytes one application of L^-1 reads from the factor
 int dotmi_plan_pd(int32_t nV, int32_t nT, const int32_t *T, const double *Xrest, int32_t *padded, int64_t *apply_bytes)
 {

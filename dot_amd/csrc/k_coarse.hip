@@ -16,6 +16,9 @@
 //                       the iteration all-reduces (zeros for the others' subdomains), the solve on every rank behind that collective,
 //                       the prolongation in zfinish_kernel<DEV, true> / the zsum branch of merge_tiles_early_kernel<NT, true>; with a
 //                       sharded Hessian coarse_assemble_kernel sums the pairs whose first subdomain the rank owns, zeros elsewhere
+//   the balanced form (dotmi_set_dot_coarse_mode, mode 2): W = H Z as a table of 3 x 6 blocks (coarse_hz_kernel at the build), the deflation
+//                       r - W y1 and the restriction c1 - W^T u around the unchanged block solve (coarse_deflate_kernel,
+//                       coarse_restrict_hz_kernel; further down, with the sequence)
 // Every sum has a fixed shape -- a thread's entries in list order, the lanes by wave_sum's tree, the four waves pairwise -- and
 // nothing is added atomically: two builds and two applications are bit-identical.  The reference has no counterpart.
 #include "k_device.hpp"
@@ -144,12 +147,11 @@ __global__ __launch_bounds__(256) void coarse_fill_kernel(int nc, int ncp, int n
 }
 
 // c_s = Z_s^T r: the three sums of w_v r_v and of w_v (x_v - c_s) x r_v over the vertices of s
-__global__ __launch_bounds__(256) void coarse_restrict_kernel(const int *__restrict__ svPtr, const int *__restrict__ svIdx,
-                                                              const double *__restrict__ wgt, const double *__restrict__ x,
-                                                              const double *__restrict__ cen, const int *__restrict__ live,
-                                                              const double *__restrict__ r, double *__restrict__ c)
+__device__ __forceinline__ void coarse_restrict_body(const int *__restrict__ svPtr, const int *__restrict__ svIdx,
+                                                     const double *__restrict__ wgt, const double *__restrict__ x,
+                                                     const double *__restrict__ cen, const int *__restrict__ live,
+                                                     const double *__restrict__ r, double *__restrict__ c, double *sm)
 {
-    __shared__ double sm[5 * 6];
     const int s = blockIdx.x;
     double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (live[s]) {
@@ -170,6 +172,26 @@ __global__ __launch_bounds__(256) void coarse_restrict_kernel(const int *__restr
     }
     coarse_block_sum<6>(acc, sm);
     if (threadIdx.x < 6) c[6 * s + threadIdx.x] = sm[4 * 6 + threadIdx.x];
+}
+__global__ __launch_bounds__(256) void coarse_restrict_kernel(const int *__restrict__ svPtr, const int *__restrict__ svIdx,
+                                                              const double *__restrict__ wgt, const double *__restrict__ x,
+                                                              const double *__restrict__ cen, const int *__restrict__ live,
+                                                              const double *__restrict__ r, double *__restrict__ c)
+{
+    __shared__ double sm[5 * 6];
+    coarse_restrict_body(svPtr, svIdx, wgt, x, cen, live, r, c, sm);
+}
+// the same restriction as a kernel of the device-resident loop (dotmi_set_dot_coarse_mode, mode 2, the q-based order): gated like
+// coarse_solve_loop_kernel with spec == 0 -- past the end of the loop and in a line-search retry it returns at once
+__global__ __launch_bounds__(256) void coarse_restrict_loop_kernel(const int *__restrict__ svPtr, const int *__restrict__ svIdx,
+                                                                   const double *__restrict__ wgt, const double *__restrict__ x,
+                                                                   const double *__restrict__ cen, const int *__restrict__ live,
+                                                                   const double *__restrict__ r, double *__restrict__ c,
+                                                                   const DevLoop *__restrict__ ctl)
+{
+    __shared__ double sm[5 * 6];
+    if (ctl->status != 0 || ctl->phase != 0) return;
+    coarse_restrict_body(svPtr, svIdx, wgt, x, cen, live, r, c, sm);
 }
 
 // y = X^T (X c) = sum_r X[r, :]^T (X[r, :] . c) on the nc live rows of the lower-triangular X (leading dimension ld): workgroup g
@@ -332,6 +354,131 @@ __global__ __launch_bounds__(256) void coarse_prolong_kernel(int nV, int nc, int
     zsum[3 * v + 2] += sc * a2;
 }
 
+// ---- the balanced form (dotmi_set_dot_coarse_mode, mode 2):  M'' = C + (I - C H) M (I - H C),  C = Z A0^-1 Z^T ----------------------------
+// W = H Z is kept as a table of 3 x 6 blocks, one per (vertex i, subdomain t) that an H block (i, j), j in t, couples (coarse_plan.hpp,
+// CoarseHzPlan), so that neither correction multiplies by H:
+//     y1 = A0^-1 Z^T r,   r1 = r - W y1,   u = M r1 (the unchanged block solve and merge),   M'' r = u + Z A0^-1 (Z^T r - W^T u).
+// (The second coarse solve runs on the difference of the two restrictions: y1 - y2 = A0^-1 (c1 - c2) is then what the existing
+// prolongation of the sharded merge, zfinish_kernel<DEV, true>, adds behind the division by the multiplicity and in front of the
+// y_i . z sums -- those sums must see the corrected vector.)
+//   once per build:     coarse_hz_kernel behind the centroids
+//   per application:    coarse_restrict_kernel, coarse_solve_kernel, coarse_deflate_kernel | block solve, merge without the division |
+//                       coarse_restrict_hz_kernel, coarse_solve_kernel, zfinish_kernel<DEV, true> (k_loopvec.hip)
+// DEV: the twins of the device-resident loop, gated like coarse_solve_loop_kernel in the q-based order (spec == 0).
+
+// W[i, t] = sum over the entry's H blocks (i, j), j in t, in list order of H_ij w_j [ I | -[x_j - c_t]x ]: 18 doubles per entry,
+// row-major 3 x 6 (the rows of coarse_assemble_kernel's `top`).  Zero for a dropped subdomain; a fixed vertex's row of H is the
+// identity on a vertex of weight zero, so its blocks come out zero by themselves.  A thread per entry
+__global__ __launch_bounds__(256) void coarse_hz_kernel(int nHz, const int *__restrict__ hzVert, const int *__restrict__ hzSub,
+                                                        const int *__restrict__ hzBlkPtr, const int *__restrict__ hzBlk,
+                                                        const int *__restrict__ adj_idx, const double *__restrict__ Hval,
+                                                        const double *__restrict__ wgt, const double *__restrict__ x,
+                                                        const double *__restrict__ cen, const int *__restrict__ live,
+                                                        double *__restrict__ hz)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= nHz) return;
+    const int t = hzSub[e];
+    double acc[18];
+#pragma unroll
+    for (int k = 0; k < 18; ++k) acc[k] = 0.0;
+    if (live[t]) {
+        const double ct0 = cen[3 * t], ct1 = cen[3 * t + 1], ct2 = cen[3 * t + 2];
+        for (int b = hzBlkPtr[e]; b < hzBlkPtr[e + 1]; ++b) {
+            const int blk = hzBlk[b];
+            const int j = adj_idx[blk];
+            const double w = wgt[j];
+            if (w == 0.0) continue;   // a fixed column vertex: a zero row of Z
+            double h[9];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) h[k] = Hval[hval_idx(blk, k)];
+            const double b0 = x[3 * j] - ct0, b1 = x[3 * j + 1] - ct1, b2 = x[3 * j + 2] - ct2;
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                acc[6 * r] += w * h[3 * r];
+                acc[6 * r + 1] += w * h[3 * r + 1];
+                acc[6 * r + 2] += w * h[3 * r + 2];
+                acc[6 * r + 3] += w * (h[3 * r + 2] * b1 - h[3 * r + 1] * b2);
+                acc[6 * r + 4] += w * (h[3 * r] * b2 - h[3 * r + 2] * b0);
+                acc[6 * r + 5] += w * (h[3 * r + 1] * b0 - h[3 * r] * b1);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 18; ++k) hz[(size_t)18 * e + k] = acc[k];
+}
+
+// y from the row blocks' parts in ascending block order (coarse_prolong_kernel's prologue), by every workgroup alike
+__device__ __forceinline__ void coarse_sum_y(int nc, int ld, const double *__restrict__ ypart, double *y)
+{
+    const int G = (nc + 63) / 64;
+    for (int k = threadIdx.x; k < nc; k += 256) {
+        double a = 0.0;
+        for (int g = k >> 6; g < G; ++g) a += ypart[(size_t)g * ld + k];
+        y[k] = a;
+    }
+    __syncthreads();
+}
+
+// r1 = r - W y: a thread per scalar dof, the vertex's entries in list order (subdomains ascending), the six products of an entry
+// left to right
+template <bool DEV>
+__global__ __launch_bounds__(256) void coarse_deflate_kernel(int n, int nc, int ld, const int *__restrict__ hzPtr,
+                                                             const int *__restrict__ hzSub, const double *__restrict__ hz,
+                                                             const double *__restrict__ ypart, const double *__restrict__ r,
+                                                             double *__restrict__ r1, const DevLoop *__restrict__ ctl)
+{
+    __shared__ double y[COARSE_NC_MAX];
+    if constexpr (DEV) {
+        if (ctl->status != 0 || ctl->phase != 0) return;
+    }
+    coarse_sum_y(nc, ld, ypart, y);
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    const int v = k / 3, dd = k - 3 * v;
+    double a = 0.0;
+    for (int e = hzPtr[v]; e < hzPtr[v + 1]; ++e) {
+        const double *row = hz + (size_t)18 * e + 6 * dd;
+        const double *ys = y + 6 * hzSub[e];
+        a += ((row[0] * ys[0] + row[1] * ys[1]) + (row[2] * ys[2] + row[3] * ys[3])) + (row[4] * ys[4] + row[5] * ys[5]);
+    }
+    r1[k] = r[k] - a;
+}
+
+// cd_t = c_t - (W^T u)_t with u_v = zsum_v / dup_v, the division as the merge makes it: one workgroup per subdomain over its entries
+// in ascending vertex (the transposed index), the lanes by wave_sum's tree, the four waves pairwise.  c: Z^T r of the same
+// application (coarse_restrict_kernel), so that the second solve gives y1 - y2
+template <bool DEV>
+__global__ __launch_bounds__(256) void coarse_restrict_hz_kernel(const int *__restrict__ hzTPtr, const int *__restrict__ hzTEnt,
+                                                                 const int *__restrict__ hzVert, const double *__restrict__ hz,
+                                                                 const int *__restrict__ dup, const double *__restrict__ zsum,
+                                                                 const double *__restrict__ c, double *__restrict__ cd,
+                                                                 const DevLoop *__restrict__ ctl)
+{
+    __shared__ double sm[5 * 6];
+    if constexpr (DEV) {
+        if (ctl->status != 0 || ctl->phase != 0) return;
+    }
+    const int t = blockIdx.x;
+    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int k = hzTPtr[t] + threadIdx.x; k < hzTPtr[t + 1]; k += 256) {
+        const int e = hzTEnt[k];
+        const int v = hzVert[e];
+        const int d = dup[v];
+        double u0 = zsum[3 * v], u1 = zsum[3 * v + 1], u2 = zsum[3 * v + 2];
+        if (d > 1) {
+            u0 /= d;
+            u1 /= d;
+            u2 /= d;
+        }
+        const double *w = hz + (size_t)18 * e;
+#pragma unroll
+        for (int a = 0; a < 6; ++a) acc[a] += (w[a] * u0 + w[6 + a] * u1) + w[12 + a] * u2;
+    }
+    coarse_block_sum<6>(acc, sm);
+    if (threadIdx.x < 6) cd[6 * t + threadIdx.x] = c[6 * t + threadIdx.x] - sm[4 * 6 + threadIdx.x];
+}
+
 // out = a (.) isd per vertex (dotmi_pcg_apply_precond: the two scalings around the block solve that the solve's kernels do on the fly)
 __global__ __launch_bounds__(256) void coarse_scale_kernel(int n, const double *__restrict__ a, const double *__restrict__ isd,
                                                            double *__restrict__ out)
@@ -392,6 +539,37 @@ void launch_coarse_solve_loop(const DevCoarse &C, hipStream_t st, const DevLoop 
 {
     hipLaunchKernelGGL(coarse_solve_loop_kernel, dim3((C.nc + 63) / 64), dim3(256), 0, st, C.nc, C.ncp, (const double *)C.W,
                        c ? c : (const double *)C.c, C.y, ctl, spec);
+}
+void launch_coarse_restrict_loop(const DevCoarse &C, const double *r, hipStream_t st, const DevLoop *ctl)
+{
+    hipLaunchKernelGGL(coarse_restrict_loop_kernel, dim3(C.nParts), dim3(256), 0, st, (const int *)C.svPtr, (const int *)C.svIdx,
+                       (const double *)C.wgt, (const double *)C.xf, (const double *)C.cen, (const int *)C.live, r, C.c, ctl);
+}
+void launch_coarse_hz(const DevCoarse &C, const DevMesh &M, const double *Hval, hipStream_t st)
+{
+    if (C.nHz == 0) return;
+    hipLaunchKernelGGL(coarse_hz_kernel, dim3((C.nHz + 255) / 256), dim3(256), 0, st, C.nHz, (const int *)C.hzVert, (const int *)C.hzSub,
+                       (const int *)C.hzBlkPtr, (const int *)C.hzBlk, (const int *)M.adj_idx, Hval, (const double *)C.wgt,
+                       (const double *)C.xf, (const double *)C.cen, (const int *)C.live, C.hz);
+}
+void launch_coarse_deflate(const DevCoarse &C, int n, const double *r, double *r1, hipStream_t st, const DevLoop *ctl)
+{
+    const dim3 grid((n + 255) / 256);
+    if (ctl)
+        hipLaunchKernelGGL(coarse_deflate_kernel<true>, grid, dim3(256), 0, st, n, C.nc, C.ncp, (const int *)C.hzPtr, (const int *)C.hzSub,
+                           (const double *)C.hz, (const double *)C.y, r, r1, ctl);
+    else
+        hipLaunchKernelGGL(coarse_deflate_kernel<false>, grid, dim3(256), 0, st, n, C.nc, C.ncp, (const int *)C.hzPtr, (const int *)C.hzSub,
+                           (const double *)C.hz, (const double *)C.y, r, r1, ctl);
+}
+void launch_coarse_restrict_hz(const DevCoarse &C, const int *dup, const double *zsum, hipStream_t st, const DevLoop *ctl)
+{
+    if (ctl)
+        hipLaunchKernelGGL(coarse_restrict_hz_kernel<true>, dim3(C.nParts), dim3(256), 0, st, (const int *)C.hzTPtr, (const int *)C.hzTEnt,
+                           (const int *)C.hzVert, (const double *)C.hz, dup, zsum, (const double *)C.c, C.cd, ctl);
+    else
+        hipLaunchKernelGGL(coarse_restrict_hz_kernel<false>, dim3(C.nParts), dim3(256), 0, st, (const int *)C.hzTPtr, (const int *)C.hzTEnt,
+                           (const int *)C.hzVert, (const double *)C.hz, dup, zsum, (const double *)C.c, C.cd, ctl);
 }
 void launch_coarse_scale(int n, const double *a, const double *isd, double *out, hipStream_t st)
 {

@@ -286,6 +286,18 @@ void check_mesh(Mesh &M, int nParts)
         std::snprintf(line, sizeof line, "%d pairs, %d entries, %d incidences", (int)s[0], (int)s[1], (int)s[2]);
         say(E);
     }
+    {   // dotmi_plan_coarse_hz
+        int32_t s[2];
+        const char *E = "dotmi_plan_coarse_hz";
+        expect(E, "sizes", dotmi_plan_coarse_hz(nV, nT, T, ep, nParts, s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), 0);
+        I32 hzPtr(nV + 1), hzSub(s[0]), hzVert(s[0]), hzBlkPtr(s[0] + 1), hzBlk(s[1]), hzTPtr(nParts + 1), hzTEnt(s[0]);
+        expect(E, "arrays", dotmi_plan_coarse_hz(nV, nT, T, ep, nParts, s, hzPtr, hzSub, hzVert, hzBlkPtr, hzBlk, hzTPtr, hzTEnt), 0);
+        invalid(E, dotmi_plan_coarse_hz(nV, nT, T, ep, 257, s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+        invalid(E, dotmi_plan_coarse_hz(nV, nT, T, ep, nParts - 1, s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+        invalid(E, dotmi_plan_coarse_hz(nV, nT, T, ep, nParts, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+        std::snprintf(line, sizeof line, "%d entries, %d blocks", (int)s[0], (int)s[1]);
+        say(E);
+    }
     {   // dotmi_plan_pd
         int32_t padded = 0;
         int64_t bytes = 0;

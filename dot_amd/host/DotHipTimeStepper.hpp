@@ -65,7 +65,8 @@ struct Options {  // the Config fields the DOT stepper reads (src/Config.hpp)
     // the rigid-mode coarse term of those solves' preconditioner (dotmi_set_pcg_coarse): off by default
     bool pcgCoarse = false;
     // the same term in DOT's own block preconditioner, M' = M + Z A0^-1 Z^T (dotmi_set_dot_coarse): off by default
-    bool dotCoarse = false;
+    // (an int: 0 off, 1 the additive form, 2 the balanced form M'' = C + (I - C H) M (I - H C), C = Z A0^-1 Z^T; `true` is mode 1)
+    int dotCoarse = 0;
 };
 
 class DotHipTimeStepper {
@@ -139,14 +140,16 @@ public:
                                      std::to_string(rc) + ")");
         if (opt_.newtonPCG || opt_.newtonPCGDist) check(dotmi_set_pcg(h_, opt_.pcgRelTol, opt_.pcgMaxIter, opt_.pcgCheckEvery), "set_pcg");
         if (opt_.pcgCoarse) check(dotmi_set_pcg_coarse(h_, 1), "set_pcg_coarse");
-        if (opt_.dotCoarse) check(dotmi_set_dot_coarse(h_, 1), "set_dot_coarse");
+        if (opt_.dotCoarse == 2) check(dotmi_set_dot_coarse_mode(h_, 2), "set_dot_coarse_mode");
+        else if (opt_.dotCoarse) check(dotmi_set_dot_coarse(h_, opt_.dotCoarse), "set_dot_coarse");
     }
-    // the coarse term of DOT's block preconditioner on a built stepper: 0 off, 1 rigid modes (dotmi_set_dot_coarse)
+    // the coarse term of DOT's block preconditioner on a built stepper: 0 off, 1 rigid modes, 2 rigid modes balanced (dotmi_set_dot_coarse_mode)
     void setDotCoarse(int mode)
     {
         require_built("setDotCoarse");
-        check(dotmi_set_dot_coarse(h_, mode), "set_dot_coarse");
-        opt_.dotCoarse = mode != 0;
+        if (mode == 2) check(dotmi_set_dot_coarse_mode(h_, mode), "set_dot_coarse_mode");
+        else check(dotmi_set_dot_coarse(h_, mode), "set_dot_coarse");
+        opt_.dotCoarse = mode;
     }
     // the coarse term of the PCG's preconditioner on a built stepper: 0 off, 1 rigid modes (dotmi_set_pcg_coarse)
     void setPCGCoarse(int mode)

@@ -15,7 +15,7 @@
 //
 // usage: dot_hip 100 <script.txt> [--mesh-root DIR] [--parts N] [--energy FCR|SNH] [--epart raw.i32]
 //                [--frames K] [--out DIR] [--device D] [--no-files] [--dump-scene K] [--dump-config] [--dump-formats DIR]
-//                [--echo-config FILE] [--fast] [--newton-pcg N [--pcg-coarse]] [--dot-coarse] [--snh-log]
+//                [--echo-config FILE] [--fast] [--newton-pcg N [--pcg-coarse]] [--dot-coarse | --dot-coarse-balanced] [--snh-log]
 //        dot_hip --write-info FILE nV nT steps iters t0..t21
 #include <algorithm>
 #include <chrono>
@@ -48,7 +48,7 @@ int main(int argc, char **argv)
     }
     if (argc < 3) {
         std::fprintf(stderr, "usage: %s 100 <script.txt> [--mesh-root DIR] [--parts N] [--energy FCR|SNH] "
-                             "[--epart raw.i32] [--frames K] [--out DIR] [--device D] [--no-files] [--dump-scene K] [--dump-config] [--dump-formats DIR] [--fast] [--newton-pcg N [--pcg-coarse]] [--dot-coarse] [--snh-log]\n", argv[0]);
+                             "[--epart raw.i32] [--frames K] [--out DIR] [--device D] [--no-files] [--dump-scene K] [--dump-config] [--dump-formats DIR] [--fast] [--newton-pcg N [--pcg-coarse]] [--dot-coarse | --dot-coarse-balanced] [--snh-log]\n", argv[0]);
         return 2;
     }
     if (std::string(argv[1]) != "100") {
@@ -58,7 +58,8 @@ int main(int argc, char **argv)
     const std::string scriptPath = argv[2];
     std::string meshRoot = ".", outDir, epartFile, energyOverride;
     int partsOverride = -1, frames = -1, device = 0, dumpScene = -1, newtonPcgParts = 0;
-    bool files = true, dumpConfig = false, fast = false, pcgCoarse = false, dotCoarse = false, snhLog = false;
+    bool files = true, dumpConfig = false, fast = false, pcgCoarse = false, snhLog = false;
+    int dotCoarse = 0;   // --dot-coarse: 1, --dot-coarse-balanced: 2 (the mode of dotmi_set_dot_coarse_mode)
     std::string dumpFormats, echoConfig;
     for (int i = 3; i < argc; ++i) {
         const std::string a = argv[i];
@@ -82,7 +83,9 @@ int main(int argc, char **argv)
         // ... with the rigid-mode coarse term in the solves' preconditioner (dotmi_set_pcg_coarse; at most 256 subdomains)
         else if (a == "--pcg-coarse") pcgCoarse = true;
         // `timeStepper DOT` scripts: the rigid-mode coarse term in DOT's own block preconditioner (dotmi_set_dot_coarse)
-        else if (a == "--dot-coarse") dotCoarse = true;
+        else if (a == "--dot-coarse") dotCoarse = 1;
+        // the same coarse space projected out on both sides of the block solve, M'' = C + (I - C H) M (I - H C) (mode 2)
+        else if (a == "--dot-coarse-balanced") dotCoarse = 2;
         // `energy SNH` scripts: the log-regularised form of the material (DOTMI_ENERGY_SNH_LOG), what a reference build with
         // SNH_WITHLOG runs for the same script.  The reference chooses it at compile time, so it is no script token and
         // config.txt keeps echoing `energy SNH`
@@ -325,8 +328,8 @@ int main(int argc, char **argv)
             double ms = 0;
             if (dotmi_dot_coarse_info(ts.handle(), &dim, &dropped, &active, &builds, &ms) != 0)
                 throw std::runtime_error("dotmi_dot_coarse_info failed");
-            std::printf("DOT coarse space: dimension %d, %d dropped, active %d, %lld builds, last build %.3f ms\n", dim, dropped, active,
-                        (long long)builds, ms);
+            std::printf("DOT coarse space: dimension %d, %d dropped, active %d, %lld builds, last build %.3f ms%s\n", dim, dropped, active,
+                        (long long)builds, ms, dotmi_dot_coarse_mode(ts.handle()) == 2 ? ", balanced" : "");
         }
         if (files) {
             timers.descent = tStep;

@@ -86,7 +86,7 @@ EXPORTS = [
     "dotmi_set_rel_tol", "dotmi_set_time_step", "dotmi_set_lame",
     "dotmi_solve_hessian", "dotmi_set_pcg", "dotmi_pcg_info",
     "dotmi_set_pcg_coarse", "dotmi_pcg_coarse_info", "dotmi_pcg_coarse_matrix", "dotmi_pcg_apply_precond", "dotmi_plan_coarse",
-    "dotmi_set_dot_coarse", "dotmi_dot_coarse_info",
+    "dotmi_set_dot_coarse", "dotmi_dot_coarse_info", "dotmi_set_dot_coarse_mode", "dotmi_dot_coarse_mode", "dotmi_plan_coarse_hz",
 ]
 
 _lib = None
@@ -183,6 +183,11 @@ def load() -> C.CDLL:
     if hasattr(L, "dotmi_set_dot_coarse"):
         L.dotmi_set_dot_coarse.argtypes = [H, C.c_int32]
         L.dotmi_dot_coarse_info.argtypes = [H, c_ip, c_ip, c_ip, C.POINTER(C.c_int64), c_dp]
+    if hasattr(L, "dotmi_dot_coarse_mode"):   # (guarded like the ones around it: a DOTMI_LIBRARY build from before mode 2)
+        L.dotmi_set_dot_coarse_mode.argtypes = [H, C.c_int32]
+        L.dotmi_dot_coarse_mode.argtypes = [H]
+        L.dotmi_dot_coarse_mode.restype = C.c_int32
+        L.dotmi_plan_coarse_hz.argtypes = [C.c_int32, C.c_int32, c_ip, c_ip, C.c_int32] + [c_ip] * 8
     L.dotmi_plan_layout.argtypes = [C.c_int32, C.c_int32, c_ip, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32,
                                     C.c_int32, C.c_int32, C.c_int32, c_ip, c_ip, c_ip, c_ip]
     if hasattr(L, "dotmi_plan_backsolve_tiles"):   # (round 5 entry; guarded like the two above -- ADVICE r05)

@@ -340,6 +340,15 @@ class DOTTimeStepper:
         (dotmi_set_dot_coarse).  step(), applyPrecond() and probeDirection() then use M'; A0 is built behind every refresh of H."""
         self._check(self._L.dotmi_set_dot_coarse(self._h, mode), "set_dot_coarse")
 
+    def setDotCoarseMode(self, mode: int):
+        """the same term by mode: 0 off, 1 additive (as setDotCoarse(1)), 2 balanced, M'' = C + (I - C H) M (I - H C) with
+        C = Z A0^-1 Z^T (dotmi_set_dot_coarse_mode).  In mode 2 W = H Z is rebuilt with A0 behind every refresh of H."""
+        self._check(self._L.dotmi_set_dot_coarse_mode(self._h, mode), "set_dot_coarse_mode")
+
+    def dotCoarseMode(self) -> int:
+        """0, 1 or 2: what setDotCoarse / setDotCoarseMode (or FLAG_DOT_COARSE) has left on the handle (dotmi_dot_coarse_mode)"""
+        return int(self._L.dotmi_dot_coarse_mode(self._h))
+
     def dotCoarseInfo(self):
         """(dimension 6 nParts, subdomains the last build dropped, active, coarse builds since create, ms of the last build)
         (dotmi_dot_coarse_info)"""

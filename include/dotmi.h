@@ -565,8 +565,25 @@ int dotmi_pcg_apply_precond(dotmi_handle *h, const double *r, double *w);
  * successful build: the step runs on M, the handle is not poisoned.  A step with the mode on does not take the unit step
  * speculatively (DOTMI_SPEC_STEP).  DOTMI_E_INVALID with a message on a handle of more than one rank, with DOTMI_FLAG_FORCE_DIST,
  * _OWNER_EXCHANGE, _GSDD, _NEWTON, _NEWTON_PCG, _LBFGS_PD, _LBFGS_HI or _ASYNC_REFRESH, on a vpart handle, for any other mode, and
- * above 256 subdomains.  (A sharded handle takes the term at create: DOTMI_FLAG_DOT_COARSE.) */
+ * above 256 subdomains.  (A sharded handle takes the term at create: DOTMI_FLAG_DOT_COARSE.)  This entry takes 0 and 1 and refuses
+ * every other value as it always has; the balanced form is mode 2 of dotmi_set_dot_coarse_mode below. */
 int dotmi_set_dot_coarse(dotmi_handle *h, int32_t mode);
+/* The coarse term of DOT's own loop by mode (new with this library: the reference has no counterpart, so iteration counts differ from
+ * its: opt-in).  mode 0 and mode 1 are dotmi_set_dot_coarse(h, 0 / 1) exactly -- one handle state behind both entries.
+ * mode 2 = the balanced form: the same Z and A0 project the coarse space out on both sides of the block solve,
+ *     M'' = C + (I - C H) M (I - H C),   C = Z A0^-1 Z^T,
+ * applied as  y1 = A0^-1 Z^T r,  r1 = r - W y1,  u = M r1,  y2 = A0^-1 W^T u,  M'' r = u + Z (y1 - y2)  with W = H Z kept as a sparse
+ * table of 3 x 6 blocks that is rebuilt with A0 -- no product with H per application.  M'' H Z y = Z y: the coarse space is solved
+ * exactly.  Six small launches per application around the unchanged block solve; a step with mode 2 active runs the device loop in
+ * its q-based order (the early order forms z inside its merge, before y2 exists).  It about halves mode 1's iterations where the
+ * rigid modes carry the error (bars), gains little on stiff meshes and costs more per iteration
+ * (profiles/dot_coarse_balanced.txt).  Refused (DOTMI_E_INVALID with a message) where dotmi_set_dot_coarse is, which includes every
+ * sharded handle (DOTMI_FLAG_DOT_COARSE stays mode 1), and for any value other than 0, 1, 2.  Switching on a live handle follows one
+ * rule: a switch from 0 builds A0 (and W for mode 2) now, 1 -> 2 builds W with a fresh A0, 2 -> 1 keeps the build.
+ * (The mode has an entry of its own because dotmi_set_dot_coarse has refused the value 2 since it exists and callers may rely on it.) */
+int dotmi_set_dot_coarse_mode(dotmi_handle *h, int32_t mode);
+/* the mode the two setters (or DOTMI_FLAG_DOT_COARSE) have left on the handle: 0, 1 or 2 (0 for NULL) */
+int32_t dotmi_dot_coarse_mode(const dotmi_handle *h);
 /* *dim = 6 nParts with the mode on, else 0; the subdomains the last build dropped; *active = 1 when the applications add the coarse
  * term; the coarse builds since create (both modes); the device time of the last one in ms.  Any pointer may be NULL. */
 int dotmi_dot_coarse_info(const dotmi_handle *h, int32_t *dim, int32_t *dropped_subdomains, int32_t *active, int64_t *builds,
@@ -581,6 +598,13 @@ int dotmi_dot_coarse_info(const dotmi_handle *h, int32_t *dim, int32_t *dropped_
 int dotmi_plan_coarse(int32_t nV, int32_t nT, const int32_t *T, const int32_t *epart, int32_t nParts, int32_t *sizes, int32_t *pairS,
                       int32_t *pairT, int32_t *pairPtr, int32_t *pairBlk, int32_t *vsPtr, int32_t *vsIdx, int32_t *svPtr,
                       int32_t *svIdx);
+/* (host only) the lists of W = H Z for mode 2 of dotmi_set_dot_coarse_mode (coarse_plan.hpp, CoarseHzPlan), same mesh arguments.
+ * sizes[2] = {entries nE, H blocks nB}; call with NULL arrays first.  An entry is a (vertex i, subdomain t) with an H block (i, j),
+ * j in t.  hzPtr[nV + 1] / hzSub[nE]: per vertex the subdomains of its entries, ascending; hzVert[nE]: an entry's vertex;
+ * hzBlkPtr[nE + 1] / hzBlk[nB]: per entry its H blocks as indices into the global block-CSR, ascending (the summation order of
+ * W[i, t]); hzTPtr[nParts + 1] / hzTEnt[nE]: per subdomain its entries in ascending vertex.  Any array may be NULL. */
+int dotmi_plan_coarse_hz(int32_t nV, int32_t nT, const int32_t *T, const int32_t *epart, int32_t nParts, int32_t *sizes, int32_t *hzPtr,
+                         int32_t *hzSub, int32_t *hzVert, int32_t *hzBlkPtr, int32_t *hzBlk, int32_t *hzTPtr, int32_t *hzTEnt);
 
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* Launch the subdomain back-solve kernel `reps` times on the handle's stream between two HIP events

@@ -4,8 +4,10 @@
                                                                           in one process: iterations and halvings per step, ms per
                                                                           step and us per iteration over steps 2..N, the coarse
                                                                           build beside ms_factor
-  python tools/dot_coarse_measure.py kernels <workload> <mode> [frames]   the same steps with the mode 0 / 1, to run under
+  python tools/dot_coarse_measure.py kernels <workload> <mode> [frames]   the same steps with the mode 0 / 1 / 2, to run under
                                                                           `rocprofv3 --kernel-trace --stats`
+  python tools/dot_coarse_measure.py balanced <workload> [frames] [reps]  `steps` with the modes 0 / 1 / 2 alternating (mode 2: the
+                                                                          balanced form; profiles/dot_coarse_balanced.txt)
   python tools/dot_coarse_measure.py sharded <workload> [frames] [reps] [off]
                                                                           `steps` on one rank under DOTMI_FLAG_FORCE_DIST, without and
                                                                           with DOTMI_FLAG_DOT_COARSE (profiles/dot_coarse_sharded.txt);
@@ -25,10 +27,10 @@ from dot_amd.workloads import load_workload  # noqa: E402
 
 def run(name, mode, frames, sharded=False):
     sc, ep, n = load_workload(name)
-    print(f"  ... {name}: a handle with the coarse term {'on' if mode else 'off'}", file=sys.stderr, flush=True)
+    print(f"  ... {name}: a handle with the coarse term {('off', 'on', 'balanced')[mode]}", file=sys.stderr, flush=True)
     ts = DOTTimeStepper(sc, ep, n, flags=(dl.FLAG_FORCE_DIST | (dl.FLAG_DOT_COARSE if mode else 0)) if sharded else 0)
     if mode and not sharded:
-        ts.setDotCoarse(1)
+        ts.setDotCoarseMode(mode) if mode == 2 else ts.setDotCoarse(mode)
     rows = []
     for _ in range(frames):
         idx, pos = sc.scripter.step(ts.getResult(), sc.cfg.dt)
@@ -54,6 +56,8 @@ def main():
     reps = int(sys.argv[4]) if len(sys.argv) > 4 else 3
     sharded = what == "sharded"
     modes = (0, 1) if has and not (sharded and "off" in sys.argv[5:]) else (0,)
+    if what == "balanced" and hasattr(dl.load(), "dotmi_dot_coarse_mode"):
+        modes = (0, 1, 2)
     res = {m: [] for m in modes}
     for _ in range(reps):                       # off, on, off, on, ...: the two share whatever else the machine is doing
         for m in modes:
@@ -69,7 +73,7 @@ def main():
         fact = np.median([r[6] for rr in res[m] for r in rr[0][1:]])
         hess = np.median([r[5] for rr in res[m] for r in rr[0][1:]])
         build = np.median([r[7] for rr in res[m] for r in rr[0][1:]])
-        print(f"  coarse {'on ' if m else 'off'}: iterations " + " ".join(f"{r[0]}" + (f"({r[1]})" if r[1] else "") for r in rows0) +
+        print(f"  coarse {('off', 'on ', 'balanced')[m]}: iterations " + " ".join(f"{r[0]}" + (f"({r[1]})" if r[1] else "") for r in rows0) +
               "  status " + " ".join(str(r[2]) for r in rows0) + ("" if same else "  (the runs differ in their counts!)"))
         print("      ms per step (steps 2..N), per run " + " ".join(f"{v:.3f}" for v in per_step) + f"  median {np.median(per_step):.3f}")
         print("      us per iteration (ms_loop / iterations, steps 2..N), per run " + " ".join(f"{v:.1f}" for v in loop_us) +
