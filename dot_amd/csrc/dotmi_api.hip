@@ -22,6 +22,13 @@ int dotmi_set_state(dotmi_handle *h, const double *x, const double *v, const dou
             xt[k] = h->fixed[i] ? xn_h[k] : xn_h[k] + (v[k] * h->dt + h->gdtsq[d]);
         }
     HIPCHECK(h, hipMemcpy(h->xt, xt.data(), bytes, hipMemcpyHostToDevice));
+    // BDF2: a state that was set has no level n-1 -- the next step is a backward-Euler start step at dt (dotmi_set_history gives the
+    // level back); x^ = x_n, and the refresh where that changes the effective step
+    if (h->tit == TIT_BDF2) {
+        h->levels = 0;
+        h->dtPrev = 0.0;
+        return tit_replan(h, false);
+    }
     return 0;
 }
 

@@ -808,6 +808,7 @@ static int take_arguments(dotmi_handle *h, const dotmi_mesh *mesh, const dotmi_p
     h->hist = prm->history;
     h->iterCap = prm->iterCap > 0 ? prm->iterCap : 10000;
     h->dt = prm->dt;
+    h->dtUser = prm->dt;
     h->dtSq = prm->dt * prm->dt;
     for (int d = 0; d < 3; ++d) {
         h->grav[d] = prm->gravity[d];

@@ -5,7 +5,8 @@
 //   dotmi_collectives.hip all-reduce (RCCL or host hook) and the owner exchange's packets
 //   dotmi_loop.hip        dotmi_step, what the loop drivers share (trial, line search, block solve), host loop, GSDD, Newton
 //   dotmi_devloop.hip     the device-resident L-BFGS-H loop: the stages of a slot in both orders, run_device_loop and its parts
-//   dotmi_reconfig.hip    tolerance, time step and materials changed on a live handle (dotmi_set_rel_tol / _time_step / _lame)
+//   dotmi_reconfig.hip    tolerance, time step, materials and the time integration rule changed on a live handle (dotmi_set_rel_tol /
+//                         _time_step / _lame / _time_integration / _history; the rule itself: time_integration.hpp, kernels: k_timeint.hip)
 //   dotmi_pd.hip / dotmi_ic.hip   the preconditioners of LBFGS-PD (scalar Laplacian) and LBFGS-HI (block incomplete Cholesky of H)
 //   dotmi_pcg.hip         Newton-PCG: conjugate gradients on the global H with the block solve (dotmi_solve_hessian, DOTMI_FLAG_NEWTON_PCG)
 //   dotmi_coarse.hip      the rigid-mode coarse space of that PCG's preconditioner (dotmi_set_pcg_coarse; lists: coarse_plan.hpp) and of
@@ -170,6 +171,13 @@ struct dotmi_handle {
     SlotMap smAll, smOwn, smSpec, smVP;
     int nOwnElem = 0, v0 = 0, v1 = 0;
     double *x = nullptr, *x_trial = nullptr, *xn = nullptr, *v = nullptr, *xt = nullptr;
+    // dotmi_set_time_integration (time_integration.hpp): under BDF2 dt, dtSq, gdtsq above keep meaning "what the launches take", the
+    // effective step of the NEXT step; dtUser is the caller's dt, dtPrev the size of the step that led from level n-1 to level n, levels
+    // whether that level exists (0: the next step is a backward-Euler start step).  Backward Euler: dtUser = dt, levels = 0.  The level
+    // n-1 and x^ of the next step are allocated, zeroed, by the first switch to BDF2
+    int tit = TIT_BE, levels = 0;
+    double dtUser = 0, dtPrev = 0;
+    double *xnm1 = nullptr, *vnm1 = nullptr, *xhat = nullptr;
     double *g = nullptr, *g_trial = nullptr, *p = nullptr, *q = nullptr, *z = nullptr, *Hp = nullptr;
     double *He = nullptr, *Hval = nullptr, *tmpn = nullptr;
     double *S[HIST_MAX + 1] = {nullptr}, *Y[HIST_MAX + 1] = {nullptr};
@@ -380,6 +388,9 @@ int refactor(dotmi_handle *h, const double *x, double *ms_hess, double *ms_fact)
 int resolve_refresh(dotmi_handle *h, double *ms_hess = nullptr, double *ms_fact = nullptr);
 int enter_with_factors(dotmi_handle *h);
 int run_factor(dotmi_handle *h);
+// dotmi_reconfig.hip (the time integration switch, time_integration.hpp)
+bool tit_apply(dotmi_handle *h, const TitPlan &p);   // dt, dtSq, gdtsq, targetGRes <- the plan's effective step; true: it changed
+int tit_replan(dotmi_handle *h, bool always);        // between two steps: the plan from the handle's levels, x^ / x~ again, the refresh
 // dotmi_pd.hip (LBFGS-PD)
 int build_pd(dotmi_handle *h, const std::vector<int> &adj_ptr, const std::vector<int> &adj_idx);
 int pd_factor(dotmi_handle *h);

@@ -7,6 +7,7 @@
 #include "merge_sum.hpp"       // MT_PAD
 #include "nd_layout.hpp"
 #include "tile_factor.hpp"
+#include "time_integration.hpp"   // TitPlan
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -622,6 +623,15 @@ void launch_gather_lame(const int *slotElem, size_t nSlots, const double *mu, co
 // x~ = x_n + dt v + dt^2 g on free vertices, x_n on fixed ones (Optimizer::computeXTilta, Optimizer.cpp:585-610), from the resident state
 void launch_x_tilde(int nV, const uint8_t *fixed, const double *xn, const double *v, double dt, const double *gdtsq, double *xt,
                     hipStream_t st);
+// ---- BDF2 (dotmi_set_time_integration; time_integration.hpp, k_timeint.hip): what a step under it launches in place of init_x / be_update ----
+// the step's end: v+ from x and x^ at the effective step that ends, the shift of the two levels, the next step's x^ and x~ by `next`
+void launch_bdf2_update(int nV, const uint8_t *fixed, const double *x, double *xhat, double *xn, double *v, double *xnm1, double *vnm1,
+                        double *xt, double dt_eff_done, const TitPlan &next, const double *gdtsq_next, hipStream_t st);
+// x^ and x~ again from the stored levels (dt, the integrator or the levels changed between two steps)
+void launch_bdf2_predict(int nV, const uint8_t *fixed, const double *xn, const double *v, const double *xnm1,
+                         const double *vnm1, double *xhat, double *xt, const TitPlan &p, const double *gdtsq, hipStream_t st);
+// the start iterate: x = x~ on free vertices
+void launch_bdf2_init_x(int nV, const uint8_t *fixed, const double *xt, double *x, hipStream_t st);
 
 // ---- Newton-PCG (DOTMI_FLAG_NEWTON_PCG, dotmi_solve_hessian; dotmi_pcg.hip / k_pcg.hip): conjugate gradients on H with the block solve ----
 // the scalars of a CG iteration, one record per parity of the iteration (k_pcg.hip)

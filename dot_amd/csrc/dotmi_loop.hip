@@ -492,8 +492,10 @@ int dotmi_step(dotmi_handle *h, dotmi_step_stats *st)
     for (double &v : h->phaseMs) v = 0.0;
     h->evPn = 0;
     phase_mark(h, -1);
-    // initX(2): x += dt v + dt^2 g on free vertices (Optimizer.cpp:442-582)
-    launch_init_x(h->nV, h->M.fixed, h->v, h->dt, h->gdtsq, h->x, h->st);
+    // initX(2): x += dt v + dt^2 g on free vertices (Optimizer.cpp:442-582); BDF2: x = x~, which the last update formed from x^, v^
+    const bool bdf2 = h->tit == TIT_BDF2;
+    if (bdf2) launch_bdf2_init_x(h->nV, h->M.fixed, h->xt, h->x, h->st);
+    else launch_init_x(h->nV, h->M.fixed, h->v, h->dt, h->gdtsq, h->x, h->st);
     LoopOut r;
     if (!h->devLoop) {
         double R[RED_K];
@@ -526,19 +528,30 @@ int dotmi_step(dotmi_handle *h, dotmi_step_stats *st)
     ms_fact += h->carryFact;
     h->carryHess = h->carryFact = 0.0;
 
+    // BDF2: from here on the launches take the NEXT step's effective step -- the refresh below is issued at it.  It changes only at the
+    // hand-over from the backward-Euler start step (dt) to the first BDF2 step (2/3 dt): there a failed step refreshes all the same,
+    // LBFGS-PD factors its L once more below, LBFGS-HI and Newton read the new fields in their own refresh
+    const double dtDone = h->dt;
+    TitPlan next{};
+    bool handOver = false;
+    if (bdf2) {
+        next = tit_plan(TIT_BDF2, h->dtUser, h->dtUser, 1);
+        handOver = tit_apply(h, next);
+        h->levels = 1;
+        h->dtPrev = h->dtUser;
+    }
     // (Newton refreshes at the START of every iteration instead; LBFGS-PD's preconditioner is constant: LBFGSTimeStepper::fullyImplicit
     // refactors only for H, HI and JH, :296-335)
-    const bool refreshAtEnd = !r.failed && !h->newton && !h->pd;
-    if (r.failed) status = 2;
-    else {
-        if (r.it >= h->iterCap) status = 2;
-        // (LBFGS-HI: its refresh takes one read-back per factorisation attempt, so it runs whole behind the BE update below)
-        if (refreshAtEnd && !h->hi)
-            if (int rc = refactor_issue(h, h->x)) return rc;
-    }
-    // BE update (Optimizer.cpp:354-361)
+    const bool refreshAtEnd = (!r.failed || handOver) && !h->newton && !h->pd;
+    if (r.failed || r.it >= h->iterCap) status = 2;
+    // (LBFGS-HI: its refresh takes one read-back per factorisation attempt, so it runs whole behind the BE update below)
+    if (refreshAtEnd && !h->hi)
+        if (int rc = refactor_issue(h, h->x)) return rc;
+    // BE update (Optimizer.cpp:354-361); BDF2: v+ = (x - x^) / dt_e, the shift of the levels, the next step's x^ and x~
     phase_mark(h, -1);
-    launch_be_update(h->nV, h->M.fixed, h->x, h->xn, h->v, h->xt, h->dt, h->gdtsq, h->st);
+    if (bdf2)
+        launch_bdf2_update(h->nV, h->M.fixed, h->x, h->xhat, h->xn, h->v, h->xnm1, h->vnm1, h->xt, dtDone, next, h->gdtsq, h->st);
+    else launch_be_update(h->nV, h->M.fixed, h->x, h->xn, h->v, h->xt, h->dt, h->gdtsq, h->st);
     phase_mark(h, DOTMI_T_SOLVE_EXTRACOMP);
     int rcFactor = 0;
     const bool asyncRefresh = refreshAtEnd && (h->flags & DOTMI_FLAG_ASYNC_REFRESH) && h->devLoop && !h->dist;
@@ -550,6 +563,7 @@ int dotmi_step(dotmi_handle *h, dotmi_step_stats *st)
         phase_collect(h);
         HIPCHECK(h, hipGetLastError());
         if (refreshAtEnd) rcFactor = h->hi ? ic_refresh(h, h->x, &ms_hess, &ms_fact) : refactor_finish(h, &ms_hess, &ms_fact);
+        else if (handOver && h->pd) rcFactor = pd_factor(h);
         if (rcFactor == DOTMI_E_DEVICE) return rcFactor;
     }
     if (st) {

@@ -3,6 +3,7 @@
 // host compiler: no handle, no device, no call into the HIP runtime -- the object links into a program without it (plan_check.cpp
 // does, under the address and undefined-behaviour sanitizers).  Built once and linked into both libraries.
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "../../include/dotmi.h"
@@ -12,6 +13,7 @@
 #include "loop_forms.hpp"
 #include "partition.hpp"
 #include "pd_plan.hpp"
+#include "time_integration.hpp"
 #include "tuning.hpp"
 #include "vpatches.hpp"
 
@@ -135,6 +137,21 @@ int dotmi_plan_loop_forms(int64_t ndof_gather, int64_t ndof_merge, int64_t nrows
 {
     if (ndof_gather < 0 || ndof_merge < 0 || nrows_spmv < 0 || !out) return DOTMI_E_INVALID;
     *out = loop_forms_mask(ndof_gather, ndof_merge, nrows_spmv, force);
+    return 0;
+}
+
+// host-only: the time integration rule of one step (time_integration.hpp: what dotmi_step and the entries of dotmi_reconfig.hip plan with)
+int dotmi_plan_time_integration(int32_t kind, double dt, double dt_prev, int32_t levels, double *c0, double *c1, double *gamma,
+                                double *dt_eff)
+{
+    if (kind != DOTMI_TIT_BE && kind != DOTMI_TIT_BDF2) return DOTMI_E_INVALID;
+    if (!(dt > 0) || !std::isfinite(dt) || levels < 0 || levels > 1) return DOTMI_E_INVALID;
+    if (kind == DOTMI_TIT_BDF2 && levels == 1 && (!(dt_prev > 0) || !std::isfinite(dt_prev))) return DOTMI_E_INVALID;
+    const TitPlan p = tit_plan(kind, dt, dt_prev, levels);
+    if (c0) *c0 = p.c0;
+    if (c1) *c1 = p.c1;
+    if (gamma) *gamma = p.gamma;
+    if (dt_eff) *dt_eff = p.dt_eff;
     return 0;
 }
 

@@ -11,6 +11,11 @@
 // The captured factorisation graph (run_factor) holds tile tasks on fixed buffers and none of these values: it is replayed as it is.
 // The forecasts a step leaves for the next one (pairing, held back-solves, vertex patches) choose among forms with identical
 // iterates; they stay, as they do across dotmi_set_state.
+//
+// The time integration rule (dotmi_set_time_integration, dotmi_set_history; time_integration.hpp) is a fourth such value: under BDF2 the
+// launches take the EFFECTIVE step dt_e = gamma dt of the next step, so whatever changes it between two steps -- the caller's dt, the
+// integrator, the stored level n-1 (dotmi_set_state drops it, dotmi_set_history gives it) -- redoes what dotmi_set_time_step redoes: x^ and
+// x~ from the stored levels and, where dt_e did change, the refresh (tit_replan).
 #include "dotmi_handle.hpp"
 
 namespace dotmi {
@@ -27,6 +32,30 @@ static int refresh_factors(dotmi_handle *h)
 {
     if (h->pd) return pd_factor(h);
     return refactor(h, h->x, nullptr, nullptr);
+}
+
+// the effective step of the next step into what the launches take; true when it changed
+bool tit_apply(dotmi_handle *h, const TitPlan &p)
+{
+    const bool changed = p.dt_eff != h->dt;
+    h->dt = p.dt_eff;
+    h->dtSq = h->dt * h->dt;
+    for (int d = 0; d < 3; ++d) h->gdtsq[d] = h->dtSq * h->grav[d];
+    h->targetGRes = host_target_gres(h);
+    return changed;
+}
+
+// between two steps: the next step's rule from (tit, dtUser, dtPrev, levels), x~ (BDF2: and x^) from the stored levels, and the refresh
+// where the effective step changed (always: whenever the caller's entry refreshes anyway)
+int tit_replan(dotmi_handle *h, bool always)
+{
+    const TitPlan p = tit_plan(h->tit, h->dtUser, h->dtPrev, h->levels);
+    const bool changed = tit_apply(h, p);
+    if (h->tit == TIT_BDF2)
+        launch_bdf2_predict(h->nV, h->M.fixed, h->xn, h->v, h->xnm1, h->vnm1, h->xhat, h->xt, p, h->gdtsq, h->st);
+    else
+        launch_x_tilde(h->nV, h->M.fixed, h->xn, h->v, h->dt, h->gdtsq, h->xt, h->st);
+    return (changed || always) ? refresh_factors(h) : 0;
 }
 
 // one family: the kernel-argument form for one material, else the slot arrays (allocated on first need) filled on the device
@@ -78,12 +107,90 @@ int dotmi_set_time_step(dotmi_handle *h, double dt)
         return DOTMI_E_INVALID;
     }
     if (int rc = enter(h)) return rc;
+    h->dtUser = dt;
+    // BDF2: the variable-step rule, w = dt / dt_prev -- not a restart (Optimizer::setTime leaves the velocity alone, too)
+    if (h->tit == TIT_BDF2) return tit_replan(h, true);
     h->dt = dt;
     h->dtSq = dt * dt;
     for (int d = 0; d < 3; ++d) h->gdtsq[d] = h->dtSq * h->grav[d];
     h->targetGRes = host_target_gres(h);
     launch_x_tilde(h->nV, h->M.fixed, h->xn, h->v, h->dt, h->gdtsq, h->xt, h->st);
     return refresh_factors(h);
+}
+
+// The reference switches on Config::timeIntegrationType at the velocity update (Optimizer.cpp:354-361), the predictor (:588-610), the
+// energy (:1188) and the gradient (:1225); its enum has the one entry TIT_BE.  Here the switch is at the first two only: BDF2's energy and
+// gradient are backward Euler's at the effective step.
+int dotmi_set_time_integration(dotmi_handle *h, int32_t kind)
+{
+    if (!h) return DOTMI_E_INVALID;
+    if (kind != DOTMI_TIT_BE && kind != DOTMI_TIT_BDF2) {
+        h->err = "dotmi_set_time_integration: unknown time integration id " + std::to_string(kind);
+        return DOTMI_E_INVALID;
+    }
+    if (int rc = enter(h)) return rc;
+    if (kind == h->tit) return 0;
+    if (kind == DOTMI_TIT_BDF2 && !h->xnm1) {
+        // zeroed: the start step forms x^ = 1 x_n - 0 x_{n-1}
+        for (double **vec : {&h->xnm1, &h->vnm1, &h->xhat}) {
+            if (int rc = dalloc(h, vec, (size_t)h->n)) return rc;
+            HIPCHECK(h, hipMemsetAsync(*vec, 0, sizeof(double) * h->n, h->st));
+        }
+    }
+    h->tit = kind;
+    h->levels = 0;   // a backward-Euler handle keeps no level n-1: the first BDF2 step is a start step
+    h->dtPrev = 0.0;
+    return tit_replan(h, false);
+}
+
+int32_t dotmi_time_integration(const dotmi_handle *h) { return h ? h->tit : DOTMI_E_INVALID; }
+
+int dotmi_time_integration_info(const dotmi_handle *h, int32_t *kind, int32_t *levels, double *dt_eff, double *dt_prev)
+{
+    if (!h) return DOTMI_E_INVALID;
+    if (kind) *kind = h->tit;
+    if (levels) *levels = h->levels;
+    if (dt_eff) *dt_eff = h->dt;
+    if (dt_prev) *dt_prev = h->levels ? h->dtPrev : 0.0;
+    return 0;
+}
+
+int dotmi_get_history(dotmi_handle *h, double *x_prev, double *v_prev, double *dt_prev)
+{
+    if (!h) return DOTMI_E_INVALID;
+    if (int rc = enter(h); rc == DOTMI_E_DEVICE) return rc;
+    if (dt_prev) *dt_prev = h->levels ? h->dtPrev : 0.0;
+    if (!h->levels) return 0;
+    const size_t bytes = sizeof(double) * h->n;
+    HIPCHECK(h, hipStreamSynchronize(h->st));
+    if (x_prev) HIPCHECK(h, hipMemcpy(x_prev, h->xnm1, bytes, hipMemcpyDeviceToHost));
+    if (v_prev) HIPCHECK(h, hipMemcpy(v_prev, h->vnm1, bytes, hipMemcpyDeviceToHost));
+    return 1;
+}
+
+int dotmi_set_history(dotmi_handle *h, const double *x_prev, const double *v_prev, double dt_prev)
+{
+    if (!h) return DOTMI_E_INVALID;
+    if (!x_prev || !v_prev) {
+        h->err = "dotmi_set_history: x_prev and v_prev must be given";
+        return DOTMI_E_INVALID;
+    }
+    if (!(dt_prev > 0) || !std::isfinite(dt_prev)) {
+        h->err = "dotmi_set_history: dt_prev must be positive and finite";
+        return DOTMI_E_INVALID;
+    }
+    if (h->tit != TIT_BDF2) {
+        h->err = "dotmi_set_history: backward Euler keeps no level n-1 (dotmi_set_time_integration(h, DOTMI_TIT_BDF2) first)";
+        return DOTMI_E_INVALID;
+    }
+    if (int rc = enter(h)) return rc;
+    const size_t bytes = sizeof(double) * h->n;
+    HIPCHECK(h, hipMemcpyAsync(h->xnm1, x_prev, bytes, hipMemcpyHostToDevice, h->st));
+    HIPCHECK(h, hipMemcpyAsync(h->vnm1, v_prev, bytes, hipMemcpyHostToDevice, h->st));
+    HIPCHECK(h, hipStreamSynchronize(h->st));   // (the caller's arrays are free again)
+    h->levels = 1;
+    h->dtPrev = dt_prev;
+    return tit_replan(h, false);
 }
 
 int dotmi_set_lame(dotmi_handle *h, const double *mu, const double *lambda)

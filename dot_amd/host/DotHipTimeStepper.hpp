@@ -13,6 +13,7 @@
 //   getResult().V               getResult             -> dotmi_get_state
 //   getIterNum/getInnerIterAmt  same
 //   updatePrecondMtrAndFactorize same                 -> dotmi_refactor / dotmi_refix
+//   Config::timeIntegrationType Options::timeIntegration / setTimeIntegration -> dotmi_set_time_integration (TIT_BE; here also BDF2)
 //   (mesh.u / mesh.lambda)      setLameParam(u, lambda) -> dotmi_set_lame     a material change on the built stepper (nT each)
 //   saveStatus()                saveStatus(path)      -> status<n> text format (Optimizer.cpp:1096-1132)
 #pragma once
@@ -67,6 +68,10 @@ struct Options {  // the Config fields the DOT stepper reads (src/Config.hpp)
     // the same term in DOT's own block preconditioner, M' = M + Z A0^-1 Z^T (dotmi_set_dot_coarse): off by default
     // (an int: 0 off, 1 the additive form, 2 the balanced form M'' = C + (I - C H) M (I - H C), C = Z A0^-1 Z^T; `true` is mode 1)
     int dotCoarse = 0;
+    // Config::timeIntegrationType (the reference's enum has TIT_BE alone): DOTMI_TIT_BE, or DOTMI_TIT_BDF2 -- variable-step BDF2, second
+    // order, on every stepper above (dotmi_set_time_integration).  The first step, and the first one after restoreState, is a
+    // backward-Euler step: status<n> carries one level
+    int timeIntegration = DOTMI_TIT_BE;
 };
 
 class DotHipTimeStepper {
@@ -142,6 +147,14 @@ public:
         if (opt_.pcgCoarse) check(dotmi_set_pcg_coarse(h_, 1), "set_pcg_coarse");
         if (opt_.dotCoarse == 2) check(dotmi_set_dot_coarse_mode(h_, 2), "set_dot_coarse_mode");
         else if (opt_.dotCoarse) check(dotmi_set_dot_coarse(h_, opt_.dotCoarse), "set_dot_coarse");
+        if (opt_.timeIntegration != DOTMI_TIT_BE) check(dotmi_set_time_integration(h_, opt_.timeIntegration), "set_time_integration");
+    }
+    // the integrator of the next steps on a built stepper: DOTMI_TIT_BE / DOTMI_TIT_BDF2 (dotmi_set_time_integration)
+    void setTimeIntegration(int kind)
+    {
+        require_built("setTimeIntegration");
+        check(dotmi_set_time_integration(h_, kind), "set_time_integration");
+        opt_.timeIntegration = kind;
     }
     // the coarse term of DOT's block preconditioner on a built stepper: 0 off, 1 rigid modes, 2 rigid modes balanced (dotmi_set_dot_coarse_mode)
     void setDotCoarse(int mode)

@@ -15,7 +15,7 @@
 //
 // usage: dot_hip 100 <script.txt> [--mesh-root DIR] [--parts N] [--energy FCR|SNH] [--epart raw.i32]
 //                [--frames K] [--out DIR] [--device D] [--no-files] [--dump-scene K] [--dump-config] [--dump-formats DIR]
-//                [--echo-config FILE] [--fast] [--newton-pcg N [--pcg-coarse]] [--dot-coarse | --dot-coarse-balanced] [--snh-log]
+//                [--echo-config FILE] [--fast] [--newton-pcg N [--pcg-coarse]] [--dot-coarse | --dot-coarse-balanced] [--snh-log] [--bdf2]
 //        dot_hip --write-info FILE nV nT steps iters t0..t21
 #include <algorithm>
 #include <chrono>
@@ -48,7 +48,7 @@ int main(int argc, char **argv)
     }
     if (argc < 3) {
         std::fprintf(stderr, "usage: %s 100 <script.txt> [--mesh-root DIR] [--parts N] [--energy FCR|SNH] "
-                             "[--epart raw.i32] [--frames K] [--out DIR] [--device D] [--no-files] [--dump-scene K] [--dump-config] [--dump-formats DIR] [--fast] [--newton-pcg N [--pcg-coarse]] [--dot-coarse | --dot-coarse-balanced] [--snh-log]\n", argv[0]);
+                             "[--epart raw.i32] [--frames K] [--out DIR] [--device D] [--no-files] [--dump-scene K] [--dump-config] [--dump-formats DIR] [--fast] [--newton-pcg N [--pcg-coarse]] [--dot-coarse | --dot-coarse-balanced] [--snh-log] [--bdf2]\n", argv[0]);
         return 2;
     }
     if (std::string(argv[1]) != "100") {
@@ -58,7 +58,7 @@ int main(int argc, char **argv)
     const std::string scriptPath = argv[2];
     std::string meshRoot = ".", outDir, epartFile, energyOverride;
     int partsOverride = -1, frames = -1, device = 0, dumpScene = -1, newtonPcgParts = 0;
-    bool files = true, dumpConfig = false, fast = false, pcgCoarse = false, snhLog = false;
+    bool files = true, dumpConfig = false, fast = false, pcgCoarse = false, snhLog = false, bdf2 = false;
     int dotCoarse = 0;   // --dot-coarse: 1, --dot-coarse-balanced: 2 (the mode of dotmi_set_dot_coarse_mode)
     std::string dumpFormats, echoConfig;
     for (int i = 3; i < argc; ++i) {
@@ -90,6 +90,10 @@ int main(int argc, char **argv)
         // SNH_WITHLOG runs for the same script.  The reference chooses it at compile time, so it is no script token and
         // config.txt keeps echoing `energy SNH`
         else if (a == "--snh-log") snhLog = true;
+        // any stepper: BDF2 in place of backward Euler (DOTMI_TIT_BDF2).  The reference's `timeIntegration` token knows only `BE`, so this
+        // is no script token either and config.txt is unchanged; status<n> keeps the reference's format (one level), so a `restart`
+        // under --bdf2 begins with a backward-Euler start step
+        else if (a == "--bdf2") bdf2 = true;
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     try {
@@ -229,6 +233,7 @@ int main(int argc, char **argv)
         }
         opt.lbfgsPD = lbfgsPD;
         opt.lbfgsHI = lbfgsHI;
+        opt.timeIntegration = bdf2 ? DOTMI_TIT_BDF2 : DOTMI_TIT_BE;
         opt.dotCoarse = dotCoarse;   // (refused by the library on every stepper but DOT's own, with its message)
         // `timeStepper LBFGSJH <n>`: block-Jacobi on a vertex partition (the reference takes METIS::partMesh_nodes;
         // without METIS a vertex goes to the lowest-numbered subdomain among its elements) and a unit first step
@@ -275,6 +280,7 @@ int main(int argc, char **argv)
         }
         std::printf("setup %.3f s, nV %d nT %d, %d subdomains, tol %.6e\n", now_s() - tSetup, mesh.nV(), mesh.nT(), nParts, ts.getTargetGRes());
 
+        if (bdf2) std::printf("time integration: BDF2 (the first step is a backward-Euler step)\n");
         if (lbfgsHI) {
             int32_t colours = 0, attempts = 0;
             double shift = 0;

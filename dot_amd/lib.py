@@ -35,6 +35,9 @@ FLAG_DOT_COARSE = 4096   # the coarse term of setDotCoarse(1) from create on; th
 # FLAG_NEWTON_PCG's step on sharded handles (world > 1, FLAG_FORCE_DIST): a flag of its own, as it adds collectives.  Under the header's
 # full name: the FLAG_* names above are the flags up to FLAG_DOT_COARSE, which tests/test_dot_coarse_sharded_host.py pins as the highest of them
 DOTMI_FLAG_NEWTON_PCG_DIST = 8192
+# enum dotmi_time_integration_kind
+TIT_BE = 0
+TIT_BDF2 = 1
 
 
 class Mesh(C.Structure):
@@ -87,6 +90,8 @@ EXPORTS = [
     "dotmi_solve_hessian", "dotmi_set_pcg", "dotmi_pcg_info",
     "dotmi_set_pcg_coarse", "dotmi_pcg_coarse_info", "dotmi_pcg_coarse_matrix", "dotmi_pcg_apply_precond", "dotmi_plan_coarse",
     "dotmi_set_dot_coarse", "dotmi_dot_coarse_info", "dotmi_set_dot_coarse_mode", "dotmi_dot_coarse_mode", "dotmi_plan_coarse_hz",
+    "dotmi_set_time_integration", "dotmi_time_integration", "dotmi_time_integration_info", "dotmi_get_history", "dotmi_set_history",
+    "dotmi_plan_time_integration",
 ]
 
 _lib = None
@@ -188,6 +193,14 @@ def load() -> C.CDLL:
         L.dotmi_dot_coarse_mode.argtypes = [H]
         L.dotmi_dot_coarse_mode.restype = C.c_int32
         L.dotmi_plan_coarse_hz.argtypes = [C.c_int32, C.c_int32, c_ip, c_ip, C.c_int32] + [c_ip] * 8
+    if hasattr(L, "dotmi_set_time_integration"):   # (guarded like the ones around it: a DOTMI_LIBRARY build from before BDF2)
+        L.dotmi_set_time_integration.argtypes = [H, C.c_int32]
+        L.dotmi_time_integration.argtypes = [H]
+        L.dotmi_time_integration.restype = C.c_int32
+        L.dotmi_time_integration_info.argtypes = [H, c_ip, c_ip, c_dp, c_dp]
+        L.dotmi_get_history.argtypes = [H, c_dp, c_dp, c_dp]
+        L.dotmi_set_history.argtypes = [H, c_dp, c_dp, C.c_double]
+        L.dotmi_plan_time_integration.argtypes = [C.c_int32, C.c_double, C.c_double, C.c_int32, c_dp, c_dp, c_dp, c_dp]
     L.dotmi_plan_layout.argtypes = [C.c_int32, C.c_int32, c_ip, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32,
                                     C.c_int32, C.c_int32, C.c_int32, c_ip, c_ip, c_ip, c_ip]
     if hasattr(L, "dotmi_plan_backsolve_tiles"):   # (round 5 entry; guarded like the two above -- ADVICE r05)

@@ -49,6 +49,9 @@ class Config:
     # Not a script token: the reference chooses the log-regularised Stable Neo-Hookean form at compile time (SNH_WITHLOG,
     # Utils/Types.hpp:36), so it stands beside the script.  Turns `energy SNH` into ENERGY_SNH_LOG; an error with FCR.
     snh_log: bool = False
+    # Not a script token either: the reference's `timeIntegration` lookup knows only `BE` (Config.cpp), so BDF2 stands beside the
+    # script like snh_log.  DOTTimeStepper switches its handle to DOTMI_TIT_BDF2 (dotmi_set_time_integration).
+    bdf2: bool = False
 
     @property
     def energy_id(self) -> int:

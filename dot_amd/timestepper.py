@@ -99,6 +99,8 @@ class DOTTimeStepper:
         self._h = h
         self._L = L
         self.last_stats: Optional[StepStats] = None
+        if cfg.bdf2:
+            self.setTimeIntegration(_lib.TIT_BDF2)
 
     def _per_element(self, a, const, name):
         if a is None and const is None:
@@ -181,6 +183,36 @@ class DOTTimeStepper:
         self.dt = dt
         self.frameAmt = int(duration / dt)
 
+    def setTimeIntegration(self, kind: int):
+        """_lib.TIT_BE or _lib.TIT_BDF2 for the next steps (dotmi_set_time_integration; Config::timeIntegrationType, whose enum has
+        TIT_BE alone in the reference).  A switch to BDF2 starts with a backward-Euler step; so does setState under BDF2."""
+        self._check(self._L.dotmi_set_time_integration(self._h, kind), "set_time_integration")
+
+    def timeIntegration(self) -> int:
+        return int(self._L.dotmi_time_integration(self._h))
+
+    def timeIntegrationInfo(self):
+        """(kind, levels: 1 when level n-1 exists, else the next step is a start step; the effective step dt_e the next step's launches
+        take; the size of the step between the two levels, 0 without) (dotmi_time_integration_info)"""
+        k, lv, de, dp_ = C.c_int32(), C.c_int32(), C.c_double(), C.c_double()
+        self._check(self._L.dotmi_time_integration_info(self._h, C.cast(C.byref(k), _lib.c_ip), C.cast(C.byref(lv), _lib.c_ip),
+                                                        C.cast(C.byref(de), _lib.c_dp), C.cast(C.byref(dp_), _lib.c_dp)),
+                    "time_integration_info")
+        return k.value, lv.value, de.value, dp_.value
+
+    def getHistory(self):
+        """BDF2's level n-1: (x_prev (nV,3), v_prev (nV,3), dt_prev), or None while there is none (dotmi_get_history)"""
+        xp, vp = np.empty((self.nV, 3)), np.empty((self.nV, 3))
+        dtp = C.c_double()
+        n = self._check(self._L.dotmi_get_history(self._h, dp(xp), dp(vp), C.cast(C.byref(dtp), _lib.c_dp)), "get_history")
+        return (xp, vp, dtp.value) if n else None
+
+    def setHistory(self, x_prev, v_prev, dt_prev: float):
+        """level n-1 of a BDF2 handle after setState: the next step is a BDF2 step, not a start step (dotmi_set_history)"""
+        xp = np.ascontiguousarray(x_prev, dtype=np.float64)
+        vp = np.ascontiguousarray(v_prev, dtype=np.float64)
+        self._check(self._L.dotmi_set_history(self._h, dp(xp), dp(vp), dt_prev), "set_history")
+
     def setLame(self, mu, lam):
         """per-element Lame parameters, shape (nT,) each (dotmi_set_lame); the factors are refreshed at the current positions"""
         mu = self._per_element(mu, None, "mu")
@@ -189,7 +221,7 @@ class DOTTimeStepper:
         self._mu, self._lam = mu, lam
 
     def solve(self, maxIter: int = 1) -> int:
-        """Optimizer::solve (Optimizer.cpp:327-368): script move, one BE step. 0 stepped, 1 all frames
+        """Optimizer::solve (Optimizer.cpp:327-368): script move, one time step (BE, or BDF2 after setTimeIntegration). 0 stepped, 1 all frames
         done, 2 stepped but hit the iteration cap / line-search failure."""
         flag = 0
         for _ in range(maxIter):

@@ -443,9 +443,47 @@ int dotmi_set_time_step(dotmi_handle *h, double dt);                            
  * everywhere: as two kernel arguments, like create), then the refresh as above and its return code */
 int dotmi_set_lame(dotmi_handle *h, const double *mu, const double *lambda);     /* nT each; dor_set_lame */
 
+/* ---- time integration --------------------------------------------------------------------------- */
+/* The reference carries Config::timeIntegrationType and switches on it at the velocity update (Optimizer.cpp:354-361), the predictor
+ * (:588-610), the energy (:1188) and the gradient (:1225); its enum has the one entry TIT_BE.  DOTMI_TIT_BDF2 is the second: variable-step
+ * BDF2, second order and L-stable.  With w = dt / dt_prev, gamma = (1 + w) / (1 + 2 w), c0 = (1 + w)^2 / (1 + 2 w), c1 = w^2 / (1 + 2 w)
+ * (w = 1: 2/3, 4/3, 1/3) and x^ = c0 x_n - c1 x_{n-1}, v^ = c0 v_n - c1 v_{n-1}, a BDF2 step is the backward-Euler step of the
+ * effective size dt_e = gamma dt from (x^, v^): x~ = x^ + dt_e v^ + dt_e^2 g on free vertices (fixed ones: their position), the same
+ * incremental potential with dt_e for dt, v+ = (x+ - x^) / dt_e on all vertices -- bit for bit what a backward-Euler handle at dt_e
+ * computes from dotmi_set_state(x^, v^, NULL).  Energy, gradient, Hessian, factors, tolerance, every stepper's loop, the coarse terms
+ * and sharding see dt_e only; only the predictor and the update are BDF2's own (dot_amd/csrc/time_integration.hpp, k_timeint.hip).
+ * The first step of a run and the first step after dotmi_set_state have no level n-1: they are backward-Euler steps at dt. */
+enum dotmi_time_integration_kind { DOTMI_TIT_BE = 0, DOTMI_TIT_BDF2 = 1 };
+/* The integrator of the next steps, on a live handle between two steps (the default is DOTMI_TIT_BE; setting the kind the handle has
+ * does nothing at all).  A switch to BDF2 starts with a backward-Euler step at dt (a backward-Euler handle keeps no level n-1); a switch
+ * back to backward Euler drops the level.  Where the switch changes the effective step, x~ and what was built with dt are redone as by
+ * dotmi_set_time_step, whose return codes these entries share.  Any other id: DOTMI_E_INVALID.  Under BDF2
+ *   dotmi_set_time_step   is the variable-step rule with w = dt / dt_prev, not a restart;
+ *   dotmi_set_state       drops level n-1: the next step is a start step (dotmi_set_history afterwards gives the level back);
+ *   dotmi_get_state       returns BDF2's v and the x~ of the next step;
+ *   dotmi_target_gres     is the tolerance at the next step's effective step.
+ * On a sharded handle every rank calls it alike (every rank holds whole x and v: nothing is exchanged). */
+int dotmi_set_time_integration(dotmi_handle *h, int32_t kind);                  /* Config::timeIntegrationType, Optimizer.cpp:354-361 */
+int32_t dotmi_time_integration(const dotmi_handle *h);                          /* the kind; DOTMI_E_INVALID for NULL */
+/* the kind, whether level n-1 exists (0 / 1: 0 = the next step is a start step), the effective step the next step's launches take and
+ * the size of the step that led from level n-1 to level n (0 without the level).  Any pointer may be NULL. */
+int dotmi_time_integration_info(const dotmi_handle *h, int32_t *kind, int32_t *levels, double *dt_eff, double *dt_prev);
+/* Level n-1 of a BDF2 handle, for a restart that continues with a BDF2 step instead of a start step (Optimizer::saveStatus carries
+ * one level only, Optimizer.cpp:1096-1177): dotmi_get_history returns the number of stored levels (0: nothing written but *dt_prev = 0;
+ * 1: x_prev, v_prev, nV*3 each, and the step size between the two levels; any pointer may be NULL).  dotmi_set_history on a BDF2 handle,
+ * after dotmi_set_state: the level, then x^, x~ and the refresh at the effective step as above.  DOTMI_E_INVALID for NULL arrays, a
+ * non-positive or non-finite dt_prev, and on a backward-Euler handle. */
+int dotmi_get_history(dotmi_handle *h, double *x_prev, double *v_prev, double *dt_prev);
+int dotmi_set_history(dotmi_handle *h, const double *x_prev, const double *v_prev, double dt_prev);          /* Optimizer.cpp:588-610 */
+/* (host only) the rule of one step from (kind, dt, dt_prev, levels in {0, 1}): x^ = c0 x_n - c1 x_{n-1}, dt_eff = gamma dt; backward
+ * Euler and levels = 0 give (1, 0, 1, dt).  Any output may be NULL.  tests/test_bdf2_reference.py */
+int dotmi_plan_time_integration(int32_t kind, double dt, double dt_prev, int32_t levels, double *c0, double *c1, double *gamma,
+                                double *dt_eff);                                                              /* Optimizer.cpp:1188, :1225 */
+
 /* ---- the hot path ----------------------------------------------------------------------------- */
-/* One backward-Euler step = Optimizer::solve(1) minus the script move:
- * DOTTimeStepper::fullyImplicit (DOTTimeStepper.cpp:273-346) + BE update (Optimizer.cpp:354-361). */
+/* One time step = Optimizer::solve(1) minus the script move:
+ * DOTTimeStepper::fullyImplicit (DOTTimeStepper.cpp:273-346) + BE update (Optimizer.cpp:354-361); under DOTMI_TIT_BDF2 the BDF2
+ * predictor and update around the same loop. */
 int dotmi_step(dotmi_handle *h, dotmi_step_stats *stats);
 /* per-iteration (alpha, E, ||g||^2) of the last step = iterStats.txt rows (DOTTimeStepper.cpp:304,329) */
 int dotmi_last_iter_log(const dotmi_handle *h, int32_t cap, double *alpha, double *E, double *g2);
